@@ -6,9 +6,15 @@ One "step" = one pass of the hot path over one batch: RanSlice.step for 4096 env
 actions generated on the device.  Inputs (fading tables, simulator state, actions) are resident
 in HBM when the timed region starts; nothing crosses PCIe inside it.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: spawns its own N ranks)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]     (N > 1: spawns its own N ranks)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs: set-up and burn-in, W warm-up steps, K timed steps, the result line (with the
+roofline of the timed launches).  --full adds everything else below: the CPU baseline, config 3 (`kbrl`), config 4
+(`shared_kbrl`) and the full record.  --dump-outputs DIR writes what the last timed step returned to a caller of the path
+(VecRanSlice.fetch: actions, obs, reward, labels, violations) as DIR/<name>.npy in float32 / float64 (DIR/<name>_rank<r>.npy
+for N > 1); the inputs are seeded, so the same arguments give the same inputs on every run.
 
 No torch here: the library's own rs_device_count / rs_synchronize, and for N > 1 a plain TCP group on 127.0.0.1
 (tools/rank_group.py: barrier, MAX of the elapsed time) found through RANK / WORLD_SIZE / LOCAL_RANK / MASTER_PORT,
@@ -16,9 +22,9 @@ whoever launched the ranks.  Replicas are independent, so GPUs shard them with n
 4096 replicas per GPU).
 
 OUTPUT.  The LAST stdout line is the compact record (< 4 KB): metric, value, ms_per_step, config, roofline (with the
-kernel's real limiter beside the HBM figure), cpu_baseline, and the summaries `kbrl` (config 3) and `shared_kbrl` (config 4:
-the RCCL exchange).  The full record (every sub-record at length) goes to profiles/bench_full_last.json and is printed on an
-EARLIER line that starts with "# full record: ".
+kernel's real limiter beside the HBM figure), and with --full cpu_baseline and the summaries `kbrl` (config 3) and
+`shared_kbrl` (config 4: the RCCL exchange).  With --full the full record (every sub-record at length) goes to
+profiles/bench_full_last.json and is printed on an EARLIER line that starts with "# full record: ".
 
 Before the W warm-up steps the environments are advanced until the UE population is stationary: blocks of 500
 steps (25 s of simulated time; the holding times have a 30 s mean) until the mean number of UEs per slice changes
@@ -350,7 +356,7 @@ def run_scaling(args):
             curve.append({'n_gpus': n, 'skipped': 'the box has %d GPU(s)' % ndev})
             continue
         cmd = [sys.executable, os.path.abspath(__file__), '--gpus', str(n), '--steps', str(args.steps), '--warmup',
-               str(args.warmup), '--envs-per-gpu', str(args.envs_per_gpu), '--no-cpu-baseline', '--no-kbrl']
+               str(args.warmup), '--envs-per-gpu', str(args.envs_per_gpu), '--no-cpu-baseline', '--no-kbrl', '--full']
         if n == 1 or args.no_shared:
             cmd += ['--no-shared']
         if args.burn_in >= 0:
@@ -595,10 +601,10 @@ def compact_line(full):
 
 
 def spawn_ranks(args):
-    """python bench.py --gpus N outside any launcher: time the CPU baseline here, then start one rank per GPU (this script
+    """python bench.py --gpus N outside any launcher: time the CPU baseline here (--full), then start one rank per GPU (this script
     again, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in the environment as torch.distributed.run sets them)"""
     cpu_file = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cpu_file = os.path.join('/tmp', 'bench_cpu_%d.json' % os.getpid())
         with open(cpu_file, 'w') as f:
             json.dump(cpu_baseline(1000, args.cpu_steps), f)
@@ -647,7 +653,13 @@ def main():
     ap.add_argument('--cpu-baseline-json', default=None, help=argparse.SUPPRESS)
     ap.add_argument('--scaling', default='', help='e.g. 1,2,4,8: run every N in turn and print ONE line with the curve and '
                                                   'the CPU baseline (Ns beyond the devices of the box are skipped)')
+    ap.add_argument('--full', action='store_true',
+                    help='beside the headline: CPU baseline, config 3 and config 4 legs, full record in profiles/bench_full_last.json')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help="write the last timed step's outputs (actions, obs, reward, labels, violations) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.scaling:
         run_scaling(args)
         return
@@ -673,7 +685,7 @@ def main():
         if args.cpu_baseline_json and os.path.exists(args.cpu_baseline_json):
             with open(args.cpu_baseline_json) as f:
                 cpu_base = json.load(f)
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             cpu_base = cpu_baseline(cpu_burn, args.cpu_steps)
 
     from rank_group import RankGroup
@@ -761,6 +773,12 @@ def main():
     t1 = time.perf_counter()
 
     c1 = env.counters()
+    if args.dump_outputs:
+        # fetched here: the kernel-timing pass of --graph below runs 100 more steps
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in env.fetch().items():
+            a = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+            np.save(os.path.join(args.dump_outputs, name + ('_rank%d' % rank if world > 1 else '') + '.npy'), a)
     if args.graph:
         env.set_kernel_timing(True)
         run(100)
@@ -859,7 +877,7 @@ def main():
             'burn_in_history_mean_ues': burn_hist,
         }
         full['cpu_baseline'] = cpu_base
-        if world == 1 and not args.no_kbrl:
+        if args.full and world == 1 and not args.no_kbrl:
             try:
                 # config 3 on the 'tdl' synthetic trace profile (tapped delay lines, the construction of the ns-3 traces the
                 # reference was run on; the profile the reference comparison of DESIGN.md section 7 was recorded on);
@@ -871,7 +889,7 @@ def main():
                 full.setdefault('kbrl', {'error': repr(e)[:300]})
 
     # ---- config 4: the exchange over RCCL, every rank's child process under a timeout (a failure stays inside the sub-record)
-    if not args.no_shared:
+    if args.full and not args.no_shared:
         tag = '%s_%d' % (os.environ.get('MASTER_PORT', '0'), os.getppid() if world > 1 else os.getpid())
         try:
             sh = run_shared_leg(args, rank, local_rank, world, tag)
@@ -886,13 +904,17 @@ def main():
     group.close()
 
     if full is not None:
-        try:
-            with open(os.path.join(ROOT, 'profiles', 'bench_full_last.json'), 'w') as f:
-                json.dump(full, f, indent=1)
-        except OSError:
-            pass
-        print('# full record: ' + json.dumps(full), flush=True)
-        print(json.dumps(compact_line(full)), flush=True)
+        line = compact_line(full)
+        if args.full:
+            try:
+                with open(os.path.join(ROOT, 'profiles', 'bench_full_last.json'), 'w') as f:
+                    json.dump(full, f, indent=1)
+            except OSError:
+                pass
+            print('# full record: ' + json.dumps(full), flush=True)
+        else:
+            line.pop('full_record', None)
+        print(json.dumps(line), flush=True)
 
 
 if __name__ == '__main__':

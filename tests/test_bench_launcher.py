@@ -35,7 +35,7 @@ def test_gpus_n_spawns_one_rank_per_gpu(monkeypatch, gpus):
                                                                    'kind': 'port', 'sample': 'stub'})
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         monkeypatch.delenv(k, raising=False)
-    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', str(gpus), '--steps', '7', '--warmup', '3'])
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', str(gpus), '--steps', '7', '--warmup', '3', '--full'])
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert e.value.code == 0
@@ -43,13 +43,72 @@ def test_gpus_n_spawns_one_rank_per_gpu(monkeypatch, gpus):
     ports = set()
     for r, (cmd, env) in enumerate(seen):
         assert cmd[0] == sys.executable and cmd[1] == os.path.join(ROOT, 'bench.py')
-        assert cmd[2:8] == ['--gpus', str(gpus), '--steps', '7', '--warmup', '3']
+        assert cmd[2:9] == ['--gpus', str(gpus), '--steps', '7', '--warmup', '3', '--full']
         assert '--cpu-baseline-json' in cmd            # rank 0 reads the baseline this process timed before launching
         assert env['RANK'] == str(r) and env['LOCAL_RANK'] == str(r) and env['WORLD_SIZE'] == str(gpus)
         assert env['MASTER_ADDR'] == '127.0.0.1' and int(env['MASTER_PORT']) > 0
         assert env.get('HSA_ENABLE_IPC_MODE_LEGACY') == '0'
         ports.add(env['MASTER_PORT'])
     assert len(ports) == 1
+
+
+def test_plain_run_times_no_cpu_baseline(monkeypatch):
+    """without --full `bench.py --gpus N` neither times the CPU baseline nor asks its ranks to: a plain run does what the
+    headline needs"""
+    bench = _load_bench()
+    seen = []
+
+    class FakeProc:
+        def wait(self):
+            return 0
+
+    def no_baseline(burn, timed):
+        raise AssertionError('a plain run timed the CPU baseline')
+    monkeypatch.setattr(bench.subprocess, 'Popen', lambda cmd, env=None: seen.append(list(cmd)) or FakeProc())
+    monkeypatch.setattr(bench, 'cpu_baseline', no_baseline)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '2', '--steps', '7', '--warmup', '3', '--dump-outputs', 'out'])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 0 and len(seen) == 2
+    for cmd in seen:
+        assert cmd[2:10] == ['--gpus', '2', '--steps', '7', '--warmup', '3', '--dump-outputs', 'out']
+        assert '--no-cpu-baseline' in cmd and '--cpu-baseline-json' not in cmd and '--full' not in cmd
+
+
+def _plain_bench(out_dir, extra=()):
+    import json
+    import subprocess
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--burn-in', '20',
+           '--envs-per-gpu', '256', '--dump-outputs', str(out_dir)] + list(extra)
+    out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_same_on_every_run(tmp_path):
+    """bench.py --dump-outputs DIR: the last timed step's outputs as float32 / float64 arrays, the same from run to run with the
+    same arguments (the host loop and the hipGraph loop compute the same steps); the line carries ms_per_step of the K steps
+    and nothing of --full"""
+    import numpy as np
+    a = _plain_bench(tmp_path / 'a')
+    b = _plain_bench(tmp_path / 'b')
+    g = _plain_bench(tmp_path / 'g', ['--graph'])
+    for line in (a, b, g):
+        for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+            assert line.get(k) is not None, k
+        assert line['steps'] == 3 and line['ms_per_step'] > 0 and line['cpu_baseline'] is None
+        assert 'kbrl' not in line and 'shared_kbrl' not in line and 'full_record' not in line
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == ['actions.npy', 'labels.npy', 'obs.npy', 'reward.npy', 'violations.npy']
+    for n in names:
+        x = np.load(tmp_path / 'a' / n)
+        assert x.dtype in (np.float32, np.float64) and x.shape[0] == 256, (n, x.dtype, x.shape)
+        for other in ('b', 'g'):
+            assert x.tobytes() == np.load(tmp_path / other / n).tobytes(), (n, other)
+    assert np.isfinite(np.load(tmp_path / 'a' / 'reward.npy')).all()
 
 
 def test_bench_imports_no_torch():

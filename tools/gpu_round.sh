@@ -8,13 +8,13 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 ( timeout 1800 python -m pytest tests -m gpu -q "$@" > $OUT/${TAG}_gputests.txt 2>&1; echo "pytest rc=$?" >> $OUT/${TAG}_gputests.txt )
 tail -5 $OUT/${TAG}_gputests.txt
-( timeout 900 python bench.py > $OUT/${TAG}_bench_stdout.txt 2> $OUT/${TAG}_bench_stderr.txt; echo "bench rc=$?" )
+( timeout 900 python bench.py --full > $OUT/${TAG}_bench_stdout.txt 2> $OUT/${TAG}_bench_stderr.txt; echo "bench rc=$?" )
 tail -1 $OUT/${TAG}_bench_stdout.txt > $OUT/${TAG}_bench_line.json
 wc -c $OUT/${TAG}_bench_line.json
 cat $OUT/${TAG}_bench_line.json
 cp profiles/bench_full_last.json $OUT/${TAG}_bench_full.json 2>/dev/null
 tail -5 $OUT/${TAG}_bench_stderr.txt
-( RANSLICE_BENCH_SHARE_GPU=1 timeout 900 python bench.py --gpus 2 --steps 300 --warmup 50 --burn-in 500 --no-cpu-baseline > $OUT/${TAG}_bench2_stdout.txt 2> $OUT/${TAG}_bench2_stderr.txt; echo "bench2 rc=$?" )
+( RANSLICE_BENCH_SHARE_GPU=1 timeout 900 python bench.py --gpus 2 --steps 300 --warmup 50 --burn-in 500 --no-cpu-baseline --full > $OUT/${TAG}_bench2_stdout.txt 2> $OUT/${TAG}_bench2_stderr.txt; echo "bench2 rc=$?" )
 tail -1 $OUT/${TAG}_bench2_stdout.txt | cut -c1-600
 for n in 8192 16384 65536; do
   timeout 600 python bench.py --no-cpu-baseline --no-kbrl --no-shared --steps 400 --warmup 100 --burn-in 2500 --envs-per-gpu $n --graph 2>/dev/null | tail -1 | python -c "
