@@ -196,6 +196,34 @@ int rs_n_vars(const rs_handle* h);
 int rs_state_bytes(rs_handle* h, uint64_t* bytes);
 int rs_save_state(rs_handle* h, void* blob, uint64_t bytes);
 int rs_load_state(rs_handle* h, const void* blob, uint64_t bytes);
+/* Replica fork (no reference counterpart).  dst replica j := src replica src_index[j] (host array of dst->n_envs entries,
+ * 0 <= index < src->n_envs, repeats allowed).  Same rs_config except n_envs; same device; identical fading tables; src must be
+ * reset.  dst takes src's slot clock and becomes reset.  Stepping dst replica j with action a gives, bit for bit, what stepping
+ * src replica src_index[j] with a would give (every draw is keyed by the replica's seed and counters in its state, never by its
+ * index in the batch).  Copied per replica: the simulator state (per-task and per-UE arrays, VBR bursts, seed, sticky error
+ * flags; the mMTC tables and queues) and the outputs of the last step.  Not copied: the per-task scheduling key and the
+ * diagnostic counters (dst's restart, as after rs_reset); no result depends on either.  Ordered after src's queued work, and
+ * src's later work after the copy; no host synchronisation.  RS_EINVAL: configurations differ or an index is out of range;
+ * RS_ESTATE: src not reset, fading tables not identical, or different devices. */
+int rs_fork(rs_handle* dst, rs_handle* src, const int32_t* src_index);
+/* Lookahead capacity: up to max_branches forked replicas per search launch (at least n_prbs + 1; the library owns the branch
+ * handle, created lazily with h's configuration and reading h's fading tables).  0 frees it. */
+int rs_set_lookahead(rs_handle* h, int max_branches);
+/* One step of every replica under the clairvoyant rule (no reference code; DESIGN.md section "Clairvoyant baseline"): for
+ * each replica the action entries are decided in order s = 0 .. n_act-1; entry s takes the candidate k in [0, R_s],
+ * R_s = n_prbs - (a_0 + ... + a_{s-1}), that minimises (violations[s], k) lexicographically, where violations[s] is what
+ * one step of a fork of the replica gives under the action (a_0 .. a_{s-1}, k, 0 .. 0).  So it is the smallest k that meets
+ * the SLA when one does, else the cheapest among the least-violating.  Then the replica steps for real with
+ * (a_0 .. a_{n_act-1}).  actions_out [n_envs][n_act] (may be NULL) receives the chosen allocation; the other outputs are
+ * rs_step's.  RS_EOVERFLOW also when a capacity was exceeded in one of a replica's branches; RS_ESTATE without lookahead
+ * capacity (rs_set_lookahead) or before rs_reset. */
+int rs_step_clairvoyant(rs_handle* h, int32_t* actions_out, float* obs, double* reward, int32_t* labels,
+                        int32_t* violations);
+/* The rule's second key when no candidate of a slice meets its SLA (a slice with a feasible candidate always takes the
+ * smallest feasible k).  mode 0 (default): the cheapest among the least-violating, as above.  mode 1 ("widest"): the largest
+ * among the least-violating -- a slice that cannot be served within one step gets what is left instead of nothing (the
+ * default starves an mMTC slice whose backlog is already too old for one step to fix, until its queue overflows). */
+int rs_set_clairvoyant_fallback(rs_handle* h, int mode);
 int rs_n_slices(const rs_handle* h);
 const char* rs_last_error(const rs_handle* h);
 void rs_destroy(rs_handle* h);

@@ -145,6 +145,16 @@ struct rs_handle {
     int32_t clock = 0;     // slots since reset (host mirror of d_run[0])
     uint64_t steps = 0;
     bool is_reset = false;
+    // replica fork and clairvoyant search (rs_fork.hip); none of these is a region of the saved state
+    uint64_t fad_hash = 0;       // hash of the fading tables as loaded (rs_fork refuses handles whose tables differ)
+    bool tables_borrowed = false;  // fad / fad_valid / fad32 / fps belong to another handle (a lookahead branch handle)
+    int32_t* d_fork_idx = nullptr;   // [n_envs] source index of rs_fork
+    int32_t* h_fork_idx = nullptr;   // its pinned host staging buffer
+    hipEvent_t ev_fork_in = nullptr, ev_fork_out = nullptr;
+    rs_handle* la = nullptr;     // lookahead branch handle of rs_step_clairvoyant (owned), created lazily
+    int la_max = 0;              // rs_set_lookahead
+    int la_widest = 0;           // rs_set_clairvoyant_fallback
+    int32_t* d_la_err = nullptr; // [n_envs] capacity flags raised in a replica's branches during the last search
     // kernel timing
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
@@ -647,17 +657,22 @@ extern "C" int rs_create(const rs_config* cfg, int device, rs_handle** out) {
     return RS_OK;
 }
 
+static void fork_release(rs_handle* h);
+
 extern "C" void rs_destroy(rs_handle* h) {
     if (!h) return;
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     drop_graph(h);
+    fork_release(h);
     if (guards_on()) check_guards(h->guarded, "rs");
     for (auto& g : h->guarded) (void)hipFree(g.base);
     for (void* p : h->allocs) (void)hipFree(p);
-    if (h->fad) (void)hipFree(h->fad);
-    if (h->fad_valid) (void)hipFree(h->fad_valid);
-    if (h->fad32) (void)hipFree(h->fad32);
-    if (h->fps) (void)hipFree(h->fps);
+    if (!h->tables_borrowed) {
+        if (h->fad) (void)hipFree(h->fad);
+        if (h->fad_valid) (void)hipFree(h->fad_valid);
+        if (h->fad32) (void)hipFree(h->fad32);
+        if (h->fps) (void)hipFree(h->fps);
+    }
     if (h->d_trace) (void)hipFree(h->d_trace);
     for (auto& e : h->ev) {
         (void)hipEventDestroy(e.first);
@@ -695,6 +710,22 @@ extern "C" int rs_device_mem_info(int device, uint64_t* free_bytes, uint64_t* to
 }
 
 // ------------------------------------------------------------------ fading tables
+
+// FNV-1a over the tables as rs_load_fading left them (row count, columns, samples, column flags): rs_fork compares it
+static uint64_t fading_hash(const rs_handle* h) {
+    uint64_t x = 1469598103934665603ull;
+    auto mix = [&x](const void* p, size_t n) {
+        const unsigned char* c = (const unsigned char*)p;
+        for (size_t i = 0; i < n; ++i) x = (x ^ c[i]) * 1099511628211ull;
+    };
+    mix(&h->hdev.P, sizeof h->hdev.P);
+    for (int f = 0; f < RS_N_TRACES; ++f) {
+        mix(&h->hdev.T[f], sizeof h->hdev.T[f]);
+        mix(h->fad_host[f].data(), sizeof(double) * h->fad_host[f].size());
+        mix(h->valid_host[f].data(), h->valid_host[f].size());
+    }
+    return x;
+}
 
 static int upload_fading(rs_handle* h) {
     RsDev& d = h->hdev;
@@ -792,6 +823,7 @@ static int upload_fading(rs_handle* h) {
     }
     HIPCHK(h, hipMemcpyAsync(h->ddev, &d, sizeof d, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->fad_hash = fading_hash(h);
     for (int f = 0; f < RS_N_TRACES; ++f) {
         std::vector<double>().swap(h->fad_host[f]);
         std::vector<uint8_t>().swap(h->valid_host[f]);
@@ -807,6 +839,16 @@ extern "C" int rs_load_fading(rs_handle* h, int trace_id, const double* data, in
     }
     HIPCHK(h, hipSetDevice(h->device));
     drop_graph(h);
+    if (h->tables_borrowed) {
+        h->err = "rs_load_fading: a lookahead branch handle shares its tables";
+        return RS_ESTATE;
+    }
+    if (h->la) {  // the branch handle reads these tables: it is made again, from the new ones, by the next search
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        rs_destroy(h->la);
+        h->la = nullptr;
+    }
+    h->fad_hash = 0;
     const int P = h->cfg.n_prbs > rows ? h->cfg.n_prbs : rows;
     if (h->hdev.P != 0 && h->hdev.P != P) {
         h->err = "rs_load_fading: all traces must have the same number of rows";
@@ -1471,4 +1513,5 @@ extern "C" int rs_load_state(rs_handle* h, const void* blob, uint64_t bytes) {
     h->is_reset = hd.is_reset != 0;
     return RS_OK;
 }
+#include "rs_fork.hip"
 #include "kb_api.hip"

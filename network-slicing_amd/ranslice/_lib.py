@@ -24,6 +24,7 @@ EXPORTS = (
     'rs_create', 'rs_load_fading', 'rs_reset', 'rs_step', 'rs_step_resident', 'rs_random_actions', 'rs_fetch',
     'rs_get_info', 'rs_set_alloc_trace', 'rs_get_alloc_trace', 'rs_get_counters', 'rs_get_rx_stats', 'rs_set_group_size', 'rs_set_schedule_hint', 'rs_get_section_profile', 'rs_get_task_profile', 'rs_run_random', 'rs_kernel_time_ms', 'rs_kernel_time_stats_ms',
     'rs_set_kernel_timing', 'rs_synchronize', 'rs_state_bytes', 'rs_save_state', 'rs_load_state', 'rs_device_count', 'rs_device_mem_info', 'rs_n_vars', 'rs_n_slices', 'rs_last_error', 'rs_destroy',
+    'rs_fork', 'rs_set_lookahead', 'rs_step_clairvoyant', 'rs_set_clairvoyant_fallback',
 ) + KB_EXPORTS
 
 
@@ -107,6 +108,10 @@ def load(dev=None):
     L.rs_last_error.restype = C.c_char_p
     L.rs_destroy.argtypes = [vp]
     L.rs_destroy.restype = None
+    L.rs_fork.argtypes = [vp, vp, ip]
+    L.rs_set_lookahead.argtypes = [vp, C.c_int]
+    L.rs_set_clairvoyant_fallback.argtypes = [vp, C.c_int]
+    L.rs_step_clairvoyant.argtypes = [vp, ip, fp, dp, ip, ip]
     i64p = C.POINTER(C.c_int64)
     L.kb_create.argtypes = [C.POINTER(KbConfig), C.c_int, C.POINTER(vp)]
     L.kb_destroy.argtypes = [vp]

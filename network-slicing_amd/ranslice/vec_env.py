@@ -39,6 +39,7 @@ class VecRanSlice:
         self.n_variables = n_vars(self.cfg)
         self.n_prbs = self.cfg.n_prbs
         self.penalty = self.cfg.penalty
+        self.device = int(device)
         self.h = C.c_void_p()
         rc = self.L.rs_create(C.byref(self.cfg), int(device), C.byref(self.h))
         self._check(rc)
@@ -126,6 +127,47 @@ class VecRanSlice:
 
     def synchronize(self):
         self._check(self.L.rs_synchronize(self.h))
+
+    # ---- replica fork and the clairvoyant step -------------------------------------------
+    def fork_from(self, src, index):
+        """replica j of this env := replica index[j] of `src` (rs_fork): a VecRanSlice of the same configuration but n_envs,
+        the same fading tables and device, reset.  This env takes src's clock; stepping replica j with action a gives, bit for
+        bit, what stepping src replica index[j] with a would.  Enqueued on the device; the host does not wait."""
+        index = np.ascontiguousarray(index, dtype=np.int32)
+        if index.shape != (self.n_envs,):
+            raise ValueError('fork_from: index must have n_envs = %d entries' % self.n_envs)
+        self._check(self.L.rs_fork(self.h, src.h, index.ctypes.data_as(_ip)))
+
+    def set_lookahead(self, max_branches=None):
+        """capacity of the clairvoyant search: forked replicas per search launch (0 frees the branch handle).  Default: as
+        many as a quarter of the free device memory holds at this env's bytes per replica, at most what one launch for the
+        whole batch needs (n_envs x (n_prbs + 1)), at least n_prbs + 1."""
+        if max_branches is None:
+            n = C.c_uint64()
+            self._check(self.L.rs_state_bytes(self.h, C.byref(n)))
+            per_replica = max(1, n.value // self.n_envs)
+            free, _ = _lib.device_mem_info(self.device)
+            cand = self.n_prbs + 1
+            max_branches = int(min(self.n_envs * cand, max(cand, (free // 4) // per_replica)))
+        self._check(self.L.rs_set_lookahead(self.h, int(max_branches)))
+        self._lookahead = int(max_branches)
+
+    def set_clairvoyant_fallback(self, mode):
+        """what a slice with no SLA-meeting candidate gets: 'cheapest' (0, default) or 'widest' (1) of the least-violating"""
+        mode = {'cheapest': 0, 'widest': 1}.get(mode, mode)
+        self._check(self.L.rs_set_clairvoyant_fallback(self.h, int(mode)))
+
+    def step_clairvoyant(self):
+        """one step of every replica under the clairvoyant rule (rs_step_clairvoyant): per replica, slice by slice, the
+        cheapest allocation that meets the SLA in a fork stepped once (else the cheapest least-violating one), then the
+        real step.  Returns (actions, obs, reward, labels, violations)."""
+        if not getattr(self, '_lookahead', 0):
+            self.set_lookahead()
+        actions = np.zeros((self.n_envs, self.n_slices), dtype=np.int32)
+        self._check(self.L.rs_step_clairvoyant(self.h, actions.ctypes.data_as(_ip), self._obs.ctypes.data_as(_fp),
+                                               self._reward.ctypes.data_as(_dp), self._labels.ctypes.data_as(_ip),
+                                               self._viol.ctypes.data_as(_ip)))
+        return actions, self._obs.copy(), self._reward.copy(), self._labels.copy(), self._viol.copy()
 
     # ---- introspection ------------------------------------------------------------------
     def l1_info(self):
