@@ -263,7 +263,9 @@ int kb_create(const kb_config* cfg, int device, kb_handle** out);
 void kb_destroy(kb_handle* k);
 const char* kb_last_error(const kb_handle* k);
 /* KBRL_Control.__init__ state (kbrl_control.py:28-39): initial_action / security_factor [n_envs][S];
- * seeds[n_envs] feed the tie-break stream of GaussianKernel.predict (kernel.py:26-27). */
+ * seeds[n_envs] feed the tie-break stream of GaussianKernel.predict (kernel.py:26-27).  Also clears the hits of the last
+ * learning step, which an inference-mode history column repeats (kb_set_learning): "none yet" reads as zeros.  RS_ESTATE on
+ * an inference-only handle (kb_deploy). */
 int kb_reset(kb_handle* k, const int32_t* initial_action, const int32_t* security_factor, const uint64_t* seeds);
 /* KBRL_Control.update_control(state, action, labels) -> hits (kbrl_control.py:80-114), all agents */
 int kb_update_control(kb_handle* k, const float* state, const int32_t* action, const int32_t* labels, int32_t* hits);
@@ -371,13 +373,48 @@ int kb_repair_times_ms(kb_handle* k, double ms[2], int64_t n[2]);
 int kb_kernel_times_ms(kb_handle* k, double ms[8], int64_t n[8]);
 /* Checkpoint / restore of the agents: the per-learner tables, the control state, the part of the dictionary pool in use and
  * the recorded histories, as one blob (kb_state_bytes waits for the stream and sizes it); kb_load_state takes a blob saved by
- * a handle of the same configuration whose pool is no larger than this handle's. */
+ * a handle of the same configuration whose dictionaries fit this handle's pool.  The flag words travel with the agents; "the
+ * pool was exhausted" (bit 16) is dropped only when this handle's pool is strictly larger than the one the blob came from. */
 int kb_state_bytes(kb_handle* k, uint64_t* bytes);
 int kb_save_state(kb_handle* k, void* blob, uint64_t bytes);
 int kb_load_state(kb_handle* k, const void* blob, uint64_t bytes);
 /* waits for the agent's stream and reports an internal error flag raised by any kernel since kb_reset (the
  * device-resident loop kb_step_resident does not check on its own); dictionaries at capacity are not errors (kb_get_pool) */
 int kb_synchronize(kb_handle* k);
+
+/* ---- agent fork and deployment (one agent per replica only: handles with shared_dictionary == 1 are out of scope and get
+ * RS_EINVAL from all three calls).
+ *
+ * Device-side gather of agents: agent j of dst := agent src_index[j] of src (src_index: host array of dst->n_envs entries,
+ * 0 <= index < src->n_envs, repeats allowed).  Same kb_config except n_envs and pool_bytes; same device; src must be reset.
+ * dst's previous dictionaries are dropped as by kb_reset and dst becomes reset.  Copied per agent: every dictionary in full
+ * (vector pages, Kinv tiles and their partial-sum areas), the per-dictionary tables (sizes, newest-landmark heads, the
+ * off-grid / float32 marks, versions; the owner of the cached kernel row remapped to the new task id), the cached (f, m) of
+ * the last kb_predict, the control state (action, security factors, margins, adjusted, accuracies), the tie-break stream
+ * (seed and counters), the observation the resident loop chose its last action in, and the flag word VERBATIM (a source agent
+ * that found its pool exhausted stays flagged in dst).  Restarted as after kb_reset: the statistics, the repair-work counters,
+ * the launch-order lists and the stored select scores -- no result depends on any of them.  dst's pool layout is an exclusive
+ * scan of the shell sizes in (dictionary, shell) order, so two forks with the same arguments give byte-identical kb_save_state
+ * blobs.  Continuing dst agent j gives, bit for bit, what continuing src agent src_index[j] would.  Ordered after src's queued
+ * work, and src's later work after the gather; the host waits once, for the scan's total.  RS_EINVAL: configurations differ,
+ * an index out of range, a shared-dictionary handle; RS_ESTATE: src not reset, different devices, an inference-only handle on
+ * either side; RS_EOVERFLOW: the dictionaries do not fit dst's pool -- dst is then left reset, with the control state of the
+ * sources and empty dictionaries. */
+int kb_fork(kb_handle* dst, kb_handle* src, const int32_t* src_index);
+/* Creates an INFERENCE-ONLY handle of n agents, agent j := agent src_index[j] of src (a learning handle, or an inference-only
+ * one: a deployed agent can be fanned out again).  Its dictionaries are the vector pages alone (landmarks, coefficients: 15,360
+ * bytes per 64 landmarks; no Kinv), in a pool sized exactly -- 512 bytes + 15,360 x the shells of the chosen dictionaries --
+ * which kb_get_pool reports.  Control state, tie-break stream and flags are copied as by kb_fork.  Learning is permanently
+ * off: kb_step_resident / kb_run_resident / kb_select_action / kb_predict work; kb_update_control, kb_update,
+ * kb_set_learning(k, 1), kb_get_learner with kinv != NULL, kb_save_state, kb_load_state, kb_fork and kb_reset (which would
+ * empty dictionaries that can never be learned again) return RS_ESTATE. */
+int kb_deploy(kb_handle* src, const int32_t* src_index, int32_t n, kb_handle** out);
+/* on = 0: the resident loop (kb_step_resident, each step of kb_run_resident) runs select_action(new obs) only -- the
+ * reference's loop body past learning_time (kbrl_control.py:131-133): dictionaries, accuracies and security factors stay as
+ * they are; margins, adjusted, action and the tie-break counters move as select_action moves them; a history column is still
+ * recorded, its hits repeating those of the last learning step (zeros if there was none since kb_reset / kb_fork).  on = 1
+ * resumes learning.  The host entry points (kb_update_control, ...) are not affected. */
+int kb_set_learning(kb_handle* k, int on);
 
 #ifdef __cplusplus
 }

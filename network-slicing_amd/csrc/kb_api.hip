@@ -64,6 +64,14 @@ struct kb_handle {
     int T = 0, nv = 0;
     bool is_reset = false;
     bool timing = false;
+    bool learning = true;          // kb_set_learning: false = the resident loop selects only (KBRL_Control.run past learning_time)
+    bool frozen = false;           // an inference-only handle (kb_deploy): no Kinv behind its dictionaries, learning permanently off
+    // kb_fork / kb_deploy into this handle (kb_fork.hip)
+    hipEvent_t ev_fork_in = nullptr, ev_fork_out = nullptr;
+    int32_t* d_fork_idx = nullptr;   // [n_envs] source agent of every agent
+    int32_t* h_fork_idx = nullptr;   // pinned staging of the same
+    uint64_t* d_fork_base = nullptr; // [n_dict + 1] first pool double of every dictionary (exclusive scan of its shells' sizes)
+    uint64_t* h_fork_total = nullptr;  // pinned: the scan's total
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
     std::vector<int> ev_kind;  // 0 update phase, 1 select phase; ONE launch of: 2 heavy_matvec_kernel, 3 heavy_rank1_kernel, 4 select_bin_kernel,
                                // 5 heavy_finish_kernel, 6 select_gemm_kernel, 7 update_small_kernel
@@ -219,12 +227,15 @@ extern "C" int kb_comm_info(kb_handle* k, int* rank, int* world) {
     return RS_OK;
 }
 
-extern "C" int kb_create(const kb_config* cfg, int device, kb_handle** out) {
+// frozen_doubles > 0: an inference-only handle whose pool is exactly that many doubles (kb_deploy)
+static int kb_create_impl(const kb_config* cfg, int device, kb_handle** out, unsigned long long frozen_doubles) {
     if (!cfg || !out) return RS_EINVAL;
     kb_handle* k = new kb_handle();
     *out = k;
     k->cfg = *cfg;
     k->device = device;
+    k->frozen = frozen_doubles > 0;
+    k->learning = !k->frozen;
     if (cfg->n_envs <= 0 || cfg->n_slices <= 0 || cfg->n_slices > KB_MAX_SLICES || cfg->n_prbs <= 0 ||
         cfg->n_prbs > KB_NPRB_MAX || cfg->capacity < 2 || cfg->capacity > KB_CAPACITY_MAX) {
         k->err = "kb_create: unsupported configuration (<= 8 learners, n_prbs <= 255, 2 <= capacity <= 65536)";
@@ -271,6 +282,7 @@ extern "C" int kb_create(const kb_config* cfg, int device, kb_handle** out) {
     D.eta = cfg->eta;
     D.shared = cfg->shared_dictionary ? 1 : 0;
     D.tri = D.shared ? 0 : 1;  // one agent per replica: the lower block triangle of Kinv only (kb_kbrl.hip, "Storage")
+    if (k->frozen) D.tri = KB_TRI_NONE;
     D.heavy_m = dev_env("KBRL_HEAVY_M") ? atoi(dev_env("KBRL_HEAVY_M")) : 0;  // developer knob; results do not depend on it
     if (dev_env("KBRL_ROUNDS")) {  // developer knob (tests): that many rounds, always enqueued; results do not depend on it
         k->heavy_rounds = atoi(dev_env("KBRL_ROUNDS"));
@@ -318,7 +330,8 @@ extern "C" int kb_create(const kb_config* cfg, int device, kb_handle** out) {
             if (want > avail) want = avail;
         }
         const unsigned long long least = 64 + (unsigned long long)ND * kb::kb_shell_doubles(0, D.tri);
-        if (want < least) {
+        if (k->frozen) want = frozen_doubles;  // exactly what the deployed dictionaries hold: nothing grows here
+        if (want < least && !k->frozen) {
             k->err = "kb_create: the dictionary pool cannot hold even one shell (48 KB) per dictionary";
             return RS_EINVAL;
         }
@@ -393,6 +406,8 @@ extern "C" int kb_create(const kb_config* cfg, int device, kb_handle** out) {
     return RS_OK;
 }
 
+extern "C" int kb_create(const kb_config* cfg, int device, kb_handle** out) { return kb_create_impl(cfg, device, out, 0); }
+
 static void kb_drop_graph(kb_handle* k) {
     if (k->gexec) (void)hipGraphExecDestroy(k->gexec);
     if (k->graph) (void)hipGraphDestroy(k->graph);
@@ -428,6 +443,12 @@ extern "C" void kb_destroy(kb_handle* k) {
     kb_comm_release(k);
     if (k->d_gather) (void)hipFree(k->d_gather);
     kb_history_release(k);
+    if (k->ev_fork_in) (void)hipEventDestroy(k->ev_fork_in);
+    if (k->ev_fork_out) (void)hipEventDestroy(k->ev_fork_out);
+    if (k->d_fork_idx) (void)hipFree(k->d_fork_idx);
+    if (k->d_fork_base) (void)hipFree(k->d_fork_base);
+    if (k->h_fork_idx) (void)hipHostFree(k->h_fork_idx);
+    if (k->h_fork_total) (void)hipHostFree(k->h_fork_total);
     if (k->h_seen) (void)hipHostFree(k->h_seen);
     if (k->h_total) (void)hipHostFree(k->h_total);
     if (k->stream) (void)hipStreamDestroy(k->stream);
@@ -439,6 +460,10 @@ extern "C" const char* kb_last_error(const kb_handle* k) { return k ? k->err.c_s
 extern "C" int kb_reset(kb_handle* k, const int32_t* initial_action, const int32_t* security_factor,
                         const uint64_t* seeds) {
     if (!k || !initial_action || !security_factor || !seeds) return RS_EINVAL;
+    if (k->frozen) {  // (it would empty dictionaries that can never be learned or loaded again)
+        k->err = "kb_reset: an inference-only handle (kb_deploy) cannot start over: deploy again from a learning handle";
+        return RS_ESTATE;
+    }
     HIPCHK(k, hipSetDevice(k->device));
     const size_t T = (size_t)k->T, N = (size_t)k->cfg.n_envs;
     uint64_t* dseed = nullptr;
@@ -460,6 +485,8 @@ extern "C" int kb_reset(kb_handle* k, const int32_t* initial_action, const int32
     HIPCHK(k, hipMemsetAsync(k->K.fver, 0xFF, sizeof(int32_t) * T, k->stream));  // -1: no stored scores
     HIPCHK(k, hipMemsetAsync(k->d_gstats, 0, sizeof(uint64_t) * 32, k->stream));
     HIPCHK(k, hipMemsetAsync(k->K.hv_work, 0, sizeof(unsigned long long) * 8, k->stream));
+    // (the hits an inference-mode history column repeats: none yet, kb_set_learning)
+    HIPCHK(k, hipMemsetAsync(k->d_hits, 0, sizeof(int32_t) * T, k->stream));
     HIPCHK(k, hipGetLastError());
     HIPCHK(k, hipStreamSynchronize(k->stream));
     if (k->h_seen) k->h_seen[0] = k->h_seen[1] = 0;
@@ -645,6 +672,10 @@ extern "C" int kb_update_control(kb_handle* k, const float* state, const int32_t
         k->err = "kb_update_control: shared-dictionary handles learn through kb_shared_scan/apply/commit";
         return RS_ESTATE;
     }
+    if (k->frozen) {
+        k->err = "kb_update_control: an inference-only handle (kb_deploy) cannot learn: it holds no Kinv";
+        return RS_ESTATE;
+    }
     HIPCHK(k, hipSetDevice(k->device));
     const size_t T = (size_t)k->T, N = (size_t)k->cfg.n_envs;
     for (size_t i = 0; i < T; ++i)
@@ -700,7 +731,9 @@ extern "C" int kb_step_resident(kb_handle* k, rs_handle* env) {
     hipEvent_t done = k->ev_order;
     HIPCHK(k, hipEventRecord(done, env->stream));
     HIPCHK(k, hipStreamWaitEvent(k->stream, done, 0));
-    int rc = launch_update_control(k, k->d_prev_state, env->d_actions, env->d_labels);
+    // inference mode (kb_set_learning(k, 0), or an inference-only handle): KBRL_Control.run past learning_time, kbrl_control.py:131-133
+    // -- the same launches without the update phase; d_hits keeps the last learning step's hits for the history column
+    int rc = k->learning ? launch_update_control(k, k->d_prev_state, env->d_actions, env->d_labels) : RS_OK;
     if (rc != RS_OK) return rc;
     rc = launch_select(k, env->d_obs, env->d_actions);
     if (rc != RS_OK) return rc;
@@ -793,6 +826,14 @@ extern "C" int kb_run_resident(kb_handle* k, rs_handle* env, int n_steps, int us
             k->g_sig = env->launch_sig;
         }
         bool launched = false;
+        if (k->gexec && n_steps - done >= 2) {
+            // The replay runs on the SIMULATOR's stream.  When the cached graph is taken as it is, nothing above has touched the
+            // agent's stream -- but work may be queued there that the loop must follow: kb_fork / kb_deploy make a source's stream
+            // wait for their gather, which reads the dictionaries these steps rewrite.  So the replay joins the agent's stream first.
+            if (!k->ev_order) HIPCHK(k, hipEventCreateWithFlags(&k->ev_order, hipEventDisableTiming));
+            HIPCHK(k, hipEventRecord(k->ev_order, k->stream));
+            HIPCHK(k, hipStreamWaitEvent(env->stream, k->ev_order, 0));
+        }
         while (k->gexec && n_steps - done >= 2) {
             HIPCHK(k, hipGraphLaunch(k->gexec, env->stream));
             env->clock += 2 * env->cfg.slots_per_step;
@@ -819,6 +860,10 @@ static int kb_one(kb_handle* k, int e, int s, const double* x, int y, bool updat
     k->gemm_fresh = false;
     if (!k->is_reset) {
         k->err = "kb_predict/kb_update: call kb_reset first";
+        return RS_ESTATE;
+    }
+    if (update && k->frozen) {
+        k->err = "kb_update: an inference-only handle (kb_deploy) cannot learn: it holds no Kinv";
         return RS_ESTATE;
     }
     HIPCHK(k, hipSetDevice(k->device));
@@ -890,6 +935,10 @@ static int kb_gather(kb_handle* k, int dict, int d, int m, double* landmarks, do
 
 extern "C" int kb_get_learner(kb_handle* k, int e, int s, int32_t* m_out, double* landmarks, double* coeff, double* kinv) {
     if (!k || e < 0 || e >= k->cfg.n_envs || s < 0 || s >= k->cfg.n_slices) return RS_EINVAL;
+    if (kinv && k->frozen) {
+        k->err = "kb_get_learner: an inference-only handle (kb_deploy) holds no Kinv";
+        return RS_ESTATE;
+    }
     HIPCHK(k, hipSetDevice(k->device));
     const size_t dict = k->D.shared ? (size_t)s : (size_t)e * k->cfg.n_slices + s;
     int32_t m = 0;
@@ -1471,10 +1520,12 @@ extern "C" int kb_history_fetch(kb_handle* k, double* reward, int16_t* resources
 // histories of kb_history_begin travel too.
 struct kb_state_header {
     uint64_t magic, n_regions, cfg_hash, pool_doubles_used, hist_steps, total_bytes;
+    uint64_t pool_doubles_cap;  // capacity of the pool the blob was saved from ("pool exhausted" describes THAT pool, kb_load_state)
     int32_t big_par, is_reset, seen0, seen1;
 };
-static const uint64_t kKbStateMagic = 0x4b42534c49434535ull;      // "KBSLICE5": the configuration hash no longer covers the pool's size
-static const uint64_t kKbStateMagicOld = 0x4b42534c49434534ull;   // "KBSLICE4" (rounds 4-5 before that change): refused by name
+static const uint64_t kKbStateMagic = 0x4b42534c49434536ull;      // "KBSLICE6": the header carries the source pool's capacity
+static const uint64_t kKbStateMagicOld = 0x4b42534c49434534ull;   // "KBSLICE4" (rounds 4-5: its hash covered the pool's size): refused by name
+static const uint64_t kKbStateMagic5 = 0x4b42534c49434535ull;     // "KBSLICE5" (a shorter header): refused by name as well
 static uint64_t kb_cfg_hash(const kb_handle* k) {
     uint64_t x = 1469598103934665603ull;
     kb_config c = k->cfg;
@@ -1517,6 +1568,10 @@ extern "C" int kb_state_bytes(kb_handle* k, uint64_t* bytes) {
 extern "C" int kb_save_state(kb_handle* k, void* blob, uint64_t bytes) {
     uint64_t need = 0;
     if (!k || !blob) return RS_EINVAL;
+    if (k->frozen) {
+        k->err = "kb_save_state: an inference-only handle (kb_deploy) has no checkpoint format; deploy it again from its source";
+        return RS_ESTATE;
+    }
     int rc = kb_state_bytes(k, &need);
     if (rc != RS_OK) return rc;
     if (bytes < need) {
@@ -1526,7 +1581,7 @@ extern "C" int kb_save_state(kb_handle* k, void* blob, uint64_t bytes) {
     unsigned long long top = 0;
     if ((rc = kb_pool_used(k, &top)) != RS_OK) return rc;
     kb_state_header hd = {kKbStateMagic, (uint64_t)k->regions.size(), kb_cfg_hash(k), (uint64_t)top, (uint64_t)k->h_steps, need,
-                          k->big_par, k->is_reset ? 1 : 0, k->h_seen ? k->h_seen[0] : 0, k->h_seen ? k->h_seen[1] : 0};
+                          (uint64_t)k->D.pool_doubles, k->big_par, k->is_reset ? 1 : 0, k->h_seen ? k->h_seen[0] : 0, k->h_seen ? k->h_seen[1] : 0};
     memcpy(blob, &hd, sizeof hd);
     char* o = (char*)blob + sizeof hd;
     for (auto& r : k->regions) {
@@ -1545,14 +1600,24 @@ extern "C" int kb_save_state(kb_handle* k, void* blob, uint64_t bytes) {
     return RS_OK;
 }
 extern "C" int kb_load_state(kb_handle* k, const void* blob, uint64_t bytes) {
-    if (!k || !blob || bytes < sizeof(kb_state_header)) return RS_EINVAL;
-    kb_state_header hd;
-    memcpy(&hd, blob, sizeof hd);
-    if (hd.magic == kKbStateMagicOld) {
-        k->err = "kb_load_state: older checkpoint format (KBSLICE4: its configuration hash covered the pool's size); re-create the "
-                 "checkpoint with this build";
+    if (!k || !blob) return RS_EINVAL;
+    if (k->frozen) {
+        k->err = "kb_load_state: an inference-only handle (kb_deploy) takes no checkpoint";
+        return RS_ESTATE;
+    }
+    uint64_t magic = 0;
+    if (bytes >= sizeof magic) memcpy(&magic, blob, sizeof magic);
+    if (magic == kKbStateMagicOld || magic == kKbStateMagic5) {
+        k->err = magic == kKbStateMagicOld
+                     ? "kb_load_state: older checkpoint format (KBSLICE4: its configuration hash covered the pool's size); re-create the "
+                       "checkpoint with this build"
+                     : "kb_load_state: older checkpoint format (KBSLICE5: its header does not say how large the source's pool was); "
+                       "re-create the checkpoint with this build";
         return RS_EINVAL;
     }
+    if (bytes < sizeof(kb_state_header)) return RS_EINVAL;
+    kb_state_header hd;
+    memcpy(&hd, blob, sizeof hd);
     if (hd.magic != kKbStateMagic || hd.n_regions != k->regions.size() || hd.cfg_hash != kb_cfg_hash(k)) {
         k->err = "kb_load_state: the blob was not saved by a handle of this configuration";
         return RS_EINVAL;
@@ -1595,8 +1660,9 @@ extern "C" int kb_load_state(kb_handle* k, const void* blob, uint64_t bytes) {
             HIPCHK(k, hipMemcpy(hp[i], o, part[i], hipMemcpyHostToDevice));
             o += part[i];
         }
-    if (hd.pool_doubles_used < (uint64_t)k->D.pool_doubles) {
-        // "the pool was exhausted" (err bit 16) described the pool the blob came from; this one has room again
+    if (hd.pool_doubles_cap < (uint64_t)k->D.pool_doubles) {
+        // "the pool was exhausted" (err bit 16) described the pool the blob came from: dropped only when this one is strictly
+        // larger -- into a pool of the same size the flag travels with the agents, as it does through kb_fork
         std::vector<int32_t> e((size_t)k->cfg.n_envs);
         HIPCHK(k, hipMemcpy(e.data(), k->K.err, sizeof(int32_t) * e.size(), hipMemcpyDeviceToHost));
         bool any = false;
@@ -1613,5 +1679,22 @@ extern "C" int kb_load_state(kb_handle* k, const void* blob, uint64_t bytes) {
         k->h_seen[1] = hd.seen1;
     }
     k->gemm_fresh = false;
+    return RS_OK;
+}
+
+/* Learning on / off for the resident loop (kb_step_resident, kb_run_resident): off = select_action(new obs) only.  The mode
+ * is host state of the handle; a captured loop is dropped when it changes. */
+extern "C" int kb_set_learning(kb_handle* k, int on) {
+    if (!k) return RS_EINVAL;
+    if (k->D.shared) {
+        k->err = "kb_set_learning: shared-dictionary handles are not supported";
+        return RS_EINVAL;
+    }
+    if (on && k->frozen) {
+        k->err = "kb_set_learning: an inference-only handle (kb_deploy) cannot learn: it holds no Kinv";
+        return RS_ESTATE;
+    }
+    if (k->learning != (on != 0)) kb_drop_graph(k);
+    k->learning = on != 0;
     return RS_OK;
 }

@@ -91,7 +91,8 @@ struct KbDev {
     int32_t first_env; // global id of local replica 0 (shared mode proposals carry global ids)
     int32_t serial_apply; // shared mode: apply a full dictionary's proposals one by one as well (KBRL_SERIAL_APPLY, tests)
     int32_t heavy_m;      // dictionaries of this many landmarks repair their mistakes in update_heavy_kernel
-    int32_t tri;          // 1: only the lower block triangle of Kinv is stored (one agent per replica); 0: both (shared dictionaries)
+    int32_t tri;          // 1: only the lower block triangle of Kinv is stored (one agent per replica); 0: both (shared dictionaries);
+                          // 2: no Kinv stored at all -- an inference-only handle (kb_deploy): a shell is its vector page
     uint64_t pool_doubles;
 };
 
@@ -165,8 +166,15 @@ __host__ __device__ inline int kb_capr(int cap) { return (cap + 63) & ~63; }
 __host__ __device__ inline size_t kb_apply_lds_doubles(int cap, int budget) {  // shared_apply_kernel's dynamic LDS
     return (size_t)kb_capr(cap) + 4 * (size_t)budget;
 }
-__host__ __device__ inline uint64_t kb_shell_doubles(int b, int tri) {  // tri: b + 1 tiles and their 128 partial sums each
+#define KB_TRI_NONE 2  // KbDev.tri of an inference-only handle
+__host__ __device__ inline uint64_t kb_shell_doubles(int b, int tri) {  // tri 1: b + 1 tiles and their 128 partial sums each
+    if (tri == KB_TRI_NONE) return (uint64_t)KB_VEC;
     return (uint64_t)KB_VEC + (tri ? (uint64_t)(b + 1) * (KB_TILE + 128) : (uint64_t)(2 * b + 1) * KB_TILE);
+}
+// doubles of the shells 0 .. b - 1 of one dictionary (tri 1 or KB_TRI_NONE): where shell b starts in a dictionary laid out whole
+__host__ __device__ inline uint64_t kb_shells_before(int b, int tri) {
+    const uint64_t v = (uint64_t)b * KB_VEC;
+    return tri == KB_TRI_NONE ? v : v + (uint64_t)(KB_TILE + 128) * ((uint64_t)b * (uint64_t)(b + 1) / 2);
 }
 
 __device__ __forceinline__ const uint64_t* shells_of(const KbDev& D, const KbState& K, int dict) {

@@ -1515,3 +1515,4 @@ extern "C" int rs_load_state(rs_handle* h, const void* blob, uint64_t bytes) {
 }
 #include "rs_fork.hip"
 #include "kb_api.hip"
+#include "kb_fork.hip"

@@ -109,6 +109,22 @@ class BatchedEvaluator(Evaluator):
         if i + k >= self.steps:
             c['agent'].step_resident(c['env'])    # the last step: update_control + select_action + its history column
 
+    def train(self, runs, device=0, capacity=16384, pool_bytes=32 << 30, graph=GRAPH):
+        """all self.steps steps of the runs, nothing written: -> (agent, env), the trained VecKBRL (its histories recorded:
+        agent.history_fetch()) and its VecRanSlice, for callers that go on with the agents (experiments_trained.py).  The
+        caller ends with release()."""
+        self._setup(runs, device=device, capacity=capacity, pool_bytes=pool_bytes)
+        for i in range(0, self.steps, CHUNK):
+            self._advance(i, min(CHUNK, self.steps - i), graph=graph)
+        return self._ctx['agent'], self._ctx['env']
+
+    def release(self):
+        """closes the handles train() returned"""
+        if getattr(self, '_ctx', None):
+            self._ctx['env'].close()
+            self._ctx['agent'].close()
+            self._ctx = None
+
     def _finish(self, verbose=True):
         c = self._ctx
         env, agent, runs, capacity = c['env'], c['agent'], c['runs'], c['capacity']

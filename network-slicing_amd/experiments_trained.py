@@ -1,0 +1,164 @@
+#!/usr/bin/env python3
+"""The paper's "inference phase" (the reference's plot_trained_results.py: steps 40,000-49,500 of the training runs) done the
+way a trained agent is used: train, freeze, fan out, evaluate.
+
+For each (scenario, accuracy range):
+  1. train --runs KBRL agents for --train-steps steps, run i as replica i of one VecRanSlice + VecKBRL pair (the machinery of
+     experiments_kbrl.BatchedEvaluator: same seeds, same device-resident loop);
+  2. deploy every trained agent --eval-replicas times (VecKBRL.deploy: landmarks and coefficients only, learning off) against
+     fresh environment seeds -- one VecRanSlice of runs x eval-replicas replicas;
+  3. run --eval-steps closed-loop steps in inference mode with the histories on the device;
+  4. write results/scenario_N/KBRL_xx_deployed/evaluation_K.npz per trained run K: violation, resources (int16) and reward
+     (float64), [eval_replicas, eval_steps] -- the keys and dtypes of ranslice.report.VecReportWrapper;
+  5. print mean violations per stage and mean resource occupation with the 95 % t-interval of plot_trained_results.py over the
+     trained agents (each agent's figure is the mean over its replicas), next to the same two numbers from the training runs'
+     own last window -- the reference's method: one trajectory per agent, the agent still learning in the window.
+
+  python experiments_trained.py [--scenarios 0] [--runs 30] [--train-steps 40000] [--eval-replicas 64] [--eval-steps 9500]
+                                [--learning-control]
+"""
+import argparse
+import os
+import time
+from itertools import product
+
+import numpy as np
+from numpy.random import default_rng
+
+import scenario_creator as sc
+from experiments_kbrl import BatchedEvaluator, CHUNK, GRAPH, accuracy_list, name
+
+RUNS = 30
+TRAIN_STEPS = 40000
+EVAL_REPLICAS = 64
+EVAL_STEPS = 9500
+EVAL_SEED0 = 1 << 20   # evaluation replica j is seeded as run EVAL_SEED0 + j would be: disjoint from the training runs' seeds
+
+
+def mean_confidence_radius(data, confidence=0.95):
+    """(mean, half-width of the two-sided Student-t interval) of a sample -- the figure plot_trained_results.py draws its
+    error bars from: t quantile at n - 1 degrees of freedom times the standard error of the mean"""
+    from scipy.stats import t as student_t
+    x = np.asarray(data, dtype=np.float64).ravel()
+    n = x.size
+    radius = student_t.ppf(0.5 + confidence / 2.0, df=n - 1) * x.std(ddof=1) / np.sqrt(n)
+    return float(x.mean()), float(radius)
+
+
+def window_statistics(violation, resources, n_prbs, start=0, end=None, confidence=0.95):
+    """violation, resources: [agents, steps] (a trajectory per agent) or [agents, replicas, steps] (several per agent, averaged
+    first).  -> dict(violations=(mean, radius), occupation=(mean, radius)) over the agents, of the per-agent means over
+    steps start:end -- violations per stage, and resources / n_prbs (plot_trained_results.py:57-62)."""
+    v = np.asarray(violation, dtype=np.float64)[..., start:end]
+    r = np.asarray(resources, dtype=np.float64)[..., start:end]
+    per_agent_v = v.reshape(v.shape[0], -1).mean(axis=1)
+    per_agent_r = r.reshape(r.shape[0], -1).mean(axis=1) / n_prbs
+    return dict(violations=mean_confidence_radius(per_agent_v, confidence), occupation=mean_confidence_radius(per_agent_r, confidence))
+
+
+def eval_seeds(n):
+    return np.array([int(default_rng(seed=EVAL_SEED0 + j).integers(0, 2 ** 63 - 1)) for j in range(n)], dtype=np.uint64)
+
+
+def _fleet_run(agent, scenario, n_replicas, eval_steps, device, graph):
+    """`agent` (one per replica) steers a fresh fleet of n_replicas environments for eval_steps closed-loop steps, the first one
+    under the action the agents last selected; -> the histories.  The fleet's seeds depend on its size alone, so two agents
+    handles run against the same traffic realisations."""
+    from ranslice import config as _c
+    from ranslice.vec_env import VecRanSlice, default_fading
+    fading = sc._FADING if sc._FADING is not None else default_fading()
+    fleet = VecRanSlice(n_envs=n_replicas, cfg=_c.make_config(scenario, n_envs=n_replicas), fading=fading, device=device)
+    fleet.reset(seeds=eval_seeds(n_replicas))
+    agent.history_begin(eval_steps)
+    fleet.enqueue_step(agent.control(with_accuracies=False)['action'])
+    for i in range(0, eval_steps - 1, CHUNK):
+        agent.run_resident(fleet, min(CHUNK, eval_steps - 1 - i), graph=graph)
+    agent.step_resident(fleet)
+    h = agent.history_fetch()
+    fleet.fetch()        # surfaces simulator capacity errors
+    fleet.close()
+    assert h['recorded'] == eval_steps
+    return h
+
+
+def train_and_deploy(scenario, a_range, runs=range(RUNS), train_steps=TRAIN_STEPS, eval_replicas=EVAL_REPLICAS, eval_steps=EVAL_STEPS,
+                     out_dir='./results', device=0, capacity=16384, pool_bytes=32 << 30, graph=GRAPH, verbose=True,
+                     learning_control=False):
+    """one (scenario, accuracy range): writes the evaluation files and returns a summary with both pairs of numbers.
+    learning_control: also run FULL forks of the same agents, learning left on, against the same fresh fleet -- what separates
+    "the agent is frozen" from "the environment is new" in the difference between the two pairs (summary['learning_control'];
+    no files)."""
+    from ranslice.kbrl_dev import VecKBRL, fork_pool_bytes
+    runs = list(runs)
+    n, R = len(runs), int(eval_replicas)
+    n_prbs = sc.scenarios[scenario]['n_prbs']
+    t0 = time.perf_counter()
+    ev = BatchedEvaluator(scenario, a_range, steps=train_steps, out_dir=out_dir)
+    agent, env = ev.train(runs, device=device, capacity=capacity, pool_bytes=pool_bytes, graph=graph)
+    hist = agent.history_fetch()
+    assert hist['recorded'] == train_steps
+    env.fetch()
+    window = min(eval_steps, train_steps)
+    trained = window_statistics(hist['violation'], hist['resources'], n_prbs, start=train_steps - window)
+    sizes = agent.dictionary_sizes()
+    t_train = time.perf_counter() - t0
+    # freeze and fan out: replicas k * R .. k * R + R - 1 carry trained run k
+    t1 = time.perf_counter()
+    index = np.repeat(np.arange(n, dtype=np.int32), R)
+    deployed = agent.deploy(index)
+    pool = deployed.pool()
+    control = None
+    if learning_control:
+        control = VecKBRL(n * R, agent.dims, agent.n_prbs, alfa=sc.alfa, accuracy_range=tuple(a_range), capacity=capacity,
+                          device=device, pool_bytes=fork_pool_bytes(sizes[index]) + pool_bytes)
+        control.fork_from(agent, index)
+        control.synchronize()
+    ev.release()
+    h = _fleet_run(deployed, scenario, n * R, eval_steps, device, graph)
+    t_eval = time.perf_counter() - t1
+    deployed.close()
+    path = '{}/scenario_{}/{}_{}_deployed/'.format(out_dir, scenario, name, int(a_range[0] * 100))
+    os.makedirs(path, exist_ok=True)
+    shape = (n, R, eval_steps)
+    viol, res, rew = h['violation'].reshape(shape), h['resources'].reshape(shape), h['reward'].reshape(shape)
+    for k, i in enumerate(runs):
+        np.savez('{}evaluation_{}.npz'.format(path, i), violation=viol[k], resources=res[k], reward=rew[k])
+    dep = window_statistics(viol, res, n_prbs)
+    summary = dict(scenario=scenario, accuracy_range=list(a_range), runs=n, train_steps=train_steps, eval_replicas=R,
+                   eval_steps=eval_steps, window=window, train_wall_s=t_train, eval_wall_s=t_eval, deployed=dep, training_window=trained,
+                   max_dictionary=int(sizes.max()), mean_dictionary=float(sizes.mean()), deployed_pool_bytes=int(pool['used_bytes']),
+                   path=path)
+    fmt = '{:.4f} +- {:.4f}'
+    if verbose:
+        print('scenario {} KBRL {}: {} agents trained {} steps ({:.1f} s), {} replicas each for {} steps in inference mode ({:.1f} s)'
+              .format(scenario, a_range[0], n, train_steps, t_train, R, eval_steps, t_eval))
+        print('  deployed (frozen, {} unseen traffic realisations per agent): violations per stage {}, resource occupation {}'
+              .format(R, fmt.format(*dep['violations']), fmt.format(*dep['occupation'])))
+        print('  training runs, last {} steps (one trajectory per agent, still learning): violations per stage {}, resource occupation {}'
+              .format(window, fmt.format(*trained['violations']), fmt.format(*trained['occupation'])))
+    if control is not None:
+        t2 = time.perf_counter()
+        hc = _fleet_run(control, scenario, n * R, eval_steps, device, graph)
+        lc = window_statistics(hc['violation'].reshape(shape), hc['resources'].reshape(shape), n_prbs)
+        summary['learning_control'] = dict(lc, wall_s=time.perf_counter() - t2, pool=control.pool())
+        control.close()
+        if verbose:
+            print('  the same agents on the same fleet with learning left on (full forks): violations per stage {}, resource occupation {}'
+                  .format(fmt.format(*lc['violations']), fmt.format(*lc['occupation'])))
+    return summary
+
+
+if __name__ == '__main__':
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--scenarios', type=int, nargs='*', default=[0, 1, 2])
+    ap.add_argument('--runs', type=int, default=RUNS)
+    ap.add_argument('--train-steps', type=int, default=TRAIN_STEPS)
+    ap.add_argument('--eval-replicas', type=int, default=EVAL_REPLICAS)
+    ap.add_argument('--eval-steps', type=int, default=EVAL_STEPS)
+    ap.add_argument('--out', default='./results')
+    ap.add_argument('--learning-control', action='store_true',
+                    help='also run full forks of the agents, learning left on, against the same fresh environments')
+    args = ap.parse_args()
+    for scenario, a_range in product(args.scenarios, accuracy_list):
+        train_and_deploy(scenario, a_range, range(args.runs), train_steps=args.train_steps, eval_replicas=args.eval_replicas,
+                         eval_steps=args.eval_steps, out_dir=args.out, learning_control=args.learning_control)

@@ -18,7 +18,27 @@ _fp = C.POINTER(C.c_float)
 _up = C.POINTER(C.c_uint64)
 
 
+VEC_PAGE_BYTES = 30 * 64 * 8   # one shell of an inference-only handle: the vector page of 64 landmarks (KB_VEC doubles)
+POOL_PREAMBLE_BYTES = 64 * 8   # pool offset 0 means "no shell": every pool starts with 64 unused doubles
+
+
+def deploy_pool_bytes(sizes):
+    """bytes kb_deploy allocates (and kb_get_pool then reports in use) for dictionaries of these sizes: the 512-byte preamble
+    that keeps offset 0 free for "not allocated", plus one 15,360-byte vector page per started 64 landmarks -- no Kinv"""
+    m = np.asarray(sizes, dtype=np.int64)
+    return POOL_PREAMBLE_BYTES + VEC_PAGE_BYTES * int(((m + 63) // 64).sum())
+
+
+def fork_pool_bytes(sizes):
+    """bytes of pool a learning handle needs to take dictionaries of these sizes through fork_from: per shell b of a
+    dictionary one vector page and b + 1 Kinv tiles of 32 KB with their 1 KB partial-sum areas, plus the preamble"""
+    nsh = (np.asarray(sizes, dtype=np.int64) + 63) // 64
+    return POOL_PREAMBLE_BYTES + int((VEC_PAGE_BYTES * nsh + (32768 + 1024) * nsh * (nsh + 1) // 2).sum())
+
+
 class VecKBRL:
+    frozen = False   # True on the inference-only objects deploy() returns
+
     def __init__(self, n_envs, dims, n_prbs, alfa=KBRL_ALFA, accuracy_range=(0.99, 0.999), gamma=KBRL_GAMMA,
                  eta=KBRL_ETA, capacity=4096, device=0, shared=False, first_env=0, pool_bytes=0):
         self.L = _lib.load()
@@ -246,6 +266,39 @@ class VecKBRL:
 
     def synchronize(self):
         self._check(self.L.kb_synchronize(self.h))
+
+    # ---- agent fork, deployment, inference mode --------------------------------------------
+    def fork_from(self, src, index):
+        """agent j of this handle := agent index[j] of `src` (kb_fork): a VecKBRL of the same configuration but n_envs and
+        pool_bytes, on the same device.  Dictionaries (Kinv included), control state, tie-break stream and flags travel;
+        statistics and caches restart.  Continuing agent j gives, bit for bit, what continuing src agent index[j] would."""
+        index = np.ascontiguousarray(index, dtype=np.int32)
+        if index.shape != (self.n_envs,):
+            raise ValueError('fork_from: index must have n_envs = %d entries' % self.n_envs)
+        if src.L is not self.L:
+            raise RuntimeError('the two agents were created from different builds of libranslice')
+        self._check(self.L.kb_fork(self.h, src.h, index.ctypes.data_as(_ip)))
+
+    def deploy(self, index):
+        """-> an inference-only VecKBRL (frozen = True) of len(index) agents, agent j := agent index[j] of this one
+        (kb_deploy): landmarks and coefficients only, in a pool of exactly deploy_pool_bytes(sizes[index]) bytes.  It selects
+        (select_action, step_resident, run_resident) and never learns."""
+        index = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        h = C.c_void_p()
+        self._check(self.L.kb_deploy(self.h, index.ctypes.data_as(_ip), int(index.size), C.byref(h)))
+        d = object.__new__(type(self))
+        d.L, d.h = self.L, h
+        cfg = KbConfig.from_buffer_copy(self.cfg)
+        cfg.n_envs = int(index.size)
+        d.cfg = cfg
+        d.n_envs, d.S, d.n_prbs, d.dims, d.nv, d.capacity = int(index.size), self.S, self.n_prbs, list(self.dims), self.nv, self.capacity
+        d.frozen = True
+        cfg.pool_bytes = d.pool()['total_bytes']
+        return d
+
+    def set_learning(self, on):
+        """on=False: step_resident / run_resident select only (KBRL_Control.run past learning_time); True resumes learning"""
+        self._check(self.L.kb_set_learning(self.h, int(bool(on))))
 
 
 PROP_W = 18  # KB_PROP_WIDTH

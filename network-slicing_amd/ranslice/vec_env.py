@@ -92,6 +92,12 @@ class VecRanSlice:
                 'total_violations': self._viol.sum(axis=1), 'n_prbs': actions.copy()}
         return self._obs.copy(), self._reward.copy(), np.zeros(self.n_envs, dtype=bool), info
 
+    def enqueue_step(self, actions):
+        """step(actions) without reading anything back: the outputs stay on the device for step_resident / VecKBRL.step_resident
+        (the first step of a closed loop, taken under the agents' initial or last selected action)"""
+        actions = np.ascontiguousarray(actions, dtype=np.int32).reshape(self.n_envs, self.n_slices)
+        self._check(self.L.rs_step(self.h, actions.ctypes.data_as(_ip), None, None, None, None))
+
     # ---- device-resident path (bench) --------------------------------------------------
     def random_actions(self, seed, step_index):
         self._check(self.L.rs_random_actions(self.h, int(seed), int(step_index)))
