@@ -225,6 +225,73 @@ int rs_step_clairvoyant(rs_handle* h, int32_t* actions_out, float* obs, double* 
  * default starves an mMTC slice whose backlog is already too old for one step to fix, until its queue overflows). */
 int rs_set_clairvoyant_fallback(rs_handle* h, int mode);
 int rs_n_slices(const rs_handle* h);
+/* ---- device-resident policy interface (no reference counterpart; DESIGN.md section "Device-resident policy interface").
+ * A policy that runs on the same GPU -- a torch module, a kernel of the caller's -- hands its actions over as a device pointer
+ * and reads the outputs of the step in place: no host copy, no host wait.  Action kinds of rs_step_device: */
+#define RS_ACT_PRBS   0   /* int32 [n_envs][n_slices]      PRBs per slice, as rs_step takes them            */
+#define RS_ACT_SHARES 1   /* float [n_envs][n_slices + 1]  ReportWrapper's simplex (wrapper.py:77-82)       */
+#define RS_ACT_INDEX  2   /* int64 [n_envs]                row of the action table (DQNWrapper, wrapper.py:136-154) */
+
+typedef struct rs_device_view {   /* device pointers owned by the handle, valid until rs_destroy */
+    int32_t device, n_envs, n_slices, n_vars;
+    void*    stream;              /* the handle's hipStream_t */
+    /* inputs a caller may fill instead of bringing its own buffer */
+    int32_t* in_prbs;  float* in_shares;  int64_t* in_index;
+    /* the action the last step executed (= the buffer rs_step_resident reads) and its row sum */
+    int32_t* actions;  int32_t* resources;          /* [n_envs][n_slices], [n_envs] */
+    /* outputs of the last step */
+    float*   obs;       float* obs_norm;            /* raw, and clip(obs,-0.5,1.5)-0.5 in float32 (wrapper.py:87-89) */
+    double*  reward;    int32_t* labels;  int32_t* violations;  int32_t* total_violations;   /* [n_envs] */
+    int64_t* rejected;                              /* one counter: action rows refused since rs_reset */
+} rs_device_view;
+
+/* The buffers behind the view that this interface adds (in_*, resources, obs_norm, total_violations, rejected), the action
+ * table and the report histories are created by the first call of this group.  They are NOT part of a checkpoint
+ * (rs_save_state / rs_load_state) and are NOT copied by rs_fork; resources, obs_norm and total_violations are written by
+ * rs_step_device only (rs_step / rs_step_resident leave them as they are). */
+int rs_get_device_view(rs_handle* h, rs_device_view* out);
+/* RanSlice.step for every replica, the actions read from device memory.
+ * Input and stream ordering.  actions_device: any device pointer on the handle's device -- one of the view's in_* buffers or
+ * the caller's own (a torch tensor's data_ptr()), laid out as `kind` says, C-contiguous.  caller_stream: the hipStream_t the
+ * caller produced the actions on and will consume the outputs on; NULL is the null stream (torch's default stream).  The call
+ * records an event on caller_stream, the handle's stream waits for it; then the rows are decoded and validated, the replicas
+ * step, the outputs are post-processed; an event recorded after everything the step queued (the side streams the step forks
+ * and joins included) is waited for by caller_stream.  With caller_stream == the handle's own stream both events are skipped.
+ * THE HOST WAITS FOR NOTHING AND NOTHING IS COPIED TO OR FROM THE HOST: the outputs stay in the view's buffers.
+ * Decoding.  RS_ACT_PRBS: the row as it is.  RS_ACT_SHARES: PRBs_i = floor((n_prbs * |a_i|) / t), t = sum |a| over all
+ * n_slices + 1 entries, t = 1 when that sum is 0, in float64 on the float32 inputs widened exactly and with the row sum taken
+ * in the order numpy takes it over a contiguous axis (left to right below 8 entries; for 8 and 9 entries
+ * ((a0+a1)+(a2+a3))+((a4+a5)+(a6+a7)), then + a8): bit-equal to ranslice.report.simplex_to_prbs on the same C-contiguous
+ * float32 array.  RS_ACT_INDEX: the row is table[idx] (rs_set_action_table).
+ * Validation, on the device (rs_step does it on the host and returns RS_EINVAL).  A row with a negative entry, a sum above
+ * n_prbs, an index outside the table, or shares without an integer image (NaN, infinite) is REFUSED: it is replaced by all
+ * zeros, *rejected is incremented, and the replica steps with the zero allocation exactly as rs_step would with a zero row.
+ * A refused row is never silently mis-sliced.  Capacity overflows stay sticky in the state's error words as ever and surface
+ * at the next rs_fetch (RS_EOVERFLOW).
+ * Schedule hint.  In automatic mode the step-kernel instance is the on-device script's (rs_set_schedule_hint); results do
+ * not depend on it.
+ * Outputs.  Besides rs_step_resident's (obs, reward, labels, violations, l1_info): resources (row sums of the executed
+ * action), obs_norm, total_violations; and, when a report history is open and its cursor is below `steps`, one column of it.
+ * RS_ESTATE before rs_reset, and for RS_ACT_INDEX without a table; RS_EINVAL for an unknown kind. */
+int rs_step_device(rs_handle* h, int kind, const void* actions_device, void* caller_stream);
+/* caller_stream waits for everything queued on the handle so far (e.g. after rs_reset, before reading the view on it) */
+int rs_stream_join(rs_handle* h, void* caller_stream);
+/* The action table of RS_ACT_INDEX: host array [n_actions][n_slices] (n_slices = rs_n_slices(h): one entry per L1 slice on an
+ * L1-multiplexed handle; the width is implied, so a binding that knows the table's shape must refuse any other width --
+ * ranslice.vec_env raises ValueError).  Copied to the device; waits for the steps in flight.  Rows are validated when used. */
+int rs_set_action_table(rs_handle* h, const int32_t* table /* host [n_actions][n_slices] */, int32_t n_actions);
+/* The histories of ReportWrapper (wrapper.py:54-57,106-109) kept on the device, like kb_history_begin: violation int16,
+ * reward f64, resources int16, [n_envs][steps], zeroed.  Every rs_step_device advances a cursor that lives in device memory
+ * and records column `cursor` while cursor < steps.  rs_reset takes the cursor back to 0 and keeps the columns, as
+ * ReportWrapper.reset does.  rs_report_extend is set_evaluation (wrapper.py:125-130): cursor := steps, steps += eval_steps,
+ * the new columns zero.  rs_report_fetch copies the arrays (any may be NULL) and min(cursor, steps) to the host and waits. */
+int rs_report_begin(rs_handle* h, int32_t steps);
+int rs_report_extend(rs_handle* h, int32_t eval_steps);
+int rs_report_fetch(rs_handle* h, int16_t* violation, double* reward, int16_t* resources, int32_t* n_recorded);  /* [n_envs][steps] */
+/* Copy between host memory and device memory of the handle's device, on the handle's stream: ordered after the steps queued so
+ * far.  to_device == 0: device -> host, and the call waits for the copy; otherwise host -> device, without waiting for the
+ * device (the host buffer may be reused when the call returns). */
+int rs_device_copy(rs_handle* h, void* dst, const void* src, uint64_t bytes, int to_device);
 const char* rs_last_error(const rs_handle* h);
 void rs_destroy(rs_handle* h);
 

@@ -155,6 +155,8 @@ struct rs_handle {
     int la_max = 0;              // rs_set_lookahead
     int la_widest = 0;           // rs_set_clairvoyant_fallback
     int32_t* d_la_err = nullptr; // [n_envs] capacity flags raised in a replica's branches during the last search
+    // device-resident policy interface (rs_policy_io.hip), created by its first call; not a region of the saved state either
+    struct PolicyIo* pio = nullptr;
     // kernel timing
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
@@ -658,12 +660,15 @@ extern "C" int rs_create(const rs_config* cfg, int device, rs_handle** out) {
 }
 
 static void fork_release(rs_handle* h);
+static void policy_io_release(rs_handle* h);
+static int policy_io_on_reset(rs_handle* h);
 
 extern "C" void rs_destroy(rs_handle* h) {
     if (!h) return;
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     drop_graph(h);
     fork_release(h);
+    policy_io_release(h);
     if (guards_on()) check_guards(h->guarded, "rs");
     for (auto& g : h->guarded) (void)hipFree(g.base);
     for (void* p : h->allocs) (void)hipFree(p);
@@ -900,6 +905,7 @@ extern "C" int rs_reset(rs_handle* h, const uint64_t* seeds, float* obs) {
     HIPCHK(h, hipMemsetAsync(h->d_counters, 0, sizeof(uint64_t) * 4 * (h->n_tasks ? h->n_tasks : 1), h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_obs, 0, sizeof(float) * N * h->n_vars, h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_run, 0, sizeof(int64_t) * 4, h->stream));
+    if (policy_io_on_reset(h) != RS_OK) return RS_EHIP;
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     (void)hipFree(tmp);
@@ -1514,5 +1520,6 @@ extern "C" int rs_load_state(rs_handle* h, const void* blob, uint64_t bytes) {
     return RS_OK;
 }
 #include "rs_fork.hip"
+#include "rs_policy_io.hip"
 #include "kb_api.hip"
 #include "kb_fork.hip"

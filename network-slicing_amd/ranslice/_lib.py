@@ -26,7 +26,23 @@ EXPORTS = (
     'rs_get_info', 'rs_set_alloc_trace', 'rs_get_alloc_trace', 'rs_get_counters', 'rs_get_rx_stats', 'rs_set_group_size', 'rs_set_schedule_hint', 'rs_get_section_profile', 'rs_get_task_profile', 'rs_run_random', 'rs_kernel_time_ms', 'rs_kernel_time_stats_ms',
     'rs_set_kernel_timing', 'rs_synchronize', 'rs_state_bytes', 'rs_save_state', 'rs_load_state', 'rs_device_count', 'rs_device_mem_info', 'rs_n_vars', 'rs_n_slices', 'rs_last_error', 'rs_destroy',
     'rs_fork', 'rs_set_lookahead', 'rs_step_clairvoyant', 'rs_set_clairvoyant_fallback',
+    'rs_get_device_view', 'rs_step_device', 'rs_stream_join', 'rs_set_action_table', 'rs_report_begin', 'rs_report_extend',
+    'rs_report_fetch', 'rs_device_copy',
 ) + KB_EXPORTS
+
+# action kinds of rs_step_device
+RS_ACT_PRBS, RS_ACT_SHARES, RS_ACT_INDEX = 0, 1, 2
+
+
+class RsDeviceView(C.Structure):
+    """rs_device_view (include/ranslice.h): device pointers owned by a handle"""
+    _fields_ = [('device', C.c_int32), ('n_envs', C.c_int32), ('n_slices', C.c_int32), ('n_vars', C.c_int32),
+                ('stream', C.c_void_p),
+                ('in_prbs', C.c_void_p), ('in_shares', C.c_void_p), ('in_index', C.c_void_p),
+                ('actions', C.c_void_p), ('resources', C.c_void_p),
+                ('obs', C.c_void_p), ('obs_norm', C.c_void_p),
+                ('reward', C.c_void_p), ('labels', C.c_void_p), ('violations', C.c_void_p), ('total_violations', C.c_void_p),
+                ('rejected', C.c_void_p)]
 
 
 class RanSliceError(RuntimeError):
@@ -113,6 +129,14 @@ def load(dev=None):
     L.rs_set_lookahead.argtypes = [vp, C.c_int]
     L.rs_set_clairvoyant_fallback.argtypes = [vp, C.c_int]
     L.rs_step_clairvoyant.argtypes = [vp, ip, fp, dp, ip, ip]
+    L.rs_get_device_view.argtypes = [vp, C.POINTER(RsDeviceView)]
+    L.rs_step_device.argtypes = [vp, C.c_int, vp, vp]
+    L.rs_stream_join.argtypes = [vp, vp]
+    L.rs_set_action_table.argtypes = [vp, ip, C.c_int32]
+    L.rs_report_begin.argtypes = [vp, C.c_int32]
+    L.rs_report_extend.argtypes = [vp, C.c_int32]
+    L.rs_report_fetch.argtypes = [vp, C.POINTER(C.c_int16), dp, C.POINTER(C.c_int16), ip]
+    L.rs_device_copy.argtypes = [vp, vp, vp, C.c_uint64, C.c_int]
     i64p = C.POINTER(C.c_int64)
     L.kb_create.argtypes = [C.POINTER(KbConfig), C.c_int, C.POINTER(vp)]
     L.kb_destroy.argtypes = [vp]

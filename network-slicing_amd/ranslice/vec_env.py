@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _lib
 from .config import RsAllocRec, make_config, n_vars
+from .device_io import DeviceArray, describe
 from .fading import synth_fading
 from .sharding import replica_seeds
 
@@ -133,6 +134,67 @@ class VecRanSlice:
 
     def synchronize(self):
         self._check(self.L.rs_synchronize(self.h))
+
+    # ---- device-resident policy interface (rs_policy_io.hip) ---------------------------------
+    def device_view(self):
+        """dict of DeviceArrays over the handle's own device buffers (rs_get_device_view), valid until close(): the inputs
+        in_prbs / in_shares / in_index, the executed `actions` and their row sums `resources`, and the outputs of the last step
+        obs, obs_norm, reward, labels, violations, total_violations; `rejected` is the one-word refusal counter.  Also
+        'stream': the handle's hipStream_t as an int."""
+        v = _lib.RsDeviceView()
+        self._check(self.L.rs_get_device_view(self.h, C.byref(v)))
+        N, S, V = self.n_envs, self.n_slices, self.n_variables
+        spec = dict(in_prbs=((N, S), np.int32), in_shares=((N, S + 1), np.float32), in_index=((N,), np.int64),
+                    actions=((N, S), np.int32), resources=((N,), np.int32), obs=((N, V), np.float32),
+                    obs_norm=((N, V), np.float32), reward=((N,), np.float64), labels=((N, S), np.int32),
+                    violations=((N, S), np.int32), total_violations=((N,), np.int32), rejected=((1,), np.int64))
+        out = {k: DeviceArray(getattr(v, k), shape, dt, owner=self) for k, (shape, dt) in spec.items()}
+        out['stream'] = int(v.stream or 0)
+        return out
+
+    def _action_kind(self, shape, dtype):
+        N, S = self.n_envs, self.n_slices
+        if dtype == np.int32 and shape in ((N, S), (N * S,)):
+            return _lib.RS_ACT_PRBS
+        if dtype == np.float32 and shape in ((N, S + 1), (N * (S + 1),)):
+            return _lib.RS_ACT_SHARES
+        if dtype == np.int64 and shape in ((N,), (N, 1)):
+            return _lib.RS_ACT_INDEX
+        raise ValueError('step_device: %s %s fits no action kind (int32 [%d, %d] PRBs, float32 [%d, %d] shares, int64 [%d] '
+                         'table rows)' % (dtype, shape, N, S, N, S + 1, N))
+
+    def step_device(self, actions, kind=None, stream=0):
+        """One step with the actions read from device memory and every output left there (rs_step_device): nothing crosses
+        PCIe and the host does not wait.  actions: a DeviceArray, anything with __cuda_array_interface__ or data_ptr() (a torch
+        tensor), or an int device pointer (then `kind` is required).  kind: RS_ACT_PRBS / RS_ACT_SHARES / RS_ACT_INDEX, inferred
+        from dtype and shape when None.  stream: the hipStream_t (int) the actions were produced on and the outputs will be
+        read on; 0 is the null stream, torch's default.  Rows that rs_step would reject are replaced by zeros and counted
+        (rejected_rows)."""
+        ptr, shape, dtype = describe(actions)
+        if shape is not None and dtype is not None:
+            fits = self._action_kind(shape, dtype)
+            if kind is None:
+                kind = fits
+            elif int(kind) != fits:
+                raise ValueError('step_device: %s %s is not the layout of action kind %d' % (dtype, shape, int(kind)))
+        elif kind is None:
+            raise ValueError('step_device: a bare pointer needs an explicit kind')
+        self._check(self.L.rs_step_device(self.h, int(kind), C.c_void_p(ptr), C.c_void_p(int(stream) or None)))
+
+    def stream_join(self, stream=0):
+        """`stream` waits for everything queued on the handle so far (rs_stream_join); the host does not"""
+        self._check(self.L.rs_stream_join(self.h, C.c_void_p(int(stream) or None)))
+
+    def set_action_table(self, table):
+        """the rows RS_ACT_INDEX picks from: int [n_actions, n_slices] (report.dqn_action_table)"""
+        table = np.ascontiguousarray(table, dtype=np.int32)
+        if table.ndim != 2 or table.shape[1] != self.n_slices or table.shape[0] == 0:
+            raise ValueError('set_action_table: expected [n_actions, %d], got %s' % (self.n_slices, table.shape))
+        self._check(self.L.rs_set_action_table(self.h, table.ctypes.data_as(_ip), table.shape[0]))
+
+    def rejected_rows(self):
+        """action rows step_device refused since reset(); waits for the handle's stream"""
+        return int(self.device_view()['rejected'].get()[0])
 
     # ---- replica fork and the clairvoyant step -------------------------------------------
     def fork_from(self, src, index):
