@@ -483,6 +483,33 @@ int kb_deploy(kb_handle* src, const int32_t* src_index, int32_t n, kb_handle** o
  * resumes learning.  The host entry points (kb_update_control, ...) are not affected. */
 int kb_set_learning(kb_handle* k, int on);
 
+/* Budgeted dictionaries.  kb_prune leaves every dictionary that holds more than `target` landmarks with exactly `target`
+ * and does not touch the others; *removed_total (may be NULL) = landmarks removed by the call.  One landmark leaves at a
+ * time: with P = Kinv of the live landmarks and c their coefficients, r = argmin_j (c_j c_j) / P[j][j] (lowest j on a tie);
+ * every survivor's coefficient takes c_i + c_r * ((-P[i][r]) / P[r][r]) -- the best approximation of c_r k(l_r, .) by the
+ * survivors, squared error c_r^2 / P[r][r] --; P[i][j] takes P[i][j] - (P[i][r] * P[j][r]) / P[r][r], the survivors' inverse
+ * Gram matrix exactly; landmark m - 1 moves into slot r (vector-page rows, row and column of Kinv) and the vacated slot and
+ * Kinv row are cleared to zeros.  The result does not depend on which other dictionaries the call prunes.  Per touched
+ * dictionary afterwards: the newest-landmark heads and chain links are rebuilt, the off-grid count recounted, the version
+ * bumped (stored select scores are not reused), the cache of the last kb_predict invalidated (kb_update then answers
+ * RS_ESTATE until a new kb_predict); the float32 mark, the control state, the tie-break stream and the flag word stay (bit
+ * 16 is sticky).  Shells are kept: growing back to the old size allocates nothing, and kb_get_pool reports the same bytes in
+ * use.  Ordered on the agent's stream, between kb_run_resident calls (never captured); the host waits for it.
+ * RS_EINVAL: target < 64 or target > capacity.  RS_ESTATE: a shared-dictionary handle, an inference-only handle, kb_reset
+ * missing, or dictionaries with a diagonal entry of Kinv that is not finite and positive -- those are left as they are (the
+ * others are pruned; kb_last_error counts them).
+ * kb_get_pruned: landmarks removed per dictionary [n_envs][S] since kb_reset / kb_load_state / kb_fork into the handle (the
+ * counters are not part of a checkpoint: kb_state_bytes and the blobs are what they were).
+ * kb_prune_time_ms: with kb_set_kernel_timing on, device time (HIP events) summed over the launches since the last call of
+ * [0] the choose, [1] the downdate, [2] the move kernel, and the launches n.
+ * kb_get_prune_work: the downdate's work since kb_reset / kb_load_state / kb_fork into the handle, counted from its work plan:
+ * [0] units of 8,192 bytes read and 8,192 written (only units that hold rows), [1] launches with work.  Like the pruned
+ * counters it is not part of a checkpoint. */
+int kb_prune(kb_handle* k, int32_t target, uint64_t* removed_total);
+int kb_get_pruned(kb_handle* k, int64_t* removed /* [n_dictionaries] since kb_reset */);
+int kb_prune_time_ms(kb_handle* k, double ms[3], int64_t n[3]);   /* choose, downdate, move: HIP events, when kernel timing is on */
+int kb_get_prune_work(kb_handle* k, uint64_t work[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,8 @@
 #pragma once
 #include "kb_kbrl.hip"
 
+struct kb_prune_state;  // kb_prune.hip
+
 struct kb_handle {
     kb_config cfg;
     int device = 0;
@@ -72,6 +74,7 @@ struct kb_handle {
     int32_t* h_fork_idx = nullptr;   // pinned staging of the same
     uint64_t* d_fork_base = nullptr; // [n_dict + 1] first pool double of every dictionary (exclusive scan of its shells' sizes)
     uint64_t* h_fork_total = nullptr;  // pinned: the scan's total
+    kb_prune_state* prune = nullptr; // kb_prune's lists and the pruned counters: NOT a saved region (kb_prune.hip)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
     std::vector<int> ev_kind;  // 0 update phase, 1 select phase; ONE launch of: 2 heavy_matvec_kernel, 3 heavy_rank1_kernel, 4 select_bin_kernel,
                                // 5 heavy_finish_kernel, 6 select_gemm_kernel, 7 update_small_kernel
@@ -80,6 +83,9 @@ struct kb_handle {
     int64_t kind_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::string err;
 };
+
+static void kb_prune_release(kb_handle* k);  // kb_prune.hip
+static void kb_prune_restart(kb_handle* k);  // the pruned counters start over (kb_reset, kb_load_state, kb_fork)
 
 template <class Tp>
 static int kalloc(kb_handle* k, Tp** p, size_t n, bool zero = true) {
@@ -449,6 +455,7 @@ extern "C" void kb_destroy(kb_handle* k) {
     if (k->d_fork_base) (void)hipFree(k->d_fork_base);
     if (k->h_fork_idx) (void)hipHostFree(k->h_fork_idx);
     if (k->h_fork_total) (void)hipHostFree(k->h_fork_total);
+    kb_prune_release(k);
     if (k->h_seen) (void)hipHostFree(k->h_seen);
     if (k->h_total) (void)hipHostFree(k->h_total);
     if (k->stream) (void)hipStreamDestroy(k->stream);
@@ -487,6 +494,7 @@ extern "C" int kb_reset(kb_handle* k, const int32_t* initial_action, const int32
     HIPCHK(k, hipMemsetAsync(k->K.hv_work, 0, sizeof(unsigned long long) * 8, k->stream));
     // (the hits an inference-mode history column repeats: none yet, kb_set_learning)
     HIPCHK(k, hipMemsetAsync(k->d_hits, 0, sizeof(int32_t) * T, k->stream));
+    kb_prune_restart(k);
     HIPCHK(k, hipGetLastError());
     HIPCHK(k, hipStreamSynchronize(k->stream));
     if (k->h_seen) k->h_seen[0] = k->h_seen[1] = 0;
@@ -1672,6 +1680,7 @@ extern "C" int kb_load_state(kb_handle* k, const void* blob, uint64_t bytes) {
         }
         if (any) HIPCHK(k, hipMemcpy(k->K.err, e.data(), sizeof(int32_t) * e.size(), hipMemcpyHostToDevice));
     }
+    kb_prune_restart(k);
     k->big_par = hd.big_par;
     k->is_reset = hd.is_reset != 0;
     if (k->h_seen) {

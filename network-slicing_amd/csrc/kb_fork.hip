@@ -255,6 +255,7 @@ static int kb_fork_core(kb_handle* dst, kb_handle* src, const int32_t* src_index
     HIPCHK(dst, hipMemsetAsync(dst->K.big, 0, sizeof(int32_t) * 2 * (1 + KB_BIG_MAX), dst->stream));
     HIPCHK(dst, hipMemsetAsync(dst->K.isbig, 0, sizeof(int32_t) * 2 * T, dst->stream));
     HIPCHK(dst, hipMemsetAsync(dst->K.pool, 0, sizeof(double) * 64, dst->stream));  // (below every shell; never read)
+    kb_prune_restart(dst);
     kb::ForkArgs a;
     memset(&a, 0, sizeof a);
     a.Dd = dst->D;

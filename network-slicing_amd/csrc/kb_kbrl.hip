@@ -1151,7 +1151,9 @@ __device__ __forceinline__ void rank1_units(const KbState& K, const uint64_t* sh
 __device__ __forceinline__ bool take_shell(const KbDev& D, const KbState& K, int dict, int b, Lds& sm) {
     if (threadIdx.x == 0) {
         int ok = 0;
-        if (b < D.max_shells) {
+        if (b < D.max_shells && K.shell[(size_t)dict * D.max_shells + b] != 0) {
+            ok = 1;  // (a shell kb_prune left behind: growing back allocates nothing)
+        } else if (b < D.max_shells) {
             const unsigned long long need = kb_shell_doubles(b, D.tri);
             unsigned long long at = *(volatile unsigned long long*)K.pool_top;
             while (at + need <= D.pool_doubles) {

@@ -1523,3 +1523,4 @@ extern "C" int rs_load_state(rs_handle* h, const void* blob, uint64_t bytes) {
 #include "rs_policy_io.hip"
 #include "kb_api.hip"
 #include "kb_fork.hip"
+#include "kb_prune.hip"

@@ -56,7 +56,18 @@ class Evaluator():
 
 
 class BatchedEvaluator(Evaluator):
-    """All runs of one (scenario, accuracy range) at once: run i = replica i."""
+    """All runs of one (scenario, accuracy range) at once: run i = replica i.
+
+    prune_to = T, prune_every = P: budgeted dictionaries -- after every P-th step (between two resident stretches) every
+    dictionary above T landmarks is pruned back to T (VecKBRL.prune); the result files then carry one extra
+    key, `pruned`: the landmarks removed from the run's dictionaries in all.  The defaults leave everything as it was."""
+
+    def __init__(self, scenario, a_range, steps=STEPS, out_dir='./results', prune_to=None, prune_every=None):
+        super().__init__(scenario, a_range, steps=steps, out_dir=out_dir)
+        if (prune_to is None) != (not prune_every):
+            raise ValueError('prune_to and prune_every go together')
+        self.prune_to, self.prune_every = prune_to, prune_every
+        self._pruned_base = 0   # what a checkpoint this evaluation resumed from had counted (the device counters restart on load)
 
     def _setup(self, runs, device=0, capacity=16384, pool_bytes=32 << 30):
         """environment + agent of this cell with run i as replica i, reset and given the first action; nothing waits"""
@@ -99,6 +110,18 @@ class BatchedEvaluator(Evaluator):
         self._ctx = dict(runs=runs, env=env, agent=agent, capacity=capacity)
 
     def _advance(self, i, k=1, graph=True):
+        """_advance_stretch, cut at the multiples of prune_every, with a prune behind each (the host waits for it)"""
+        if not self.prune_every:
+            return self._advance_stretch(i, k, graph=graph)
+        end = i + k
+        while i < end:
+            n = min(end - i, self.prune_every - i % self.prune_every)
+            self._advance_stretch(i, n, graph=graph)
+            i += n
+            if i % self.prune_every == 0 and i < self.steps:
+                self._ctx['agent'].prune(self.prune_to)
+
+    def _advance_stretch(self, i, k=1, graph=True):
         """steps i .. i + k - 1 of KBRL_Control.run's loop, enqueued on this cell's own streams (no host wait).  Every step
         but the run's last is an agent step followed by a simulator step: those go out k at a time (kb_run_resident, two
         captured steps replayed as a hipGraph)."""
@@ -133,6 +156,7 @@ class BatchedEvaluator(Evaluator):
         assert hist['recorded'] == self.steps
         sizes = agent.dictionary_sizes()
         pool = agent.pool()
+        pruned = (agent.pruned() + self._pruned_base).sum(axis=1) if self.prune_every else None
         self.last_run = dict(max_dictionary=int(sizes.max()), mean_dictionary=float(sizes.mean()), pool=pool)
         if pool['saturated'] or pool['pool_full']:
             import warnings
@@ -149,6 +173,8 @@ class BatchedEvaluator(Evaluator):
         for k, i in enumerate(runs):
             results = {'reward': hist['reward'][k], 'resources': hist['resources'][k], 'hits': hist['hits'][k],
                        'adjusted': hist['adjusted'][k], 'SLA': hist['SLA'][k], 'violation': hist['violation'][k]}
+            if self.prune_every:
+                results['pruned'] = np.int64(pruned[k])
             file_path = '{}results_{}.npz'.format(self.path, i)
             savez(file_path, **results)
             files.append(file_path)
@@ -171,8 +197,9 @@ class BatchedEvaluator(Evaluator):
         # written beside the old checkpoint and moved onto it: a crash during the write -- the case this exists for -- leaves
         # the previous checkpoint intact instead of a torn .npz
         tmp = path + '.tmp.npz'
+        extra = dict(pruned=c['agent'].pruned() + self._pruned_base) if self.prune_every else {}
         np.savez(tmp, next_step=np.int64(next_step), steps=np.int64(self.steps), runs=np.asarray(c['runs'], dtype=np.int64),
-                 env=env_blob, agent=agent_blob)
+                 env=env_blob, agent=agent_blob, **extra)
         os.replace(tmp, path)
 
     def load_checkpoint(self, path):
@@ -183,6 +210,8 @@ class BatchedEvaluator(Evaluator):
             raise ValueError('checkpoint %s belongs to another evaluation (steps / runs differ)' % path)
         c['env'].load_state(z['env'])
         c['agent'].load_state(z['agent'])
+        if self.prune_every and 'pruned' in z.files:
+            self._pruned_base = z['pruned']
         return int(z['next_step'])
 
     def evaluate_all(self, runs, device=0, capacity=16384, pool_bytes=32 << 30, verbose=True, checkpoint=None,
@@ -218,17 +247,18 @@ class BatchedEvaluator(Evaluator):
 
 
 def evaluate_grid(cells, runs, steps=STEPS, out_dir='./results', device=0, capacity=16384, pool_bytes=16 << 30, verbose=False,
-                  graph=False):
+                  graph=False, prune_to=None, prune_every=None):
     """The reference's whole experiment (experiments_kbrl.py:57-70: every scenario x accuracy range x run) as ONE job on
     one GPU: a BatchedEvaluator per cell, each with its environment and agents on streams of their own, all advanced in
     the same host loop -- a cell of 30 runs leaves most of the chip idle (a handful of waves per kernel), so the cells'
     kernels run beside each other.  Nothing in the loop waits for the device.  (graph=False: graph launches of different
     handles do not overlap on this runtime -- 22.4 s per 6,000 steps of the six cells against 16.1 s with plain launches,
     profiles/r04_w_grid_graph.txt -- while a single cell gains 5 % from the graph.)  Returns {(scenario, a_lo): [files]}, file
-    for file what evaluate_all writes cell by cell (tests/test_gpu_kbrl.py::test_grid_of_cells_equals_cell_by_cell)."""
+    for file what evaluate_all writes cell by cell (tests/test_gpu_kbrl.py::test_grid_of_cells_equals_cell_by_cell).
+    prune_to / prune_every: budgeted dictionaries in every cell (BatchedEvaluator)."""
     evs = []
     for scenario, a_range in cells:
-        ev = BatchedEvaluator(scenario, a_range, steps=steps, out_dir=out_dir)
+        ev = BatchedEvaluator(scenario, a_range, steps=steps, out_dir=out_dir, prune_to=prune_to, prune_every=prune_every)
         ev._setup(runs, device=device, capacity=capacity, pool_bytes=pool_bytes)
         evs.append(ev)
     for i in range(0, steps, CHUNK):

@@ -300,6 +300,34 @@ class VecKBRL:
         """on=False: step_resident / run_resident select only (KBRL_Control.run past learning_time); True resumes learning"""
         self._check(self.L.kb_set_learning(self.h, int(bool(on))))
 
+    # ---- budgeted dictionaries ------------------------------------------------------------------
+    def prune(self, target):
+        """every dictionary above `target` landmarks is brought down to exactly `target` (kb_prune): one landmark at a time, the
+        one whose loss changes the classifier least (smallest coeff^2 / Kinv[j][j]) is folded into the survivors and Kinv
+        downdated exactly.  Shells are kept (pool()['used_bytes'] does not move).  Call it between run_resident stretches.
+        -> landmarks removed by the call"""
+        n = C.c_uint64()
+        self._check(self.L.kb_prune(self.h, int(target), C.byref(n)))
+        return int(n.value)
+
+    def pruned(self):
+        """landmarks removed per dictionary [n_envs, S] since reset / load_state / fork_from (not part of a checkpoint)"""
+        n = self.S if self.cfg.shared_dictionary else self.n_envs * self.S
+        out = np.zeros(n, dtype=np.int64)
+        self._check(self.L.kb_get_pruned(self.h, out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out if self.cfg.shared_dictionary else out.reshape(self.n_envs, self.S)
+
+    def prune_times_ms(self):
+        """with set_kernel_timing on: device time summed over the launches of the three prune kernels since the last call, their
+        launch counts, and the downdate's bytes (read + written) since reset, counted from its work plan (kb_get_prune_work)"""
+        ms = (C.c_double * 3)()
+        n = (C.c_int64 * 3)()
+        self._check(self.L.kb_prune_time_ms(self.h, ms, n))
+        w = (C.c_uint64 * 2)()
+        self._check(self.L.kb_get_prune_work(self.h, w))
+        return dict(choose_ms=ms[0], downdate_ms=ms[1], move_ms=ms[2], n_choose=n[0], n_downdate=n[1], n_move=n[2],
+                    downdate_bytes=int(w[0]) * 16384, downdate_launches=int(w[1]))
+
 
 PROP_W = 18  # KB_PROP_WIDTH
 
