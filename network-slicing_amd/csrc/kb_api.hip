@@ -65,7 +65,6 @@ struct kb_handle {
     int n_dict = 0;
     int T = 0, nv = 0;
     bool is_reset = false;
-    bool timing = false;
     bool learning = true;          // kb_set_learning: false = the resident loop selects only (KBRL_Control.run past learning_time)
     bool frozen = false;           // an inference-only handle (kb_deploy): no Kinv behind its dictionaries, learning permanently off
     // kb_fork / kb_deploy into this handle (kb_fork.hip)
@@ -75,10 +74,8 @@ struct kb_handle {
     uint64_t* d_fork_base = nullptr; // [n_dict + 1] first pool double of every dictionary (exclusive scan of its shells' sizes)
     uint64_t* h_fork_total = nullptr;  // pinned: the scan's total
     kb_prune_state* prune = nullptr; // kb_prune's lists and the pruned counters: NOT a saved region (kb_prune.hip)
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-    std::vector<int> ev_kind;  // 0 update phase, 1 select phase; ONE launch of: 2 heavy_matvec_kernel, 3 heavy_rank1_kernel, 4 select_bin_kernel,
-                               // 5 heavy_finish_kernel, 6 select_gemm_kernel, 7 update_small_kernel
-    size_t ev_used = 0;
+    EventSpans spans;  // kernel timing (kb_set_kernel_timing), by kind: 0 update phase, 1 select phase; ONE launch of: 2 heavy_matvec_kernel,
+                       // 3 heavy_rank1_kernel, 4 select_bin_kernel, 5 heavy_finish_kernel, 6 select_gemm_kernel, 7 update_small_kernel
     double kind_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // mean per kind over the span the last kb_phase_times_ms call summed up
     int64_t kind_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::string err;
@@ -436,10 +433,7 @@ extern "C" void kb_destroy(kb_handle* k) {
     if (guards_on()) check_guards(k->guarded, "kb");
     for (auto& g : k->guarded) (void)hipFree(g.base);
     for (void* p : k->allocs) (void)hipFree(p);
-    for (auto& e : k->ev) {
-        (void)hipEventDestroy(e.first);
-        (void)hipEventDestroy(e.second);
-    }
+    k->spans.release();
     if (k->ev_order) (void)hipEventDestroy(k->ev_order);
     if (k->ev_join) (void)hipEventDestroy(k->ev_join);
     if (k->side) (void)hipStreamSynchronize(k->side);
@@ -547,23 +541,6 @@ static void launch_shared_gemm(kb_handle* k, const float* d_state) {
     hipLaunchKernelGGL(kb::shared_fgemm_kernel, dim3(S, rts, chunks * (KB_GEMM_KS / 4)), dim3(256), 0, k->stream, k->D, k->K, d_state);
 }
 
-static int kb_time_begin(kb_handle* k, hipEvent_t* e1, int kind = 0) {
-    *e1 = nullptr;
-    if (!k->timing) return RS_OK;
-    if (k->ev_used == k->ev.size()) {
-        hipEvent_t a0, a1;
-        HIPCHK(k, hipEventCreate(&a0));
-        HIPCHK(k, hipEventCreate(&a1));
-        k->ev.emplace_back(a0, a1);
-        k->ev_kind.push_back(0);
-    }
-    k->ev_kind[k->ev_used] = kind;
-    HIPCHK(k, hipEventRecord(k->ev[k->ev_used].first, k->stream));
-    *e1 = k->ev[k->ev_used].second;
-    k->ev_used++;
-    return RS_OK;
-}
-
 static int launch_update_control(kb_handle* k, const float* d_state, const int32_t* d_action, const int32_t* d_labels) {
     kb::CtlArgs a;
     a.D = k->D;
@@ -577,8 +554,7 @@ static int launch_update_control(kb_handle* k, const float* d_state, const int32
     a.big_par = -1;
     const unsigned grid1 = (unsigned)k->T;
     hipEvent_t e1;
-    int rc = kb_time_begin(k, &e1);
-    if (rc != RS_OK) return rc;
+    HIPCHK(k, k->spans.begin(k->stream, 0, &e1));
     if (k->D.heavy_m > 0)
         hipLaunchKernelGGL(kb::update_control_kernel<true>, dim3(grid1), dim3(64), 0, k->stream, a);
     else
@@ -588,9 +564,9 @@ static int launch_update_control(kb_handle* k, const float* d_state, const int32
         // each, taken by persistent workgroups
         const unsigned blocks = (unsigned)(k->T < k->heavy_blocks ? k->T : k->heavy_blocks);
         // (with per-kernel event timing on, everything stays on the one stream: the account is per kernel, not per overlap)
-        const bool forked = k->side != nullptr && !k->timing;
+        const bool forked = k->side != nullptr && !k->spans.on;
         hipEvent_t es;
-        if ((rc = kb_time_begin(k, &es, 7)) != RS_OK) return rc;
+        HIPCHK(k, k->spans.begin(k->stream, 7, &es));
         if (forked) {
             HIPCHK(k, hipEventRecord(k->ev_sfork, k->stream));
             HIPCHK(k, hipStreamWaitEvent(k->side, k->ev_sfork, 0));
@@ -606,15 +582,15 @@ static int launch_update_control(kb_handle* k, const float* d_state, const int32
         if (rounds && k->heavy_rounds > 0) hipLaunchKernelGGL(kb::heavy_plan_kernel, dim3(1), dim3(1024), 0, k->stream, k->D, k->K);
         for (int r = 0; rounds && r < k->heavy_rounds; ++r) {  // one repair of every pending large learner per round, chip-wide
             hipEvent_t em, er;  // (with kb_set_kernel_timing: each launch of the two streaming kernels on its own, for their roofline)
-            if ((rc = kb_time_begin(k, &em, 2)) != RS_OK) return rc;
+            HIPCHK(k, k->spans.begin(k->stream, 2, &em));
             hipLaunchKernelGGL(kb::heavy_matvec_kernel, dim3((unsigned)k->mv_grid), dim3(256), 0, k->stream, k->D, k->K);
             if (em) HIPCHK(k, hipEventRecord(em, k->stream));
             hipEvent_t ef;
-            if ((rc = kb_time_begin(k, &ef, 5)) != RS_OK) return rc;
+            HIPCHK(k, k->spans.begin(k->stream, 5, &ef));
             hipLaunchKernelGGL(kb::heavy_finish_kernel, dim3(1024), dim3(256), 0, k->stream, a);
             if (ef) HIPCHK(k, hipEventRecord(ef, k->stream));
             hipLaunchKernelGGL(kb::heavy_plan_kernel, dim3(1), dim3(1024), 0, k->stream, k->D, k->K);
-            if ((rc = kb_time_begin(k, &er, 3)) != RS_OK) return rc;
+            HIPCHK(k, k->spans.begin(k->stream, 3, &er));
             hipLaunchKernelGGL(kb::heavy_rank1_kernel, dim3((unsigned)k->r1_grid), dim3(256), 0, k->stream, k->D, k->K);
             if (er) HIPCHK(k, hipEventRecord(er, k->stream));
         }
@@ -635,8 +611,7 @@ static int launch_select(kb_handle* k, const float* d_state, int32_t* d_action_o
     a.gemm = k->D.shared ? 1 : 0;
     k->gemm_fresh = false;  // (kb_shared_step_resident sets it again once the state has become d_prev_state)
     hipEvent_t e1;
-    int rc = kb_time_begin(k, &e1, 1);
-    if (rc != RS_OK) return rc;
+    HIPCHK(k, k->spans.begin(k->stream, 1, &e1));
     if (a.gemm) launch_shared_gemm(k, d_state);
     if (k->D.shared) {
         hipLaunchKernelGGL(kb::select_kernel, dim3((unsigned)k->T), dim3(64), 0, k->stream, a);
@@ -644,7 +619,7 @@ static int launch_select(kb_handle* k, const float* d_state, int32_t* d_action_o
               // as one product on the matrix cores
         const unsigned slots = (unsigned)k->T + (a.big_par >= 0 ? KB_BIG_MAX : 0);
         hipEvent_t eb, eg;
-        if ((rc = kb_time_begin(k, &eb, 4)) != RS_OK) return rc;
+        HIPCHK(k, k->spans.begin(k->stream, 4, &eb));
         if (a.big_par >= 0) {  // the listed large learners several waves each, the others a wave each
             if (dev_env("KBRL_BIN_TWO_LAUNCHES")) {  // test build: the two kernels one after the other (rounds 4-5; same bits)
                 hipLaunchKernelGGL(kb::select_bin_big_kernel, dim3(KB_BINBIG_GRID), dim3(64 * KB_BINBIG_WAVES), 0, k->stream, a);
@@ -658,7 +633,7 @@ static int launch_select(kb_handle* k, const float* d_state, int32_t* d_action_o
             hipLaunchKernelGGL(kb::select_bin_kernel, dim3(slots), dim3(64), 0, k->stream, a, 0);
         }
         if (eb) HIPCHK(k, hipEventRecord(eb, k->stream));
-        if ((rc = kb_time_begin(k, &eg, 6)) != RS_OK) return rc;
+        HIPCHK(k, k->spans.begin(k->stream, 6, &eg));
         hipLaunchKernelGGL(kb::select_gemm_kernel, dim3((slots + KB_SEL_WAVES - 1) / KB_SEL_WAVES), dim3(256), 0, k->stream, a);
         if (eg) HIPCHK(k, hipEventRecord(eg, k->stream));
     }
@@ -735,14 +710,11 @@ extern "C" int kb_step_resident(kb_handle* k, rs_handle* env) {
         env->hint_auto = true;
     }
     // order after the simulator's step on its own stream
-    if (!k->ev_order) HIPCHK(k, hipEventCreateWithFlags(&k->ev_order, hipEventDisableTiming));
-    hipEvent_t done = k->ev_order;
-    HIPCHK(k, hipEventRecord(done, env->stream));
-    HIPCHK(k, hipStreamWaitEvent(k->stream, done, 0));
+    int rc = stream_after(k, &k->ev_order, env->stream, k->stream);
+    if (rc != RS_OK) return rc;
     // inference mode (kb_set_learning(k, 0), or an inference-only handle): KBRL_Control.run past learning_time, kbrl_control.py:131-133
     // -- the same launches without the update phase; d_hits keeps the last learning step's hits for the history column
-    int rc = k->learning ? launch_update_control(k, k->d_prev_state, env->d_actions, env->d_labels) : RS_OK;
-    if (rc != RS_OK) return rc;
+    if (k->learning && (rc = launch_update_control(k, k->d_prev_state, env->d_actions, env->d_labels)) != RS_OK) return rc;
     rc = launch_select(k, env->d_obs, env->d_actions);
     if (rc != RS_OK) return rc;
     if (k->h_steps > 0) {  // KBRL_Control.run's history columns of this step (kbrl_control.py:135-141)
@@ -766,8 +738,7 @@ extern "C" int kb_step_resident(kb_handle* k, rs_handle* env) {
     }
     HIPCHK(k, hipMemcpyAsync(k->d_prev_state, env->d_obs, sizeof(float) * (size_t)k->cfg.n_envs * k->nv,
                              hipMemcpyDeviceToDevice, k->stream));
-    HIPCHK(k, hipEventRecord(done, k->stream));
-    HIPCHK(k, hipStreamWaitEvent(env->stream, done, 0));
+    if ((rc = stream_after(k, &k->ev_order, k->stream, env->stream)) != RS_OK) return rc;
     HIPCHK(k, hipGetLastError());
     return RS_OK;
 }
@@ -796,7 +767,7 @@ extern "C" int kb_run_resident(kb_handle* k, rs_handle* env, int n_steps, int us
     static const bool no_graph = getenv("ROCP_TOOL_LIBRARIES") != nullptr &&
                                  !(dev_env("KBRL_GRAPH_UNDER_PROFILER") && atoi(dev_env("KBRL_GRAPH_UNDER_PROFILER")) != 0);
     if (no_graph) use_graph = 0;
-    if (use_graph && !k->timing && !env->timing && !k->D.shared && n_steps >= 3) {
+    if (use_graph && !k->spans.on && !env->spans.on && !k->D.shared && n_steps >= 3) {
         if (!k->gexec || k->g_env != env || k->g_sig != env->launch_sig) {
             // (one plain step first: whatever the loop creates lazily -- events, the schedule hint -- exists before the capture)
             kb_drop_graph(k);
@@ -838,9 +809,7 @@ extern "C" int kb_run_resident(kb_handle* k, rs_handle* env, int n_steps, int us
             // The replay runs on the SIMULATOR's stream.  When the cached graph is taken as it is, nothing above has touched the
             // agent's stream -- but work may be queued there that the loop must follow: kb_fork / kb_deploy make a source's stream
             // wait for their gather, which reads the dictionaries these steps rewrite.  So the replay joins the agent's stream first.
-            if (!k->ev_order) HIPCHK(k, hipEventCreateWithFlags(&k->ev_order, hipEventDisableTiming));
-            HIPCHK(k, hipEventRecord(k->ev_order, k->stream));
-            HIPCHK(k, hipStreamWaitEvent(env->stream, k->ev_order, 0));
+            if ((rc = stream_after(k, &k->ev_order, k->stream, env->stream)) != RS_OK) return rc;
         }
         while (k->gexec && n_steps - done >= 2) {
             HIPCHK(k, hipGraphLaunch(k->gexec, env->stream));
@@ -853,9 +822,7 @@ extern "C" int kb_run_resident(kb_handle* k, rs_handle* env, int n_steps, int us
             // The graph carries the agent's kernels but runs on the SIMULATOR's stream: the agent's stream joins it here, so
             // that kb_synchronize / kb_get_stats / kb_save_state (which wait for the agent's stream only) see the loop's end
             // even when the call ends on a graph launch.
-            if (!k->ev_join) HIPCHK(k, hipEventCreateWithFlags(&k->ev_join, hipEventDisableTiming));
-            HIPCHK(k, hipEventRecord(k->ev_join, env->stream));
-            HIPCHK(k, hipStreamWaitEvent(k->stream, k->ev_join, 0));
+            if ((rc = stream_after(k, &k->ev_join, env->stream, k->stream)) != RS_OK) return rc;
         }
     }
     for (; done < n_steps; ++done)
@@ -1070,8 +1037,8 @@ extern "C" int kb_get_repair_work(kb_handle* k, uint64_t work[8]) {
 extern "C" int kb_set_kernel_timing(kb_handle* k, int enable) {
     if (!k) return RS_EINVAL;
     kb_drop_graph(k);
-    k->timing = enable != 0;
-    k->ev_used = 0;
+    k->spans.on = enable != 0;
+    k->spans.reset();
     if (enable && k->D.shared && k->d_gstats && dev_env("KBRL_APPLY_TIMES")) {  // (developer aid: count from here on)
         HIPCHK(k, hipSetDevice(k->device));
         HIPCHK(k, hipMemsetAsync(k->d_gstats + 8, 0, sizeof(uint64_t) * 24, k->stream));
@@ -1087,12 +1054,10 @@ extern "C" int kb_phase_times_ms(kb_handle* k, double ms[2], int64_t n[2]) {
     HIPCHK(k, hipStreamSynchronize(k->stream));
     double tot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (size_t i = 0; i < k->ev_used; ++i) {
-        float t = 0.f;
-        HIPCHK(k, hipEventElapsedTime(&t, k->ev[i].first, k->ev[i].second));
-        tot[k->ev_kind[i] & 7] += t;
-        cnt[k->ev_kind[i] & 7] += 1;
-    }
+    HIPCHK(k, k->spans.drain([&](int kind, double t) {
+        tot[kind & 7] += t;
+        cnt[kind & 7] += 1;
+    }));
     for (int q = 0; q < 8; ++q) {
         k->kind_n[q] = cnt[q];
         k->kind_ms[q] = cnt[q] ? tot[q] / (double)cnt[q] : 0.0;
@@ -1101,7 +1066,6 @@ extern "C" int kb_phase_times_ms(kb_handle* k, double ms[2], int64_t n[2]) {
         n[q] = k->kind_n[q];
         ms[q] = k->kind_ms[q];
     }
-    k->ev_used = 0;
     return RS_OK;
 }
 
@@ -1187,8 +1151,7 @@ extern "C" int kb_shared_scan(kb_handle* k, const float* state, const int32_t* a
     a.cstar = k->d_cstar;
     a.round = round;
     hipEvent_t e1;
-    int rc = kb_time_begin(k, &e1);
-    if (rc != RS_OK) return rc;
+    HIPCHK(k, k->spans.begin(k->stream, 0, &e1));
     k->gemm_fresh = false;
     launch_shared_gemm(k, a.state);
     hipLaunchKernelGGL(kb::shared_scan_kernel, dim3((unsigned)k->T), dim3(64), 0, k->stream, a);
@@ -1306,7 +1269,7 @@ static int shared_step_core(kb_handle* k, const float* d_state, const int32_t* d
         a.cstar = k->d_cstar;
         a.round = rnd;
         hipEvent_t e1 = nullptr;
-        if (kb_time_begin(k, &e1) != RS_OK) local(hipErrorUnknown, "event for the kernel timing");
+        local(k->spans.begin(k->stream, 0, &e1), "event for the kernel timing");
         // (resident loop, round 0: select_action of the previous step scored this very state against these very dictionaries)
         if (!(rnd == 0 && k->gemm_fresh && d_state == k->d_prev_state)) launch_shared_gemm(k, a.state);
         k->gemm_fresh = false;
@@ -1419,18 +1382,15 @@ extern "C" int kb_shared_step_resident(kb_handle* k, rs_handle* env, int32_t bud
         rs_set_schedule_hint(env, 1);
         env->hint_auto = true;
     }
-    if (!k->ev_order) HIPCHK(k, hipEventCreateWithFlags(&k->ev_order, hipEventDisableTiming));
-    hipEvent_t done = k->ev_order;
-    HIPCHK(k, hipEventRecord(done, env->stream));
-    HIPCHK(k, hipStreamWaitEvent(k->stream, done, 0));
-    int rc = shared_step_core(k, k->d_prev_state, env->d_actions, env->d_labels, budget, max_rounds, nullptr, rounds_out);
+    int rc = stream_after(k, &k->ev_order, env->stream, k->stream);
+    if (rc != RS_OK) return rc;
+    rc = shared_step_core(k, k->d_prev_state, env->d_actions, env->d_labels, budget, max_rounds, nullptr, rounds_out);
     if (rc != RS_OK) return rc;
     rc = launch_select(k, env->d_obs, env->d_actions);
     if (rc != RS_OK) return rc;
     HIPCHK(k, hipMemcpyAsync(k->d_prev_state, env->d_obs, sizeof(float) * (size_t)k->cfg.n_envs * k->nv,
                              hipMemcpyDeviceToDevice, k->stream));
-    HIPCHK(k, hipEventRecord(done, k->stream));
-    HIPCHK(k, hipStreamWaitEvent(env->stream, done, 0));
+    if ((rc = stream_after(k, &k->ev_order, k->stream, env->stream)) != RS_OK) return rc;
     HIPCHK(k, hipGetLastError());
     k->gemm_fresh = true;  // workF / workE now describe d_prev_state; nothing learns before the next step's first scan
     return RS_OK;
@@ -1535,14 +1495,12 @@ static const uint64_t kKbStateMagic = 0x4b42534c49434536ull;      // "KBSLICE6":
 static const uint64_t kKbStateMagicOld = 0x4b42534c49434534ull;   // "KBSLICE4" (rounds 4-5: its hash covered the pool's size): refused by name
 static const uint64_t kKbStateMagic5 = 0x4b42534c49434535ull;     // "KBSLICE5" (a shorter header): refused by name as well
 static uint64_t kb_cfg_hash(const kb_handle* k) {
-    uint64_t x = 1469598103934665603ull;
     kb_config c = k->cfg;
     c.pool_bytes = 0;  // (see below: the pool's size is not part of the configuration)
-    const unsigned char* p = (const unsigned char*)&c;
-    for (size_t i = 0; i < sizeof c; ++i) x = (x ^ p[i]) * 1099511628211ull;
+    uint64_t x = fnv1a(&c, sizeof c);
     // (the pool's own size is not part of the configuration: a blob fits any handle whose pool holds what the blob uses --
     // with kb_config.pool_bytes == 0 the pool is sized from the free memory of the moment and differs from process to process)
-    for (auto& r : k->regions) x = (x ^ (r.first == (void*)k->K.pool ? 0ull : (uint64_t)r.second)) * 1099511628211ull;
+    for (auto& r : k->regions) x = fnv1a_step(x, r.first == (void*)k->K.pool ? 0ull : (uint64_t)r.second);
     return x;
 }
 static size_t kb_hist_bytes(const kb_handle* k, size_t part[7]) {

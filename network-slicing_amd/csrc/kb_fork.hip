@@ -186,10 +186,7 @@ static uint64_t kb_fork_cfg_hash(const kb_handle* k) {
     kb_config c = k->cfg;
     c.n_envs = 0;
     c.pool_bytes = 0;
-    uint64_t x = 1469598103934665603ull;
-    const unsigned char* p = (const unsigned char*)&c;
-    for (size_t i = 0; i < sizeof c; ++i) x = (x ^ p[i]) * 1099511628211ull;
-    return x;
+    return fnv1a(&c, sizeof c);
 }
 
 // Every device array behind a handle is a region of its saved state (k->regions, filled by kalloc).  The fork names each one:
@@ -238,15 +235,12 @@ static int kb_fork_core(kb_handle* dst, kb_handle* src, const int32_t* src_index
     const size_t T = (size_t)dst->T;
     HIPCHK(dst, hipSetDevice(dst->device));
     kb_drop_graph(dst);
-    if (!dst->ev_fork_in) HIPCHK(dst, hipEventCreateWithFlags(&dst->ev_fork_in, hipEventDisableTiming));
-    if (!dst->ev_fork_out) HIPCHK(dst, hipEventCreateWithFlags(&dst->ev_fork_out, hipEventDisableTiming));
     if (!dst->d_fork_idx) HIPCHK(dst, hipMalloc((void**)&dst->d_fork_idx, sizeof(int32_t) * n_dst));
     if (!dst->d_fork_base) HIPCHK(dst, hipMalloc((void**)&dst->d_fork_base, sizeof(uint64_t) * ((size_t)ND + 2)));
     if (!dst->h_fork_idx) HIPCHK(dst, hipHostMalloc((void**)&dst->h_fork_idx, sizeof(int32_t) * n_dst, hipHostMallocDefault));
     if (!dst->h_fork_total) HIPCHK(dst, hipHostMalloc((void**)&dst->h_fork_total, sizeof(uint64_t), hipHostMallocDefault));
     memcpy(dst->h_fork_idx, src_index, sizeof(int32_t) * n_dst);  // (a previous fork ended with its host wait: the buffer is free)
-    HIPCHK(dst, hipEventRecord(dst->ev_fork_in, src->stream));
-    HIPCHK(dst, hipStreamWaitEvent(dst->stream, dst->ev_fork_in, 0));
+    if ((rc = stream_after(dst, &dst->ev_fork_in, src->stream, dst->stream)) != RS_OK) return rc;
     HIPCHK(dst, hipMemcpyAsync(dst->d_fork_idx, dst->h_fork_idx, sizeof(int32_t) * n_dst, hipMemcpyHostToDevice, dst->stream));
     // what kb_reset restarts (the tables kernel writes stats, fver and the retained hits)
     HIPCHK(dst, hipMemsetAsync(dst->d_gstats, 0, sizeof(uint64_t) * 32, dst->stream));
@@ -285,8 +279,7 @@ static int kb_fork_core(kb_handle* dst, kb_handle* src, const int32_t* src_index
         hipLaunchKernelGGL(kb::fork_shells_kernel, dim3((unsigned)(grid < 16384 ? grid : 16384)), dim3(256), 0, dst->stream, a);
     }
     HIPCHK(dst, hipGetLastError());
-    HIPCHK(dst, hipEventRecord(dst->ev_fork_out, dst->stream));
-    HIPCHK(dst, hipStreamWaitEvent(src->stream, dst->ev_fork_out, 0));
+    if ((rc = stream_after(dst, &dst->ev_fork_out, dst->stream, src->stream)) != RS_OK) return rc;
     if (dst->h_seen) dst->h_seen[0] = dst->h_seen[1] = 0;
     dst->gemm_fresh = false;
     dst->big_par = 0;

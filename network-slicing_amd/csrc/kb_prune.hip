@@ -387,9 +387,7 @@ struct kb_prune_state {
     unsigned long long* h_info = nullptr;  // pinned
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     int grid = 2048;                       // one co-resident round of workgroups of prune_downdate_kernel
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;  // kernel timing: a pair per launch of the three phases
-    std::vector<int> ev_kind;              // 0 choose, 1 downdate, 2 move
-    size_t ev_used = 0;
+    EventSpans spans;                      // kernel timing: a pair per launch of the three phases, kind 0 choose, 1 downdate, 2 move
 };
 
 static void kb_prune_release(kb_handle* k) {
@@ -401,10 +399,7 @@ static void kb_prune_release(kb_handle* k) {
     if (p->h_info) (void)hipHostFree(p->h_info);
     if (p->ev_in) (void)hipEventDestroy(p->ev_in);
     if (p->ev_out) (void)hipEventDestroy(p->ev_out);
-    for (auto& e : p->ev) {
-        (void)hipEventDestroy(e.first);
-        (void)hipEventDestroy(e.second);
-    }
+    p->spans.release();
     delete p;
     k->prune = nullptr;
 }
@@ -439,25 +434,6 @@ static int kb_prune_prepare(kb_handle* k) {
     return RS_OK;
 }
 
-// an event pair around one launch of a phase, when kernel timing is on (kb_set_kernel_timing)
-static int kb_prune_time_begin(kb_handle* k, int kind, hipEvent_t* e1) {
-    *e1 = nullptr;
-    if (!k->timing) return RS_OK;
-    kb_prune_state* p = k->prune;
-    if (p->ev_used == p->ev.size()) {
-        hipEvent_t a0, a1;
-        HIPCHK(k, hipEventCreate(&a0));
-        HIPCHK(k, hipEventCreate(&a1));
-        p->ev.emplace_back(a0, a1);
-        p->ev_kind.push_back(0);
-    }
-    p->ev_kind[p->ev_used] = kind;
-    HIPCHK(k, hipEventRecord(p->ev[p->ev_used].first, k->stream));
-    *e1 = p->ev[p->ev_used].second;
-    p->ev_used++;
-    return RS_OK;
-}
-
 extern "C" int kb_prune(kb_handle* k, int32_t target, uint64_t* removed_total) {
     if (!k) return RS_EINVAL;
     if (removed_total) *removed_total = 0;
@@ -486,10 +462,7 @@ extern "C" int kb_prune(kb_handle* k, int32_t target, uint64_t* removed_total) {
     if (rc != RS_OK) return rc;
     kb_prune_state* p = k->prune;
     // behind whatever is queued on either of the handle's streams (the resident loop joins the agent's stream itself)
-    if (k->side) {
-        HIPCHK(k, hipEventRecord(p->ev_in, k->side));
-        HIPCHK(k, hipStreamWaitEvent(k->stream, p->ev_in, 0));
-    }
+    if (k->side && (rc = stream_after(k, &p->ev_in, k->side, k->stream)) != RS_OK) return rc;
     kb::PruneArgs a;
     memset(&a, 0, sizeof a);
     a.D = k->D;
@@ -511,26 +484,24 @@ extern "C" int kb_prune(kb_handle* k, int32_t target, uint64_t* removed_total) {
     const unsigned listed = (unsigned)p->h_info[0];
     const int rounds = (int)p->h_info[1];
     if (listed == 0) return RS_OK;
+    p->spans.on = k->spans.on;  // an event pair around one launch of a phase, when kernel timing is on (kb_set_kernel_timing)
     for (int r = 0; r < rounds; ++r) {
         hipEvent_t e;
-        if ((rc = kb_prune_time_begin(k, 0, &e)) != RS_OK) return rc;
+        HIPCHK(k, p->spans.begin(k->stream, 0, &e));
         hipLaunchKernelGGL(kb::prune_choose_kernel, dim3(listed), dim3(256), 0, k->stream, a);
         if (e) HIPCHK(k, hipEventRecord(e, k->stream));
         hipLaunchKernelGGL(kb::prune_plan_kernel, dim3(1), dim3(1024), 0, k->stream, a);
-        if ((rc = kb_prune_time_begin(k, 1, &e)) != RS_OK) return rc;
+        HIPCHK(k, p->spans.begin(k->stream, 1, &e));
         hipLaunchKernelGGL(kb::prune_downdate_kernel, dim3((unsigned)p->grid), dim3(256), 0, k->stream, a);
         if (e) HIPCHK(k, hipEventRecord(e, k->stream));
-        if ((rc = kb_prune_time_begin(k, 2, &e)) != RS_OK) return rc;
+        HIPCHK(k, p->spans.begin(k->stream, 2, &e));
         hipLaunchKernelGGL(kb::prune_move_kernel, dim3(listed), dim3(256), 0, k->stream, a);
         if (e) HIPCHK(k, hipEventRecord(e, k->stream));
     }
     hipLaunchKernelGGL(kb::prune_finish_kernel, dim3(listed), dim3(256), 0, k->stream, a);
     HIPCHK(k, hipGetLastError());
     HIPCHK(k, hipMemcpyAsync(p->h_info, p->d_info, sizeof(unsigned long long) * 8, hipMemcpyDeviceToHost, k->stream));
-    if (k->side) {
-        HIPCHK(k, hipEventRecord(p->ev_out, k->stream));
-        HIPCHK(k, hipStreamWaitEvent(k->side, p->ev_out, 0));
-    }
+    if (k->side && (rc = stream_after(k, &p->ev_out, k->stream, k->side)) != RS_OK) return rc;
     HIPCHK(k, hipStreamSynchronize(k->stream));
     k->gemm_fresh = false;
     if (removed_total) *removed_total = (uint64_t)p->h_info[3];
@@ -575,12 +546,9 @@ extern "C" int kb_prune_time_ms(kb_handle* k, double ms[3], int64_t n[3]) {
     if (!p) return RS_OK;
     HIPCHK(k, hipSetDevice(k->device));
     HIPCHK(k, hipStreamSynchronize(k->stream));
-    for (size_t i = 0; i < p->ev_used; ++i) {
-        float t = 0.f;
-        HIPCHK(k, hipEventElapsedTime(&t, p->ev[i].first, p->ev[i].second));
-        ms[p->ev_kind[i]] += t;
-        n[p->ev_kind[i]] += 1;
-    }
-    p->ev_used = 0;
+    HIPCHK(k, p->spans.drain([&](int kind, double t) {
+        ms[kind] += t;
+        n[kind] += 1;
+    }));
     return RS_OK;
 }

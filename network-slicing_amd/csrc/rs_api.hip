@@ -11,6 +11,8 @@
 #include <string>
 #include <vector>
 
+#include "rs_host.h"
+
 // Developer knobs (sweep switches, the guard bands, the fault injector of the shared step's abort path) are read from the
 // environment only by the test build (make dev: -DRS_DEV -> build/libranslice_dev.so, loaded explicitly by the tests that turn
 // them: ranslice._lib.load(dev=True)).  The production library reads none of them.
@@ -157,25 +159,13 @@ struct rs_handle {
     int32_t* d_la_err = nullptr; // [n_envs] capacity flags raised in a replica's branches during the last search
     // device-resident policy interface (rs_policy_io.hip), created by its first call; not a region of the saved state either
     struct PolicyIo* pio = nullptr;
-    // kernel timing
-    bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-    size_t ev_used = 0;
+    EventSpans spans;  // kernel timing (rs_set_kernel_timing): a pair around the primary step launches of every step
     std::string err;
 };
 
 static int auto_hint(const rs_handle* h);
 
 static void drop_graph(rs_handle* h);
-
-#define HIPCHK(h, call)                                                                              \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                            \
-            return RS_EHIP;                                                                          \
-        }                                                                                            \
-    } while (0)
 
 template <class T>
 static int dalloc(rs_handle* h, T** p, size_t n) {
@@ -679,10 +669,7 @@ extern "C" void rs_destroy(rs_handle* h) {
         if (h->fps) (void)hipFree(h->fps);
     }
     if (h->d_trace) (void)hipFree(h->d_trace);
-    for (auto& e : h->ev) {
-        (void)hipEventDestroy(e.first);
-        (void)hipEventDestroy(e.second);
-    }
+    h->spans.release();
     if (h->side) (void)hipStreamDestroy(h->side);
     if (h->side2) (void)hipStreamDestroy(h->side2);
     if (h->side3) (void)hipStreamDestroy(h->side3);
@@ -718,11 +705,8 @@ extern "C" int rs_device_mem_info(int device, uint64_t* free_bytes, uint64_t* to
 
 // FNV-1a over the tables as rs_load_fading left them (row count, columns, samples, column flags): rs_fork compares it
 static uint64_t fading_hash(const rs_handle* h) {
-    uint64_t x = 1469598103934665603ull;
-    auto mix = [&x](const void* p, size_t n) {
-        const unsigned char* c = (const unsigned char*)p;
-        for (size_t i = 0; i < n; ++i) x = (x ^ c[i]) * 1099511628211ull;
-    };
+    uint64_t x = kFnvOffsetBasis;
+    auto mix = [&x](const void* p, size_t n) { x = fnv1a(p, n, x); };
     mix(&h->hdev.P, sizeof h->hdev.P);
     for (int f = 0; f < RS_N_TRACES; ++f) {
         mix(&h->hdev.T[f], sizeof h->hdev.T[f]);
@@ -916,6 +900,27 @@ extern "C" int rs_reset(rs_handle* h, const uint64_t* seeds, float* obs) {
     return RS_OK;
 }
 
+// what every step kernel is handed: zeroed, with the fields the multiplexed and the per-slice step share filled in
+static StepArgs step_args(const rs_handle* h) {
+    StepArgs a;
+    memset(&a, 0, sizeof a);
+    a.D = h->ddev;
+    a.S = h->d_st;
+    a.fad = h->fad;
+    a.fad32 = h->fad32;
+    a.fps = h->fps;
+    a.fad_valid = h->fad_valid;
+    a.actions = h->d_actions;
+    a.run = h->d_run;
+    a.obs = h->d_obs;
+    a.labels = h->d_labels;
+    a.violations = h->d_viol;
+    a.info = h->d_info;
+    a.counters = h->d_counters;
+    a.trace = h->d_trace;
+    return a;
+}
+
 static int launch_step(rs_handle* h) {
     if (!h->is_reset) {
         h->err = "rs_step: call rs_reset first";
@@ -927,38 +932,12 @@ static int launch_step(rs_handle* h) {
     }
     if (h->mux) {
         if (h->n_tasks > 0) {
-            StepArgs a;
-            memset(&a, 0, sizeof a);
-            a.D = h->ddev;
-            a.S = h->d_st;
-            a.fad = h->fad;
-            a.fad32 = h->fad32;
-            a.fps = h->fps;
-            a.fad_valid = h->fad_valid;
-            a.actions = h->d_actions;
-            a.run = h->d_run;
-            a.obs = h->d_obs;
-            a.labels = h->d_labels;
-            a.violations = h->d_viol;
-            a.info = h->d_info;
-            a.counters = h->d_counters;
-            a.trace = h->d_trace;
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (h->timing) {
-                if (h->ev_used == h->ev.size()) {
-                    hipEvent_t a0, a1;
-                    HIPCHK(h, hipEventCreate(&a0));
-                    HIPCHK(h, hipEventCreate(&a1));
-                    h->ev.emplace_back(a0, a1);
-                }
-                e0 = h->ev[h->ev_used].first;
-                e1 = h->ev[h->ev_used].second;
-                h->ev_used++;
-                HIPCHK(h, hipEventRecord(e0, h->stream));
-            }
+            StepArgs a = step_args(h);
+            hipEvent_t e1;
+            HIPCHK(h, h->spans.begin(h->stream, 0, &e1));
             if (h->trace_on) hipLaunchKernelGGL((embb_mux_step_kernel<true>), dim3((unsigned)h->cfg.n_envs), dim3(64), 0, h->stream, a);
             else hipLaunchKernelGGL((embb_mux_step_kernel<false>), dim3((unsigned)h->cfg.n_envs), dim3(64), 0, h->stream, a);
-            if (h->timing) HIPCHK(h, hipEventRecord(e1, h->stream));
+            if (e1) HIPCHK(h, hipEventRecord(e1, h->stream));
         }
         if (h->cfg.n_mmtc > 0) {
             rs::MtcArgs ma;
@@ -991,41 +970,11 @@ static int launch_step(rs_handle* h) {
         HIPCHK(h, hipEventRecord(h->ev_join, h->side));
     }
     if (h->n_tasks > 0) {
-        StepArgs a;
-        a.D = h->ddev;
-        a.S = h->d_st;
-        a.fad = h->fad;
-        a.fad32 = h->fad32;
-        a.fps = h->fps;
-        a.fad_valid = h->fad_valid;
-        a.actions = h->d_actions;
-        a.run = h->d_run;
-        a.obs = h->d_obs;
-        a.labels = h->d_labels;
-        a.violations = h->d_viol;
-        a.info = h->d_info;
-        a.counters = h->d_counters;
-        a.trace = h->d_trace;
+        StepArgs a = step_args(h);
         a.sections = h->d_sections;
         a.redo = h->d_redo;
         a.pace = h->d_pace;
-        a.replay = 0;
-        a.order = nullptr;
-        a.spread = 0;
-        a.order_off = 0;
         a.order_cnt = -1;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (h->timing) {
-            if (h->ev_used == h->ev.size()) {
-                hipEvent_t a0, a1;
-                HIPCHK(h, hipEventCreate(&a0));
-                HIPCHK(h, hipEventCreate(&a1));
-                h->ev.emplace_back(a0, a1);
-            }
-            e0 = h->ev[h->ev_used].first;
-            e1 = h->ev[h->ev_used].second;
-            h->ev_used++;
-        }
         hipStream_t lstream = h->stream;
         auto launch = [&](int g) {
             // at most one wave per SIMD of the chip: one task per wave (StepArgs::spread)
@@ -1083,7 +1032,8 @@ static int launch_step(rs_handle* h) {
             a.order = h->d_order;
         }
         // the event pair brackets the step launches of the step (without a split: what rocprofv3 lists as embb_step_kernel<G,...>)
-        if (h->timing) HIPCHK(h, hipEventRecord(e0, h->stream));
+        hipEvent_t e1;
+        HIPCHK(h, h->spans.begin(h->stream, 0, &e1));
         if (a.order && seg_head + seg_light > 0) {
             const int seg_mid = h->n_tasks - seg_head - seg_light;
             HIPCHK(h, hipEventRecord(h->ev_fork2, h->stream));
@@ -1123,7 +1073,7 @@ static int launch_step(rs_handle* h) {
         } else {
             launch(h->group);
         }
-        if (h->timing) HIPCHK(h, hipEventRecord(e1, h->stream));
+        if (e1) HIPCHK(h, hipEventRecord(e1, h->stream));
         a.order = nullptr;
         if (h->group < 32) {
             a.replay = 1;
@@ -1266,7 +1216,7 @@ extern "C" int rs_run_random(rs_handle* h, uint64_t seed, uint64_t step_index0, 
     }
     hipLaunchKernelGGL(set_run_kernel, dim3(1), dim3(1), 0, h->stream, h->d_run, seed, step_index0);
     int done = 0, rc;
-    if (use_graph && !h->timing && n_steps >= 2) {
+    if (use_graph && !h->spans.on && n_steps >= 2) {
         if (h->gexec && h->graph_par != h->order_par) {  // realign with the parity the graph was captured at
             if ((rc = enqueue_scripted_step(h)) != RS_OK) return rc;
             done += 1;
@@ -1399,8 +1349,8 @@ extern "C" int rs_get_task_profile(rs_handle* h, uint64_t* out) {
 
 extern "C" int rs_set_kernel_timing(rs_handle* h, int enable) {
     if (!h) return RS_EINVAL;
-    h->timing = enable != 0;
-    h->ev_used = 0;
+    h->spans.on = enable != 0;
+    h->spans.reset();
     return RS_OK;
 }
 
@@ -1409,18 +1359,17 @@ extern "C" int rs_kernel_time_stats_ms(rs_handle* h, double out[3], int64_t* lau
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     double tot = 0.0, mn = 0.0, mx = 0.0;
-    for (size_t i = 0; i < h->ev_used; ++i) {
-        float ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms, h->ev[i].first, h->ev[i].second));
+    int64_t n = 0;
+    HIPCHK(h, h->spans.drain([&](int, double ms) {
         tot += ms;
-        mn = (i == 0 || ms < mn) ? ms : mn;
+        mn = (n == 0 || ms < mn) ? ms : mn;
         mx = ms > mx ? ms : mx;
-    }
-    out[0] = h->ev_used ? tot / (double)h->ev_used : 0.0;
+        n += 1;
+    }));
+    out[0] = n ? tot / (double)n : 0.0;
     out[1] = mn;
     out[2] = mx;
-    if (launches) *launches = (int64_t)h->ev_used;
-    h->ev_used = 0;
+    if (launches) *launches = n;
     return RS_OK;
 }
 
@@ -1449,12 +1398,17 @@ struct rs_state_header {
     int64_t clock, steps;
     int32_t order_par, graph_par, block_hint, hint_auto, is_reset, pad;
 };
+// the main stream and every side stream the handle has
+static int sync_streams(rs_handle* h) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (hipStream_t s : {h->side, h->side2, h->side3})
+        if (s) HIPCHK(h, hipStreamSynchronize(s));
+    return RS_OK;
+}
 static const uint64_t kRsStateMagic = 0x52534c4943453034ull;  // "RSLICE04"
 static uint64_t rs_cfg_hash(const rs_handle* h) {
-    uint64_t x = 1469598103934665603ull;
-    const unsigned char* p = (const unsigned char*)&h->cfg;
-    for (size_t i = 0; i < sizeof h->cfg; ++i) x = (x ^ p[i]) * 1099511628211ull;
-    for (auto& r : h->regions) x = (x ^ (uint64_t)r.second) * 1099511628211ull;
+    uint64_t x = fnv1a(&h->cfg, sizeof h->cfg);
+    for (auto& r : h->regions) x = fnv1a_step(x, (uint64_t)r.second);
     return x;
 }
 extern "C" int rs_state_bytes(rs_handle* h, uint64_t* bytes) {
@@ -1472,10 +1426,7 @@ extern "C" int rs_save_state(rs_handle* h, void* blob, uint64_t bytes) {
         return RS_EINVAL;
     }
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->side) HIPCHK(h, hipStreamSynchronize(h->side));
-    if (h->side2) HIPCHK(h, hipStreamSynchronize(h->side2));
-    if (h->side3) HIPCHK(h, hipStreamSynchronize(h->side3));
+    if (sync_streams(h) != RS_OK) return RS_EHIP;
     rs_state_header hd = {kRsStateMagic, (uint64_t)h->regions.size(), need, rs_cfg_hash(h), (int64_t)h->clock, (int64_t)h->steps,
                           h->order_par, h->graph_par, h->block_hint, h->hint_auto ? 1 : 0, h->is_reset ? 1 : 0, 0};
     memcpy(blob, &hd, sizeof hd);
@@ -1498,10 +1449,7 @@ extern "C" int rs_load_state(rs_handle* h, const void* blob, uint64_t bytes) {
         return RS_EINVAL;
     }
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->side) HIPCHK(h, hipStreamSynchronize(h->side));
-    if (h->side2) HIPCHK(h, hipStreamSynchronize(h->side2));
-    if (h->side3) HIPCHK(h, hipStreamSynchronize(h->side3));
+    if (sync_streams(h) != RS_OK) return RS_EHIP;
     drop_graph(h);
     const char* o = (const char*)blob + sizeof hd;
     for (auto& r : h->regions) {

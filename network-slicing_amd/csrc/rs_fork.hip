@@ -185,10 +185,7 @@ static int fork_table(rs_handle* dst, rs_handle* src, bool with_actions, rs::For
 static uint64_t fork_cfg_hash(const rs_handle* h) {
     rs_config c = h->cfg;
     c.n_envs = 0;
-    uint64_t x = 1469598103934665603ull;
-    const unsigned char* p = (const unsigned char*)&c;
-    for (size_t i = 0; i < sizeof c; ++i) x = (x ^ p[i]) * 1099511628211ull;
-    return x;
+    return fnv1a(&c, sizeof c);
 }
 
 static int fork_check(rs_handle* dst, rs_handle* src, const char* who) {
@@ -208,11 +205,6 @@ static int fork_check(rs_handle* dst, rs_handle* src, const char* who) {
         dst->err = std::string(who) + ": the handles' fading tables are not identical";
         return RS_ESTATE;
     }
-    return RS_OK;
-}
-
-static int ensure_event(rs_handle* h, hipEvent_t* e) {
-    if (!*e) HIPCHK(h, hipEventCreateWithFlags(e, hipEventDisableTiming));
     return RS_OK;
 }
 
@@ -258,8 +250,7 @@ extern "C" int rs_fork(rs_handle* dst, rs_handle* src, const int32_t* src_index)
     else HIPCHK(dst, hipEventSynchronize(dst->ev_fork_out));
     memcpy(dst->h_fork_idx, src_index, sizeof(int32_t) * n_dst);
     // after src's queued work (its finalize_kernel has joined its side streams); src's next step waits for the gather
-    HIPCHK(dst, hipEventRecord(dst->ev_fork_in, src->stream));
-    HIPCHK(dst, hipStreamWaitEvent(dst->stream, dst->ev_fork_in, 0));
+    if ((rc = stream_after(dst, &dst->ev_fork_in, src->stream, dst->stream)) != RS_OK) return rc;
     HIPCHK(dst, hipMemcpyAsync(dst->d_fork_idx, dst->h_fork_idx, sizeof(int32_t) * n_dst, hipMemcpyHostToDevice,
                                dst->stream));
     a.index = dst->d_fork_idx;
@@ -269,9 +260,7 @@ extern "C" int rs_fork(rs_handle* dst, rs_handle* src, const int32_t* src_index)
     hipLaunchKernelGGL(rs::fork_gather_kernel, dim3((unsigned)((n_dst + 3) / 4)), dim3(256), 0, dst->stream, a);
     HIPCHK(dst, hipGetLastError());
     if ((rc = fork_adopt(dst, src)) != RS_OK) return rc;
-    HIPCHK(dst, hipEventRecord(dst->ev_fork_out, dst->stream));
-    HIPCHK(dst, hipStreamWaitEvent(src->stream, dst->ev_fork_out, 0));
-    return RS_OK;
+    return stream_after(dst, &dst->ev_fork_out, dst->stream, src->stream);
 }
 
 static void fork_release(rs_handle* h) {
@@ -395,8 +384,7 @@ extern "C" int rs_step_clairvoyant(rs_handle* h, int32_t* actions_out, float* ob
     a.acts_src = h->d_actions;
     a.acts_dst = B->d_actions;
     // every round of every chunk on the branch handle's stream, behind h's queued work; h's real step behind the last select
-    HIPCHK(h, hipEventRecord(B->ev_fork_in, h->stream));
-    HIPCHK(h, hipStreamWaitEvent(B->stream, B->ev_fork_in, 0));
+    if ((rc = stream_after(h, &B->ev_fork_in, h->stream, B->stream)) != RS_OK) return rc;
     HIPCHK(h, hipMemsetAsync(h->d_la_err, 0, sizeof(int32_t) * N, B->stream));
     for (int s = 0; s < S; ++s)
         for (int c0 = 0; c0 < N; c0 += chunk) {
@@ -417,8 +405,7 @@ extern "C" int rs_step_clairvoyant(rs_handle* h, int32_t* actions_out, float* ob
                                h->la_widest, h->d_actions, h->d_la_err);
             HIPCHK(h, hipGetLastError());
         }
-    HIPCHK(h, hipEventRecord(B->ev_fork_out, B->stream));
-    HIPCHK(h, hipStreamWaitEvent(h->stream, B->ev_fork_out, 0));
+    if ((rc = stream_after(h, &B->ev_fork_out, B->stream, h->stream)) != RS_OK) return rc;
     if ((rc = launch_step(h)) != RS_OK) return rc;
     if ((rc = rs_fetch(h, actions_out, obs, reward, labels, violations)) != RS_OK) return rc;
     std::vector<int32_t> e((size_t)N);

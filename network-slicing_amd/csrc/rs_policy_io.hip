@@ -280,10 +280,7 @@ extern "C" int rs_step_device(rs_handle* h, int kind, const void* actions_device
     }
     hipStream_t cs = (hipStream_t)caller_stream;
     const bool foreign = cs != h->stream;
-    if (foreign) {
-        HIPCHK(h, hipEventRecord(p->ev_in, cs));
-        HIPCHK(h, hipStreamWaitEvent(h->stream, p->ev_in, 0));
-    }
+    if (foreign && (rc = stream_after(h, &p->ev_in, cs, h->stream)) != RS_OK) return rc;
     const unsigned nb = (unsigned)((h->cfg.n_envs + 255) / 256);
     rs::FrontArgs f;
     f.D = h->ddev;
@@ -317,11 +314,7 @@ extern "C" int rs_step_device(rs_handle* h, int kind, const void* actions_device
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(rs::policy_back_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, b);
     HIPCHK(h, hipGetLastError());
-    if (foreign) {
-        HIPCHK(h, hipEventRecord(p->ev_out, h->stream));
-        HIPCHK(h, hipStreamWaitEvent(cs, p->ev_out, 0));
-    }
-    return RS_OK;
+    return foreign ? stream_after(h, &p->ev_out, h->stream, cs) : RS_OK;
 }
 
 extern "C" int rs_stream_join(rs_handle* h, void* caller_stream) {
@@ -331,9 +324,7 @@ extern "C" int rs_stream_join(rs_handle* h, void* caller_stream) {
     int rc = pio_ensure(h);
     if (rc != RS_OK) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipEventRecord(h->pio->ev_out, h->stream));
-    HIPCHK(h, hipStreamWaitEvent(cs, h->pio->ev_out, 0));
-    return RS_OK;
+    return stream_after(h, &h->pio->ev_out, h->stream, cs);
 }
 
 extern "C" int rs_set_action_table(rs_handle* h, const int32_t* table, int32_t n_actions) {
