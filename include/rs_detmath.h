@@ -7,8 +7,12 @@
  * primitives (+, -, *, /, sqrt, fma) in a fixed order.  The same text compiles as C
  * (gcc, oracle) and as HIP device code (hipcc, gfx950); both translation units are built
  * with -ffp-contract=off so that no fused multiply-add is introduced or removed behind
- * our back.  Accuracy is ~1-2 ulp, far inside the 1e-12 relative tolerance at which the
- * oracle is pinned against the numpy reference (tests/golden, fixture G2).
+ * our back.  Accuracy in ulps of the correctly rounded result, measured against 220-bit mpmath
+ * on some 40,000 arguments per function, branch seams included (tests/test_primitives.py):
+ *     rs_exp 0.84    rs_log 1.89    rs_acos 1.09    rs_log10 3.89
+ * (rs_log10 is worst next to 1, where the rounding of log(x) times log10(e) adds to rs_log's own
+ * error).  The test asserts 1.0 / 2.0 / 1.5 / 4.5.  All of this is far inside the 1e-12 relative
+ * tolerance at which the oracle is pinned against the numpy reference (tests/golden, fixture G2).
  *
  * Where the reference calls these: np.exp/np.log in sigmoid/inv_sigmoid
  * (reference channel_models.py:35-41), np.log10/np.arccos/np.sqrt in macro_cell/location

@@ -1472,3 +1472,6 @@ extern "C" int rs_load_state(rs_handle* h, const void* blob, uint64_t bytes) {
 #include "kb_api.hip"
 #include "kb_fork.hip"
 #include "kb_prune.hip"
+#ifdef RS_DEV
+#include "rs_probe.hip"  // rs_dev_probe: the arithmetic primitives one by one (tests/test_gpu_primitives.py)
+#endif

@@ -654,6 +654,11 @@ __device__ __forceinline__ float fast_sigmoid(float v, float hi, float c1, float
     const float e = __builtin_amdgcn_exp2f(t2);
     return __builtin_amdgcn_rcpf(1.0f + e);
 }
+// s* - ref(mcs) in dB of the draw u, (B - ln((1 - u) / u)) / A on the transcendental unit: lf = ln((1 - u) / u), then dq.  Macros, not a
+// function: with the chain in a helper the step kernel's instances were scheduled differently (the loads of rx_B and rx_invA moved),
+// and the test build's probe (rs_probe.hip) has to run the very text the kernel runs.
+#define RS_RX_LF(u) (0.6931471805599453f * __builtin_amdgcn_logf((float)(1.0 - (u)) * __builtin_amdgcn_rcpf((float)(u))))
+#define RS_RX_DQ(D, lf) (((D)->rx_B - (lf)) * (D)->rx_invA)
 typedef float rs_f4u __attribute__((ext_vector_type(4), aligned(4)));
 // sum of the sigmoids of the (up to four) elements k0 .. k0 + 3 < n held in q: (s0 + s1) + (s2 + s3) in float32
 __device__ __forceinline__ float fast_quad(rs_f4u q, int k0, int n, float hi, float c1, float loc) {
@@ -1622,8 +1627,8 @@ __global__ __launch_bounds__(256, (G == 16 && !TRACE) ? RS_OCC : RS_OCC_OTHER) v
                         u = rs_stream_uniform(&st);  // the draw the reception step consumes below
                     }
                     central = u >= 1.0e-4 && u <= 1.0 - 1.0e-4;
-                    const float lf = 0.6931471805599453f * __builtin_amdgcn_logf((float)(1.0 - u) * __builtin_amdgcn_rcpf((float)u));
-                    const float dq = (D->rx_B - lf) * D->rx_invA;  // s* - ref(mcs), dB
+                    const float lf = RS_RX_LF(u);
+                    const float dq = RS_RX_DQ(D, lf);  // s* - ref(mcs), dB
                     const float ystar = fast_sigmoid((float)((ref - x0) + (double)dq), 0.0f, L_c1[mod], 0.0f);
                     St = single ? (double)dq : (double)rbs * (double)ystar;
                 };

@@ -194,5 +194,8 @@ def load(dev=None):
     for name in EXPORTS:
         if name not in ('rs_last_error', 'rs_destroy', 'kb_last_error', 'kb_destroy'):
             getattr(L, name).restype = C.c_int
+    if hasattr(L, 'rs_dev_probe'):  # the test build only (csrc/rs_probe.hip): one arithmetic primitive per element
+        L.rs_dev_probe.argtypes = [C.c_int, C.c_int, vp, vp, C.c_int64, dp]
+        L.rs_dev_probe.restype = C.c_int
     _libs[path] = L
     return L

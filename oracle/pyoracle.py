@@ -70,6 +70,15 @@ def lib():
         for f in ('rso_exp', 'rso_log', 'rso_acos'):
             getattr(L, f).restype = C.c_double
             getattr(L, f).argtypes = [C.c_double]
+        _up = C.POINTER(C.c_uint32)
+        L.rso_detmath.argtypes = [C.c_int, _dp, _dp, _dp, C.c_int64, _dp]
+        L.rso_philox_block.argtypes = [_up, _up, C.c_int64]
+        L.rso_philox_block.restype = None
+        L.rso_stream_probe.argtypes = [C.c_int, _up, _dp, C.c_int64, _dp]
+        L.rso_walker_redraw.argtypes = [_up, C.c_int, _ip, C.c_int64]
+        L.rso_walker_redraw.restype = None
+        L.rso_macro_cell_stream.restype = C.c_double
+        L.rso_macro_cell_stream.argtypes = [C.POINTER(RsConfig), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _up]
         _lib = L
     return _lib
 
@@ -221,6 +230,62 @@ def macro_cell(cfg, uv, normal):
     used = C.c_int32()
     v = lib().rso_macro_cell(C.byref(cfg), _p(uv, _dp), len(uv), float(normal), C.byref(used))
     return v, used.value
+
+
+# ---- the arithmetic primitives one by one (rs_oracle.h; the same op numbers as rs_dev_probe of the test build)
+OPS = ('EXP_OOL', 'EXP_INLINE', 'EXP_NONPOS', 'EXP2_OOL', 'LOG_OOL', 'LOG_INLINE', 'LOG10', 'ACOS', 'SIGMOID', 'SIGMOID2',
+       'INV_SIGMOID', 'DIV', 'SQRT', 'RINT', 'FMA', 'PHILOX', 'UNIFORM', 'EXPONENTIAL', 'INTEGERS', 'PM1', 'NORMAL', 'WALKER',
+       'MACRO_CELL', 'LANE_PAIRWISE', 'TEAM_PAIRWISE', 'FAST_SIGMOID', 'RX_DQ')
+OP = {name: i for i, name in enumerate(OPS)}
+
+
+def _params(params):
+    p = np.zeros(4, dtype=np.float64)
+    p[:len(params)] = params
+    return p
+
+
+def detmath(op, a, b=None, params=()):
+    """out[i] = op(a[i]) (rso_detmath); b: the divisor of DIV, or multiplier and addend (2 n values) of FMA"""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = np.ascontiguousarray(b if b is not None else np.zeros(0), dtype=np.float64)
+    assert len(b) == {OP['DIV']: len(a), OP['FMA']: 2 * len(a)}.get(OP[op], 0)
+    out = np.zeros(len(a), dtype=np.float64)
+    rc = lib().rso_detmath(OP[op], _p(a, _dp), _p(b, _dp), _p(out, _dp), len(a), _p(_params(params), _dp))
+    assert rc == 0, rc
+    return out
+
+
+def philox_block(words):
+    """first two output words of Philox4x32-10 for rows (c0, c1, c2, c3, k0, k1)"""
+    w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, 6)
+    out = np.zeros((len(w), 2), dtype=np.uint32)
+    lib().rso_philox_block(_p(w, C.POINTER(C.c_uint32)), _p(out, C.POINTER(C.c_uint32)), len(w))
+    return out
+
+
+def stream_probe(kind, streams, params=()):
+    """(value, ctr afterwards) of one draw of `kind` on every stream row (key0, key1, slice, serial, ctr)"""
+    st = np.ascontiguousarray(streams, dtype=np.uint32).reshape(-1, 5)
+    out = np.zeros((len(st), 2), dtype=np.float64)
+    rc = lib().rso_stream_probe(OP[kind], _p(st, C.POINTER(C.c_uint32)), _p(out, _dp), len(st), _p(_params(params), _dp))
+    assert rc == 0, rc
+    return out
+
+
+def walker_redraw(rows, T):
+    """(findex, fstep) for rows (key0, key1, slice, serial, now, attempt)"""
+    w = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, 6)
+    out = np.zeros((len(w), 2), dtype=np.int32)
+    lib().rso_walker_redraw(_p(w, C.POINTER(C.c_uint32)), int(T), _p(out, _ip), len(w))
+    return out
+
+
+def macro_cell_stream(cfg, key, slice_id, serial, ctr):
+    """(nominal SINR, ctr afterwards) of the oracle's macro_cell on a Philox stream"""
+    after = C.c_uint32()
+    v = lib().rso_macro_cell_stream(C.byref(cfg), int(key), int(slice_id), int(serial), int(ctr), C.byref(after))
+    return v, after.value
 
 
 # ----------------------------------------------------------------------------- KBRL oracle

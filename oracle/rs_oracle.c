@@ -1115,3 +1115,75 @@ double rso_bench_run(rs_oracle* o, uint64_t action_seed, int64_t replica, uint64
 double rso_exp(double x) { return rs_exp(x); }
 double rso_log(double x) { return rs_log(x); }
 double rso_acos(double x) { return rs_acos(x); }
+
+/* ---- the primitives one by one (rs_oracle.h) */
+int rso_detmath(int op, const double* a, const double* b, double* out, int64_t n, const double* params) {
+    const double x0 = params ? params[0] : 0.0, k = params ? params[1] : 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+        const double x = a[i];
+        switch (op) {
+            case RSO_EXP_OOL: case RSO_EXP_INLINE: case RSO_EXP2_OOL: out[i] = rs_exp(x); break;
+            case RSO_EXP_NONPOS: out[i] = rs_exp_nonpos(x); break;
+            case RSO_LOG_OOL: case RSO_LOG_INLINE: out[i] = rs_log(x); break;
+            case RSO_LOG10: out[i] = rs_log10(x); break;
+            case RSO_ACOS: out[i] = rs_acos(x); break;
+            case RSO_SIGMOID: case RSO_SIGMOID2: out[i] = rs_sigmoid(x, x0, k); break;
+            case RSO_INV_SIGMOID: out[i] = rs_inv_sigmoid(x, x0, k); break;
+            case RSO_DIV: out[i] = x / b[i]; break;
+            case RSO_SQRT: out[i] = RS_SQRT(x); break;
+            case RSO_RINT: out[i] = RS_RINT(x); break;
+            case RSO_FMA: out[i] = RS_FMA(x, b[i], b[n + i]); break;
+            default: return RS_EINVAL;
+        }
+    }
+    return 0;
+}
+
+void rso_philox_block(const uint32_t* in, uint32_t* out, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t* w = in + 6 * i;
+        rs_philox4x32_10(w[0], w[1], w[2], w[3], w[4], w[5], &out[2 * i], &out[2 * i + 1]);
+    }
+}
+
+int rso_stream_probe(int kind, const uint32_t* st, double* out, int64_t n, const double* params) {
+    if (kind < RSO_UNIFORM || kind > RSO_NORMAL) return RS_EINVAL;
+    if (!params && kind != RSO_UNIFORM && kind != RSO_PM1) return RS_EINVAL;
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t* w = st + 5 * i;
+        rs_stream s = {w[0], w[1], w[2], w[3], w[4]};
+        double v = 0.0;
+        switch (kind) {
+            case RSO_UNIFORM: v = rs_stream_uniform(&s); break;
+            case RSO_EXPONENTIAL: v = rs_stream_exponential(&s, params[0]); break;
+            case RSO_INTEGERS: v = (double)rs_stream_integers(&s, (int64_t)params[0]); break;
+            case RSO_PM1: v = (double)rs_stream_pm1(&s); break;
+            default: v = rs_stream_normal(&s, params[0], params[1]); break;
+        }
+        out[2 * i] = v;
+        out[2 * i + 1] = (double)s.ctr;
+    }
+    return 0;
+}
+
+void rso_walker_redraw(const uint32_t* in, int T, int32_t* out, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t* w = in + 6 * i;
+        int fi, fs;
+        rs_walker_redraw(w[0], w[1], w[2], w[3], w[4], w[5], T, &fi, &fs);
+        out[2 * i] = fi;
+        out[2 * i + 1] = fs;
+    }
+}
+
+double rso_macro_cell_stream(const rs_config* cfg, uint64_t key, uint32_t slice, uint32_t serial, uint32_t ctr,
+                             uint32_t* ctr_after) {
+    rs_oracle* o = (rs_oracle*)calloc(1, sizeof(rs_oracle)); /* use_tape = 0: the Philox streams */
+    if (!o) return rs_nan();
+    o->cfg = *cfg;
+    rs_stream s = {(uint32_t)key, (uint32_t)(key >> 32), slice, serial, ctr};
+    const double v = macro_cell(o, &s);
+    if (ctr_after) *ctr_after = s.ctr;
+    free(o);
+    return v;
+}

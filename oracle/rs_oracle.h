@@ -74,6 +74,30 @@ double rso_exp(double x);
 double rso_log(double x);
 double rso_acos(double x);
 
+/* ---- the arithmetic primitives one by one: the host side of rs_dev_probe (network-slicing_amd/csrc/rs_probe.hip, test build),
+ * same op numbers.  tests/test_primitives.py pins them against mpmath, the Random123 known answers and an integer restatement
+ * of Philox; tests/test_gpu_primitives.py compares the device with them bit for bit. */
+enum {
+    RSO_EXP_OOL = 0, RSO_EXP_INLINE, RSO_EXP_NONPOS, RSO_EXP2_OOL, RSO_LOG_OOL, RSO_LOG_INLINE, RSO_LOG10, RSO_ACOS,
+    RSO_SIGMOID, RSO_SIGMOID2, RSO_INV_SIGMOID, RSO_DIV, RSO_SQRT, RSO_RINT, RSO_FMA,
+    RSO_PHILOX, RSO_UNIFORM, RSO_EXPONENTIAL, RSO_INTEGERS, RSO_PM1, RSO_NORMAL
+};
+/* out[i] = op(a[i]) for i < n.  The host has one code shape per function, so the four exp ops all run rs_exp except
+ * RSO_EXP_NONPOS (rs_exp_nonpos), both log ops rs_log, both sigmoid ops rs_sigmoid; params = {x0, k} for the sigmoids.
+ * RSO_DIV: a[i] / b[i].  RSO_FMA: fma(a[i], b[i], b[n + i]) (b holds 2 n values).  Returns 0, or RS_EINVAL for another op. */
+int rso_detmath(int op, const double* a, const double* b, double* out, int64_t n, const double* params);
+/* in: n x (c0, c1, c2, c3, k0, k1); out: n x the block's first two words */
+void rso_philox_block(const uint32_t* in, uint32_t* out, int64_t n);
+/* kind = RSO_UNIFORM .. RSO_NORMAL on n streams st[n][5] = (key0, key1, slice, serial, ctr); params: exponential {scale},
+ * integers {n}, normal {loc, scale}; out[n][2] = (value, ctr afterwards) */
+int rso_stream_probe(int kind, const uint32_t* st, double* out, int64_t n, const double* params);
+/* in: n x (key0, key1, slice, serial, now, attempt); out: n x (findex, fstep) */
+void rso_walker_redraw(const uint32_t* in, int T, int32_t* out, int64_t n);
+/* the oracle's own macro_cell (generate_xy, the shadowing normal, the link budget) on the Philox stream (key, slice, serial) from
+ * draw `ctr`; *ctr_after = the stream's draw counter afterwards */
+double rso_macro_cell_stream(const rs_config* cfg, uint64_t key, uint32_t slice, uint32_t serial, uint32_t ctr,
+                             uint32_t* ctr_after);
+
 #ifdef __cplusplus
 }
 #endif
