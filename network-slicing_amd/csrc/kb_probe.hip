@@ -1,0 +1,68 @@
+// kb_probe.hip -- TEST BUILD ONLY (#included by rs_api.hip inside #ifdef RS_DEV; libranslice.so has none of it).
+//
+// Read-only accessors for a device test of the scoring chain: what kb_select_action (kb_kbrl.hip: bin_pass /
+// select_bin_big_body, select_gemm_kernel, add_direct_terms, score_single) left on the device, stage by stage, so that every
+// stage can be held to tests/scoring_mirror.py bit for bit (tests/test_gpu_scoring.py binds them).  Plain copies on
+// the agent's stream after it has drained: no kernel is launched, nothing on the device is written.
+//
+//   kb_dev_get_scores  K.F [T][256], K.Wg [T][256] and K.fdirect [T] as the last kb_select_action left them (rows of learners
+//                      with fewer than two landmarks hold no W: select_bin_* leaves them alone)
+//   kb_dev_get_rows    the first min(m, max_m) entries of one learner's KB_ROW_D0 / KB_ROW_E / KB_ROW_IDX rows, its
+//                      coefficients and last coordinates, and the handle's G table (256 entries)
+
+extern "C" int kb_dev_get_scores(kb_handle* k, double* F, double* W, int32_t* fdirect) {
+    if (!k) return RS_EINVAL;
+    if (k->D.shared) {
+        k->err = "kb_dev_get_scores: shared-dictionary handles keep no per-learner scores";
+        return RS_ESTATE;
+    }
+    HIPCHK(k, hipSetDevice(k->device));
+    HIPCHK(k, hipStreamSynchronize(k->stream));
+    const size_t T = (size_t)k->T;
+    if (F) HIPCHK(k, hipMemcpyAsync(F, k->K.F, sizeof(double) * T * 256, hipMemcpyDeviceToHost, k->stream));
+    if (W) HIPCHK(k, hipMemcpyAsync(W, k->K.Wg, sizeof(double) * T * 256, hipMemcpyDeviceToHost, k->stream));
+    if (fdirect) HIPCHK(k, hipMemcpyAsync(fdirect, k->K.fdirect, sizeof(int32_t) * T, hipMemcpyDeviceToHost, k->stream));
+    HIPCHK(k, hipStreamSynchronize(k->stream));
+    return RS_OK;
+}
+
+extern "C" int kb_dev_get_rows(kb_handle* k, int e, int s, int32_t max_m, int32_t* m_out, double* D0, double* E, int32_t* idx,
+                               double* coeff, double* lam, double* gtab) {
+    if (!k || e < 0 || e >= k->cfg.n_envs || s < 0 || s >= k->cfg.n_slices || max_m < 0) return RS_EINVAL;
+    HIPCHK(k, hipSetDevice(k->device));
+    HIPCHK(k, hipStreamSynchronize(k->stream));
+    const size_t dict = k->D.shared ? (size_t)s : (size_t)e * k->cfg.n_slices + s;
+    const int d = k->cfg.dims[s] + 1;
+    int32_t m = 0;
+    HIPCHK(k, hipMemcpy(&m, k->K.m + dict, sizeof m, hipMemcpyDeviceToHost));
+    if (m_out) *m_out = m;
+    if (gtab) HIPCHK(k, hipMemcpy(gtab, k->K.gtab, sizeof(double) * 256, hipMemcpyDeviceToHost));
+    const int take = m < max_m ? m : max_m;
+    if (take <= 0) return RS_OK;
+    const int nch = (take + KB_CH - 1) / KB_CH;
+    if (nch > k->D.max_shells) {
+        k->err = "kb_dev_get_rows: more landmarks than the shell table holds";
+        return RS_ESTATE;
+    }
+    std::vector<uint64_t> sh((size_t)nch);
+    HIPCHK(k, hipMemcpy(sh.data(), k->K.shell + dict * (size_t)k->D.max_shells, sizeof(uint64_t) * (size_t)nch, hipMemcpyDeviceToHost));
+    std::vector<double> page(KB_VEC);
+    for (int b = 0; b < nch; ++b) {
+        if (sh[b] == 0 || sh[b] + KB_VEC > k->D.pool_doubles) {  // (a shell the dictionary's size promises but the table lacks)
+            k->err = "kb_dev_get_rows: shell table entry out of the pool";
+            return RS_ESTATE;
+        }
+        HIPCHK(k, hipMemcpy(page.data(), k->K.pool + sh[b], sizeof(double) * KB_VEC, hipMemcpyDeviceToHost));
+        const int cnt = take - KB_CH * b < KB_CH ? take - KB_CH * b : KB_CH;
+        const int32_t* ix = (const int32_t*)(page.data() + KB_ROW_IDX * KB_CH);
+        for (int l = 0; l < cnt; ++l) {
+            const int j = KB_CH * b + l;
+            if (D0) D0[j] = page[KB_ROW_D0 * KB_CH + l];
+            if (E) E[j] = page[KB_ROW_E * KB_CH + l];
+            if (idx) idx[j] = ix[l];
+            if (coeff) coeff[j] = page[KB_ROW_CO * KB_CH + l];
+            if (lam) lam[j] = page[(d - 1) * KB_CH + l];
+        }
+    }
+    return RS_OK;
+}

@@ -91,10 +91,11 @@ def test_production_library_reads_no_developer_knob():
         assert k + b'\0' not in prod, k
         assert k + b'\0' in dev, k
     # the primitive probe (csrc/rs_probe.hip) is test tooling too: neither the entry point nor its kernels are in the product
-    for k in (b'rs_dev_probe', b'probe_kernel'):
+    # and so are the accessors of the agent's scoring chain (csrc/kb_probe.hip)
+    for k in (b'rs_dev_probe', b'probe_kernel', b'kb_dev_get_scores', b'kb_dev_get_rows'):
         assert k not in prod, k
         assert k in dev, k
-    assert 'rs_dev_probe' not in _lib.EXPORTS
+    assert not [n for n in _lib.EXPORTS if '_dev_' in n]
     for k in (b'RANSLICE_RCCL_LIB', b'KBRL_COLLECTIVE_TIMEOUT_S'):
         assert k in prod, k
     src = ''.join(open(os.path.join(ROOT, 'network-slicing_amd', 'csrc', f)).read() for f in ('rs_api.hip', 'kb_api.hip'))
