@@ -476,6 +476,23 @@ int kb_fork(kb_handle* dst, kb_handle* src, const int32_t* src_index);
  * kb_set_learning(k, 1), kb_get_learner with kinv != NULL, kb_save_state, kb_load_state, kb_fork and kb_reset (which would
  * empty dictionaries that can never be learned again) return RS_ESTATE. */
 int kb_deploy(kb_handle* src, const int32_t* src_index, int32_t n, kb_handle** out);
+/* kb_deploy BY REFERENCE: an inference-only handle of n replicas whose dictionaries are stored ONCE per distinct agent of
+ * src_index (vector pages only; agents nobody names are not stored), read-only and shared by all the replicas that name the
+ * agent.  Same arguments and checks as kb_deploy; src is a learning handle or a copy-deployed inference-only one.  Private per
+ * replica, copied exactly as kb_deploy copies it: control state (action, security factors, margins, adjusted, accuracies),
+ * tie-break stream (seed and counters), the observation the resident loop chose its last action in, the flag word verbatim;
+ * history buffers (kb_history_begin) are the handle's own, per replica.  kb_get_pool reports the store: exactly 512 bytes +
+ * 15,360 x the shells of the DISTINCT (agent, slice) dictionaries -- 30 agents fanned out onto 65,536 replicas cost 30
+ * agents' landmarks, not 65,536.  Selection is one fused
+ * kernel that scores up to sixteen replicas of an agent per pass over its landmarks and writes nothing into a dictionary's
+ * page; every replica's scores, action, margin, tie draws and counters are bit for bit those of a kb_deploy handle given the
+ * same src_index and states.  Works: kb_select_action, kb_step_resident, kb_run_resident (plain and hipGraph), kb_get_control,
+ * kb_set_adjusted, kb_get_stats, kb_get_flags, kb_get_pool, kb_history_begin / kb_history_fetch, kb_get_sizes and
+ * kb_get_learner with kinv == NULL (per replica, through the map), kb_synchronize, kb_destroy.  RS_ESTATE: everything a
+ * kb_deploy handle refuses; kb_predict and kb_get_kernel_row (they would write a cached row into a shared page); kb_prune;
+ * kb_deploy, kb_deploy_ref and kb_fork with the by-reference handle as source.  RS_EINVAL: a shared-dictionary src, an index
+ * out of range, n <= 0.  Ordered as kb_deploy: after src's queued work, and src's later work after the gather. */
+int kb_deploy_ref(kb_handle* src, const int32_t* src_index, int32_t n, kb_handle** out);
 /* on = 0: the resident loop (kb_step_resident, each step of kb_run_resident) runs select_action(new obs) only -- the
  * reference's loop body past learning_time (kbrl_control.py:131-133): dictionaries, accuracies and security factors stay as
  * they are; margins, adjusted, action and the tie-break counters move as select_action moves them; a history column is still

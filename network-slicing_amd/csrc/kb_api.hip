@@ -4,6 +4,7 @@
 #include "kb_kbrl.hip"
 
 struct kb_prune_state;  // kb_prune.hip
+struct kb_ref_state;    // kb_ref.hip
 
 struct kb_handle {
     kb_config cfg;
@@ -74,6 +75,7 @@ struct kb_handle {
     uint64_t* d_fork_base = nullptr; // [n_dict + 1] first pool double of every dictionary (exclusive scan of its shells' sizes)
     uint64_t* h_fork_total = nullptr;  // pinned: the scan's total
     kb_prune_state* prune = nullptr; // kb_prune's lists and the pruned counters: NOT a saved region (kb_prune.hip)
+    kb_ref_state* ref = nullptr;     // a by-reference handle (kb_deploy_ref): the store of shared dictionaries, the map, the groups (kb_ref.hip)
     EventSpans spans;  // kernel timing (kb_set_kernel_timing), by kind: 0 update phase, 1 select phase; ONE launch of: 2 heavy_matvec_kernel,
                        // 3 heavy_rank1_kernel, 4 select_bin_kernel, 5 heavy_finish_kernel, 6 select_gemm_kernel, 7 update_small_kernel
     double kind_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // mean per kind over the span the last kb_phase_times_ms call summed up
@@ -83,6 +85,11 @@ struct kb_handle {
 
 static void kb_prune_release(kb_handle* k);  // kb_prune.hip
 static void kb_prune_restart(kb_handle* k);  // the pruned counters start over (kb_reset, kb_load_state, kb_fork)
+// by-reference handles (kb_ref.hip): their dictionaries live in a store handle, (replica, slice) -> dictionary through a map
+static void kb_ref_release(kb_handle* k);
+static kb_handle* kb_ref_store(kb_handle* k);
+static int kb_ref_dict(kb_handle* k, size_t task);
+static int kb_ref_select(kb_handle* k, const float* d_state);  // the scoring of launch_select: one fused kernel
 
 template <class Tp>
 static int kalloc(kb_handle* k, Tp** p, size_t n, bool zero = true) {
@@ -450,6 +457,7 @@ extern "C" void kb_destroy(kb_handle* k) {
     if (k->h_fork_idx) (void)hipHostFree(k->h_fork_idx);
     if (k->h_fork_total) (void)hipHostFree(k->h_fork_total);
     kb_prune_release(k);
+    kb_ref_release(k);
     if (k->h_seen) (void)hipHostFree(k->h_seen);
     if (k->h_total) (void)hipHostFree(k->h_total);
     if (k->stream) (void)hipStreamDestroy(k->stream);
@@ -613,7 +621,11 @@ static int launch_select(kb_handle* k, const float* d_state, int32_t* d_action_o
     hipEvent_t e1;
     HIPCHK(k, k->spans.begin(k->stream, 1, &e1));
     if (a.gemm) launch_shared_gemm(k, d_state);
-    if (k->D.shared) {
+    if (k->ref) {  // shared read-only dictionaries: binning, product and scan in one kernel, no large-learner list
+        a.big_par = -1;
+        const int rc = kb_ref_select(k, d_state);
+        if (rc != RS_OK) return rc;
+    } else if (k->D.shared) {
         hipLaunchKernelGGL(kb::select_kernel, dim3((unsigned)k->T), dim3(64), 0, k->stream, a);
     } else {  // one agent per replica: a wave per learner bins its landmarks, then sixteen learners per workgroup are scored
               // as one product on the matrix cores
@@ -841,6 +853,10 @@ static int kb_one(kb_handle* k, int e, int s, const double* x, int y, bool updat
         k->err = "kb_update: an inference-only handle (kb_deploy) cannot learn: it holds no Kinv";
         return RS_ESTATE;
     }
+    if (k->ref) {
+        k->err = "kb_predict: a by-reference handle (kb_deploy_ref) shares read-only dictionaries: the cached kernel row would be written into a shared page";
+        return RS_ESTATE;
+    }
     HIPCHK(k, hipSetDevice(k->device));
     kb::OneArgs a;
     a.D = k->D;
@@ -915,12 +931,21 @@ extern "C" int kb_get_learner(kb_handle* k, int e, int s, int32_t* m_out, double
         return RS_ESTATE;
     }
     HIPCHK(k, hipSetDevice(k->device));
-    const size_t dict = k->D.shared ? (size_t)s : (size_t)e * k->cfg.n_slices + s;
+    size_t dict = k->D.shared ? (size_t)s : (size_t)e * k->cfg.n_slices + s;
+    kb_handle* p = k;  // the handle whose pool holds the dictionary
+    if (k->ref) {
+        p = kb_ref_store(k);
+        dict = (size_t)kb_ref_dict(k, dict);
+    }
     int32_t m = 0;
-    HIPCHK(k, hipMemcpyAsync(&m, k->K.m + dict, sizeof m, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(k, hipStreamSynchronize(k->stream));
+    HIPCHK(k, hipMemcpyAsync(&m, p->K.m + dict, sizeof m, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(k, hipStreamSynchronize(p->stream));
     if (m_out) *m_out = m;
-    if (m > 0 && (landmarks || coeff || kinv)) return kb_gather(k, (int)dict, k->cfg.dims[s] + 1, m, landmarks, coeff, kinv, nullptr);
+    if (m > 0 && (landmarks || coeff || kinv)) {
+        const int rc = kb_gather(p, (int)dict, k->cfg.dims[s] + 1, m, landmarks, coeff, kinv, nullptr);
+        if (rc != RS_OK && p != k) k->err = p->err;
+        return rc;
+    }
     return RS_OK;
 }
 
@@ -967,6 +992,10 @@ extern "C" int kb_get_stats(kb_handle* k, uint64_t stats[4]) {
 // GaussianKernel.k(x) of the last kb_predict on learner (e, s) (kernel.py:13-20): the cached row K_f, m entries
 extern "C" int kb_get_kernel_row(kb_handle* k, int e, int s, int32_t* m_out, double* row) {
     if (!k || e < 0 || e >= k->cfg.n_envs || s < 0 || s >= k->cfg.n_slices) return RS_EINVAL;
+    if (k->ref) {
+        k->err = "kb_get_kernel_row: a by-reference handle (kb_deploy_ref) shares read-only dictionaries and caches no kernel row";
+        return RS_ESTATE;
+    }
     HIPCHK(k, hipSetDevice(k->device));
     const size_t task = (size_t)e * k->cfg.n_slices + s;
     const size_t dict = k->D.shared ? (size_t)s : task;
@@ -982,6 +1011,14 @@ extern "C" int kb_get_kernel_row(kb_handle* k, int e, int s, int32_t* m_out, dou
 extern "C" int kb_get_sizes(kb_handle* k, int32_t* m_out) {
     if (!k || !m_out) return RS_EINVAL;
     HIPCHK(k, hipSetDevice(k->device));
+    if (k->ref) {  // per replica, through the map
+        kb_handle* p = kb_ref_store(k);
+        std::vector<int32_t> ms((size_t)p->n_dict);
+        HIPCHK(k, hipMemcpyAsync(ms.data(), p->K.m, sizeof(int32_t) * ms.size(), hipMemcpyDeviceToHost, p->stream));
+        HIPCHK(k, hipStreamSynchronize(p->stream));
+        for (size_t t = 0; t < (size_t)k->T; ++t) m_out[t] = ms[(size_t)kb_ref_dict(k, t)];
+        return RS_OK;
+    }
     HIPCHK(k, hipMemcpyAsync(m_out, k->K.m, sizeof(int32_t) * (size_t)k->n_dict, hipMemcpyDeviceToHost, k->stream));
     HIPCHK(k, hipStreamSynchronize(k->stream));
     return RS_OK;
@@ -994,12 +1031,13 @@ extern "C" int kb_get_pool(kb_handle* k, uint64_t* used_bytes, uint64_t* total_b
     HIPCHK(k, hipSetDevice(k->device));
     unsigned long long top = 0;
     std::vector<int32_t> e((size_t)k->cfg.n_envs);
-    HIPCHK(k, hipMemcpyAsync(&top, k->K.pool_top, sizeof top, hipMemcpyDeviceToHost, k->stream));
+    kb_handle* p = k->ref ? kb_ref_store(k) : k;  // (a by-reference handle: the pool is the store's, the distinct dictionaries once)
+    HIPCHK(k, hipMemcpyAsync(&top, p->K.pool_top, sizeof top, hipMemcpyDeviceToHost, k->stream));
     HIPCHK(k, hipMemcpyAsync(e.data(), k->K.err, sizeof(int32_t) * e.size(), hipMemcpyDeviceToHost, k->stream));
     HIPCHK(k, hipStreamSynchronize(k->stream));
-    if (top > k->D.pool_doubles) top = k->D.pool_doubles;
+    if (top > p->D.pool_doubles) top = p->D.pool_doubles;
     if (used_bytes) *used_bytes = (uint64_t)top * 8;
-    if (total_bytes) *total_bytes = (uint64_t)k->D.pool_doubles * 8;
+    if (total_bytes) *total_bytes = (uint64_t)p->D.pool_doubles * 8;
     int32_t ns = 0, nf = 0;
     for (int32_t v : e) {
         ns += (v & 8) ? 1 : 0;

@@ -297,6 +297,10 @@ static int kb_fork_check(kb_handle* dst_or_null, kb_handle* src, const int32_t* 
         *err = std::string(who) + ": shared-dictionary handles are not supported";
         return RS_EINVAL;
     }
+    if (src->ref || (dst_or_null && dst_or_null->ref)) {
+        *err = std::string(who) + ": a by-reference handle (kb_deploy_ref) holds its dictionaries in a shared read-only store: deploy from its source";
+        return RS_ESTATE;
+    }
     if (dst_or_null && kb_fork_cfg_hash(dst_or_null) != kb_fork_cfg_hash(src)) {
         *err = std::string(who) + ": the handles' configurations differ (beyond n_envs and pool_bytes)";
         return RS_EINVAL;

@@ -524,6 +524,7 @@ __device__ __forceinline__ double* page_of(const KbState& K, const uint64_t* sh,
 // chunks [b0, b1) of the dictionary, by ONE wave, into Wacc (LDS, 256 doubles, zeroed by the caller); the landmarks that take
 // the direct evaluation are listed from position `pos0` of dlist on.  Returns flags | (how many of them) << 8.
 // one chunk's landmarks: D0 / E (MODE 0: computed and left in the dictionary's rows), the direct-evaluation list, W[a] += coeff_j E_j
+// (kb_ref.hip: ref_bin_chunk is this routine without the stores into the page -- a change to the conditions or the listing goes there too)
 template <int MODE>
 __device__ __forceinline__ void bin_one_chunk(const KbDev& D, const ChunkRows<MODE>& R, double* P, int lane, int cnt, int d, const double* x,
                                               double* Wacc, double* dlist, int pos0, int& flags, int& ndir) {
@@ -662,9 +663,25 @@ __device__ __forceinline__ void chain_scores(const KbDev& D, const double* G2, c
 // (kernel.py:26-27), needs them, and then it needs them exactly.  The rule looks at the candidate's own binned sum only, so
 // it is the same in every kernel.
 #define KB_F_SETTLED 1e-240
-template <int NG>
+// |l_j[:d-1] - x|^2 of the landmark this lane holds, from the rows load_chunk brought (eMBB learners) or from the page: the sum
+// bin_one_chunk forms, for the callers that keep D0 to themselves (read-only dictionaries, kb_ref.hip)
+__device__ __forceinline__ double chunk_d0(const ChunkRows<2>& R, const double* P, int lane, int d, const double* x) {
+    if (d - 1 != 10) return dist0(P, lane, d, x);
+    double d0 = 0.0;
+#pragma unroll
+    for (int q = 0; q < 10; ++q) {
+        const double t = R.v[q] - x[q];
+        d0 += t * t;
+    }
+    return d0;
+}
+// RECOMPUTE: the dictionary's D0 / E rows do not belong to this state (a read-only dictionary many replicas score against at
+// once): beyond the list the rows are walked again and D0 / E formed anew from the coordinates (x; f32: their float32 copy), by the
+// operations that formed them the first time -- the same bits
+template <int NG, bool RECOMPUTE = false>
 __device__ __forceinline__ void add_direct_terms(const KbDev& D, const KbState& K, const uint64_t* sh, int m, int d, int c_base, int ng,
-                                                 int flags, const double* dlist, double (&f)[NG]) {
+                                                 int flags, const double* dlist, double (&f)[NG], const double* x = nullptr,
+                                                 bool f32 = false) {
     const int lane = threadIdx.x & 63;
     const int nch = (m + 63) >> 6;
     const bool off_grid = (flags & 2) != 0;
@@ -704,11 +721,20 @@ __device__ __forceinline__ void add_direct_terms(const KbDev& D, const KbState& 
         for (int b = 0; b < nch; ++b) {
             const double* P = vec_page(K, sh, b);
             const int cnt = m - 64 * b < 64 ? m - 64 * b : 64;
-            const double E = P[KB_ROW_E * KB_CH + lane];
+            double E, d0r = 0.0;
+            if (RECOMPUTE) {
+                ChunkRows<2> R;
+                load_chunk<2>(P, lane, d, R, f32);
+                d0r = chunk_d0(R, P, lane, d, x);
+                E = rs_exp_nonpos(-D.gamma * d0r);
+            } else {
+                E = P[KB_ROW_E * KB_CH + lane];
+            }
             const int a = ((const int32_t*)(P + KB_ROW_IDX * KB_CH))[lane];
             unsigned long long dm = __ballot(lane < cnt && (a < 0 || (!(E >= KB_E_TINY) && E > 0.0)));
             if (!dm) continue;
-            const double d0 = P[KB_ROW_D0 * KB_CH + lane], lam = P[(d - 1) * KB_CH + lane], co = P[KB_ROW_CO * KB_CH + lane];
+            const double d0 = RECOMPUTE ? d0r : P[KB_ROW_D0 * KB_CH + lane];
+            const double lam = P[(d - 1) * KB_CH + lane], co = P[KB_ROW_CO * KB_CH + lane];
             while (dm) {
                 const int jj = __builtin_ctzll(dm);
                 dm &= dm - 1ull;
@@ -2250,6 +2276,8 @@ struct GemmLds {
     int task[KB_SEL_WAVES], m[KB_SEL_WAVES];
 };
 
+// (kb_ref.hip restates this kernel's product loop and its scan of a learner's row -- toeplitz_product, select_commit -- for
+// select_ref_kernel: a change to either goes there too)
 __global__ __launch_bounds__(256) void select_gemm_kernel(SelArgs A) {
     const KbDev& D = A.D;
     const KbState& K = A.K;

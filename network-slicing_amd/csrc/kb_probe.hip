@@ -9,6 +9,8 @@
 //                      with fewer than two landmarks hold no W: select_bin_* leaves them alone)
 //   kb_dev_get_rows    the first min(m, max_m) entries of one learner's KB_ROW_D0 / KB_ROW_E / KB_ROW_IDX rows, its
 //                      coefficients and last coordinates, and the handle's G table (256 entries)
+// By-reference handles (kb_ref.hip) answer both: their scores are per task as everywhere (they keep no W: zeros), their rows are
+// those of the store's dictionary the map names for (e, s) -- which no selection may ever have changed.
 
 extern "C" int kb_dev_get_scores(kb_handle* k, double* F, double* W, int32_t* fdirect) {
     if (!k) return RS_EINVAL;
@@ -31,28 +33,34 @@ extern "C" int kb_dev_get_rows(kb_handle* k, int e, int s, int32_t max_m, int32_
     if (!k || e < 0 || e >= k->cfg.n_envs || s < 0 || s >= k->cfg.n_slices || max_m < 0) return RS_EINVAL;
     HIPCHK(k, hipSetDevice(k->device));
     HIPCHK(k, hipStreamSynchronize(k->stream));
-    const size_t dict = k->D.shared ? (size_t)s : (size_t)e * k->cfg.n_slices + s;
+    size_t dict = k->D.shared ? (size_t)s : (size_t)e * k->cfg.n_slices + s;
+    kb_handle* const q = k;
+    if (q->ref) {  // (from here on k is the handle whose pool holds the dictionary; errors are reported there and copied back)
+        dict = (size_t)kb_ref_dict(q, dict);
+        k = kb_ref_store(q);
+        HIPCHK(q, hipStreamSynchronize(k->stream));
+    }
     const int d = k->cfg.dims[s] + 1;
     int32_t m = 0;
-    HIPCHK(k, hipMemcpy(&m, k->K.m + dict, sizeof m, hipMemcpyDeviceToHost));
+    HIPCHK(q, hipMemcpy(&m, k->K.m + dict, sizeof m, hipMemcpyDeviceToHost));
     if (m_out) *m_out = m;
-    if (gtab) HIPCHK(k, hipMemcpy(gtab, k->K.gtab, sizeof(double) * 256, hipMemcpyDeviceToHost));
+    if (gtab) HIPCHK(q, hipMemcpy(gtab, k->K.gtab, sizeof(double) * 256, hipMemcpyDeviceToHost));
     const int take = m < max_m ? m : max_m;
     if (take <= 0) return RS_OK;
     const int nch = (take + KB_CH - 1) / KB_CH;
     if (nch > k->D.max_shells) {
-        k->err = "kb_dev_get_rows: more landmarks than the shell table holds";
+        q->err = "kb_dev_get_rows: more landmarks than the shell table holds";
         return RS_ESTATE;
     }
     std::vector<uint64_t> sh((size_t)nch);
-    HIPCHK(k, hipMemcpy(sh.data(), k->K.shell + dict * (size_t)k->D.max_shells, sizeof(uint64_t) * (size_t)nch, hipMemcpyDeviceToHost));
+    HIPCHK(q, hipMemcpy(sh.data(), k->K.shell + dict * (size_t)k->D.max_shells, sizeof(uint64_t) * (size_t)nch, hipMemcpyDeviceToHost));
     std::vector<double> page(KB_VEC);
     for (int b = 0; b < nch; ++b) {
         if (sh[b] == 0 || sh[b] + KB_VEC > k->D.pool_doubles) {  // (a shell the dictionary's size promises but the table lacks)
-            k->err = "kb_dev_get_rows: shell table entry out of the pool";
+            q->err = "kb_dev_get_rows: shell table entry out of the pool";
             return RS_ESTATE;
         }
-        HIPCHK(k, hipMemcpy(page.data(), k->K.pool + sh[b], sizeof(double) * KB_VEC, hipMemcpyDeviceToHost));
+        HIPCHK(q, hipMemcpy(page.data(), k->K.pool + sh[b], sizeof(double) * KB_VEC, hipMemcpyDeviceToHost));
         const int cnt = take - KB_CH * b < KB_CH ? take - KB_CH * b : KB_CH;
         const int32_t* ix = (const int32_t*)(page.data() + KB_ROW_IDX * KB_CH);
         for (int l = 0; l < cnt; ++l) {

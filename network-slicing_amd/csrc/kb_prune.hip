@@ -449,6 +449,10 @@ extern "C" int kb_prune(kb_handle* k, int32_t target, uint64_t* removed_total) {
         k->err = "kb_prune: shared-dictionary handles are not supported";
         return RS_ESTATE;
     }
+    if (k->ref) {
+        k->err = "kb_prune: a by-reference handle (kb_deploy_ref) shares read-only dictionaries: prune the learning handle and deploy again";
+        return RS_ESTATE;
+    }
     if (k->frozen) {
         k->err = "kb_prune: an inference-only handle (kb_deploy) holds no Kinv: prune the learning handle and deploy again";
         return RS_ESTATE;

@@ -83,11 +83,12 @@ def _fleet_run(agent, scenario, n_replicas, eval_steps, device, graph):
 
 def train_and_deploy(scenario, a_range, runs=range(RUNS), train_steps=TRAIN_STEPS, eval_replicas=EVAL_REPLICAS, eval_steps=EVAL_STEPS,
                      out_dir='./results', device=0, capacity=16384, pool_bytes=32 << 30, graph=GRAPH, verbose=True,
-                     learning_control=False):
+                     learning_control=False, by_reference=False):
     """one (scenario, accuracy range): writes the evaluation files and returns a summary with both pairs of numbers.
     learning_control: also run FULL forks of the same agents, learning left on, against the same fresh fleet -- what separates
     "the agent is frozen" from "the environment is new" in the difference between the two pairs (summary['learning_control'];
-    no files)."""
+    no files).  by_reference: the fleet shares each agent's dictionaries (VecKBRL.deploy(index, by_reference=True)): the pool is
+    the trained agents', not the replicas'; the results are the copy's bit for bit."""
     from ranslice.kbrl_dev import VecKBRL, fork_pool_bytes
     runs = list(runs)
     n, R = len(runs), int(eval_replicas)
@@ -105,7 +106,7 @@ def train_and_deploy(scenario, a_range, runs=range(RUNS), train_steps=TRAIN_STEP
     # freeze and fan out: replicas k * R .. k * R + R - 1 carry trained run k
     t1 = time.perf_counter()
     index = np.repeat(np.arange(n, dtype=np.int32), R)
-    deployed = agent.deploy(index)
+    deployed = agent.deploy(index, by_reference=by_reference)
     pool = deployed.pool()
     control = None
     if learning_control:
@@ -127,7 +128,7 @@ def train_and_deploy(scenario, a_range, runs=range(RUNS), train_steps=TRAIN_STEP
     summary = dict(scenario=scenario, accuracy_range=list(a_range), runs=n, train_steps=train_steps, eval_replicas=R,
                    eval_steps=eval_steps, window=window, train_wall_s=t_train, eval_wall_s=t_eval, deployed=dep, training_window=trained,
                    max_dictionary=int(sizes.max()), mean_dictionary=float(sizes.mean()), deployed_pool_bytes=int(pool['used_bytes']),
-                   path=path)
+                   by_reference=bool(by_reference), path=path)
     fmt = '{:.4f} +- {:.4f}'
     if verbose:
         print('scenario {} KBRL {}: {} agents trained {} steps ({:.1f} s), {} replicas each for {} steps in inference mode ({:.1f} s)'
@@ -158,7 +159,10 @@ if __name__ == '__main__':
     ap.add_argument('--out', default='./results')
     ap.add_argument('--learning-control', action='store_true',
                     help='also run full forks of the agents, learning left on, against the same fresh environments')
+    ap.add_argument('--by-reference', action='store_true',
+                    help="the replicas of an agent share one read-only copy of its dictionaries (kb_deploy_ref): same results, the agents' pool")
     args = ap.parse_args()
     for scenario, a_range in product(args.scenarios, accuracy_list):
         train_and_deploy(scenario, a_range, range(args.runs), train_steps=args.train_steps, eval_replicas=args.eval_replicas,
-                         eval_steps=args.eval_steps, out_dir=args.out, learning_control=args.learning_control)
+                         eval_steps=args.eval_steps, out_dir=args.out, learning_control=args.learning_control,
+                         by_reference=args.by_reference)

@@ -29,6 +29,13 @@ def deploy_pool_bytes(sizes):
     return POOL_PREAMBLE_BYTES + VEC_PAGE_BYTES * int(((m + 63) // 64).sum())
 
 
+def deploy_ref_pool_bytes(sizes, index):
+    """bytes kb_deploy_ref's handle reports as its pool: deploy_pool_bytes of the DISTINCT agents of `index` (sizes: the
+    source's [n_envs, S] dictionary sizes) -- every dictionary somebody references once, whatever the number of replicas"""
+    m = np.asarray(sizes, dtype=np.int64)
+    return deploy_pool_bytes(m[np.unique(np.asarray(index, dtype=np.int64))])
+
+
 def fork_pool_bytes(sizes):
     """bytes of pool a learning handle needs to take dictionaries of these sizes through fork_from: per shell b of a
     dictionary one vector page and b + 1 Kinv tiles of 32 KB with their 1 KB partial-sum areas, plus the preamble"""
@@ -38,6 +45,7 @@ def fork_pool_bytes(sizes):
 
 class VecKBRL:
     frozen = False   # True on the inference-only objects deploy() returns
+    by_reference = False   # True on those deploy(index, by_reference=True) returns: dictionaries stored once per distinct agent
 
     def __init__(self, n_envs, dims, n_prbs, alfa=KBRL_ALFA, accuracy_range=(0.99, 0.999), gamma=KBRL_GAMMA,
                  eta=KBRL_ETA, capacity=4096, device=0, shared=False, first_env=0, pool_bytes=0):
@@ -279,13 +287,18 @@ class VecKBRL:
             raise RuntimeError('the two agents were created from different builds of libranslice')
         self._check(self.L.kb_fork(self.h, src.h, index.ctypes.data_as(_ip)))
 
-    def deploy(self, index):
+    def deploy(self, index, by_reference=False):
         """-> an inference-only VecKBRL (frozen = True) of len(index) agents, agent j := agent index[j] of this one
         (kb_deploy): landmarks and coefficients only, in a pool of exactly deploy_pool_bytes(sizes[index]) bytes.  It selects
-        (select_action, step_resident, run_resident) and never learns."""
+        (select_action, step_resident, run_resident) and never learns.
+        by_reference=True (kb_deploy_ref): the replicas of an agent share ONE read-only copy of its dictionaries -- the pool is
+        deploy_ref_pool_bytes(sizes, index) bytes, the distinct agents once; control state and tie-break streams stay per
+        replica and every result equals the copy's bit for bit.  pool(), dictionary_sizes() and learner(e, s) answer per
+        replica; predict() and kernel_row() are refused (they would write into a shared page)."""
         index = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
         h = C.c_void_p()
-        self._check(self.L.kb_deploy(self.h, index.ctypes.data_as(_ip), int(index.size), C.byref(h)))
+        deploy = self.L.kb_deploy_ref if by_reference else self.L.kb_deploy
+        self._check(deploy(self.h, index.ctypes.data_as(_ip), int(index.size), C.byref(h)))
         d = object.__new__(type(self))
         d.L, d.h = self.L, h
         cfg = KbConfig.from_buffer_copy(self.cfg)
@@ -293,6 +306,7 @@ class VecKBRL:
         d.cfg = cfg
         d.n_envs, d.S, d.n_prbs, d.dims, d.nv, d.capacity = int(index.size), self.S, self.n_prbs, list(self.dims), self.nv, self.capacity
         d.frozen = True
+        d.by_reference = bool(by_reference)
         cfg.pool_bytes = d.pool()['total_bytes']
         return d
 

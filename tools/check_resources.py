@@ -14,6 +14,8 @@ KB_SCRATCH = {'update_small_kernel': 64, 'update_heavy_kernel': 16, 'update_cont
               'heavy_matvec_kernel': 0, 'heavy_rank1_kernel': 0, 'select_bin_kernel': 16, 'select_bin_big_kernel': 16, 'select_gemm_kernel': 0}
 # kb_prune's kernels (kb_prune.hip): reported, and held to no scratch at all -- the downdate is a pure streaming kernel
 PRUNE = ['prune_list_kernel', 'prune_choose_kernel', 'prune_plan_kernel', 'prune_downdate_kernel', 'prune_move_kernel', 'prune_finish_kernel']
+# kb_deploy_ref's kernels (kb_ref.hip): reported, and held to no scratch at all, as they are built and documented
+REF_SCRATCH = {'select_ref_kernel': 0, 'ref_gather_kernel': 0}
 PRODUCTION = ["embb_step_kernelILi16ELb0ELb0ELb1E", "embb_step_kernelILi16ELb0ELb1ELb1E"]   # <16, false, plain | BLOCK, FDIV>
 
 
@@ -63,6 +65,15 @@ def check(path=LOG):
                                                                            r.get('LDS Size')))
         if r.get('ScratchSize', 0) > 0:
             bad.append('%s spills %d B/lane (> 0)' % (key, r['ScratchSize']))
+    for key, limit in REF_SCRATCH.items():
+        hit = [k for k in res if key in k]
+        if not hit:
+            bad.append('%s: not found in %s' % (key, path))
+            continue
+        r = res[hit[0]]
+        print('%s: VGPRs %s, scratch %s B/lane, occupancy %s' % (key, r.get('VGPRs'), r.get('ScratchSize'), r.get('Occupancy')))
+        if r.get('ScratchSize', 0) > limit:
+            bad.append('%s spills %d B/lane (> %d)' % (key, r['ScratchSize'], limit))
     return bad
 
 

@@ -12,6 +12,12 @@
                                 [--out profiles/deploy_record.json]
 
 --fanout-only: train, fan out once with each call and exit (the run to put under `rocprofv3 --kernel-trace --stats`).
+
+--by-reference [--ref-sizes 4096 65536]: the fan-out by reference (kb_deploy_ref) against the copy (kb_deploy), the same trained
+agents in the same process, and nothing else; writes profiles/deploy_ref_record.json.  Per size and per kind: the bytes of the
+pool, the device memory the handle took (free memory before and after the call), closed-loop inference ms per step (hipGraph)
+and the select phase's ms (kb_phase_times_ms, plain launches) -- over --ref-repeats rounds in which the two kinds alternate in
+going first, every round's figure with min / median / max.  With one size and one round it is the run to put under rocprofv3.
 """
 import argparse
 import json
@@ -56,6 +62,69 @@ def timed(call, sync):
     return out, time.perf_counter() - t0
 
 
+def by_reference_leg(agent, scenario, sizes_n, steps, repeats=3):
+    """copy against by-reference at every size of `sizes_n`: `repeats` rounds, each round both kinds on a fresh deployment and a
+    fresh fleet, the kind that goes first alternating from round to round.  Per kind the record keeps every round's closed-loop
+    ms per step and select-phase ms with their min, median and max; the ratios are formed from the medians.
+    -> {size: {copy: ..., by_reference: ..., by_reference_over_copy: ...}}"""
+    from ranslice import _lib
+    from ranslice.kbrl_dev import deploy_pool_bytes, deploy_ref_pool_bytes
+    n = agent.n_envs
+    sizes = agent.dictionary_sizes()
+
+    def spread(v):
+        return dict(runs=[float(x) for x in v], min=float(min(v)), median=float(np.median(v)), max=float(max(v)))
+    out = {}
+    for N in sizes_n:
+        index = (np.arange(N) % n).astype(np.int32)
+        runs = {'copy': [], 'by_reference': []}
+        failed = {}
+        for rep in range(repeats):
+            for kind in (('copy', 'by_reference') if rep % 2 == 0 else ('by_reference', 'copy')):
+                try:
+                    agent.synchronize()
+                    free0, _ = _lib.device_mem_info(0)
+                    dep, t_dep = timed(lambda: agent.deploy(index, by_reference=kind == 'by_reference'), lambda d: d.synchronize())
+                    free1, _ = _lib.device_mem_info(0)
+                    pool = dep.pool()
+                    want = deploy_ref_pool_bytes(sizes, index) if kind == 'by_reference' else deploy_pool_bytes(sizes[index])
+                    assert pool['used_bytes'] == pool['total_bytes'] == want, (kind, pool, want)
+                    env = fresh_env(scenario, N, dep.control(with_accuracies=False)['action'])
+                    r = rate(dep, env, steps)
+                    dep.set_kernel_timing(True)       # (timed launches go one by one: the graph is not used)
+                    dep.run_resident(env, 10, graph=False)
+                    dep.synchronize()
+                    dep.phase_times_ms()
+                    dep.run_resident(env, 40, graph=False)
+                    dep.synchronize()
+                    ph = dep.phase_times_ms()
+                    dep.set_kernel_timing(False)
+                    runs[kind].append(dict(pool_bytes=pool['used_bytes'], device_memory_taken_bytes=int(free0 - free1),
+                                           deploy_wall_ms=1e3 * t_dep, ms_per_step=r['ms_per_step'], select_phase_ms=ph['select_ms'],
+                                           select_phases_timed=int(ph['n_select'])))
+                    env.close()
+                    dep.close()
+                except Exception as e:      # recorded, not hidden
+                    failed[kind] = repr(e)
+        leg = {}
+        for kind, rs in runs.items():
+            if kind in failed or not rs:
+                leg[kind] = dict(failed=failed.get(kind, 'no run'))
+                continue
+            leg[kind] = dict(pool_bytes=rs[0]['pool_bytes'], steps=steps, select_phases_timed=rs[0]['select_phases_timed'],
+                             device_memory_taken_bytes=spread([x['device_memory_taken_bytes'] for x in rs]),
+                             deploy_wall_ms=spread([x['deploy_wall_ms'] for x in rs]),
+                             ms_per_step=spread([x['ms_per_step'] for x in rs]),
+                             select_phase_ms=spread([x['select_phase_ms'] for x in rs]))
+        if all('failed' not in v for v in leg.values()):
+            leg['by_reference_over_copy'] = dict(
+                pool_bytes=leg['by_reference']['pool_bytes'] / leg['copy']['pool_bytes'],
+                **{k: leg['by_reference'][k]['median'] / leg['copy'][k]['median']
+                   for k in ('device_memory_taken_bytes', 'ms_per_step', 'select_phase_ms')})
+        out[str(N)] = dict(leg, order='copy first in rounds 0, 2, ..; by reference first in rounds 1, 3, ..', rounds=repeats)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--scenario', type=int, default=0)
@@ -67,8 +136,14 @@ def main():
     ap.add_argument('--fanout-only', action='store_true')
     ap.add_argument('--experiment', type=int, nargs=3, metavar=('TRAIN_STEPS', 'EVAL_REPLICAS', 'EVAL_STEPS'), default=None,
                     help='also run experiments_trained.train_and_deploy for the scenario and record its numbers (e.g. 40000 64 9500)')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'deploy_record.json'))
+    ap.add_argument('--by-reference', action='store_true',
+                    help='measure kb_deploy_ref against kb_deploy only, and write profiles/deploy_ref_record.json')
+    ap.add_argument('--ref-sizes', type=int, nargs='+', default=[4096, 65536])
+    ap.add_argument('--ref-repeats', type=int, default=3, help='rounds of the --by-reference leg (the two kinds alternate in going first)')
+    ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, 'profiles', 'deploy_ref_record.json' if args.by_reference else 'deploy_record.json')
     import scenario_creator as sc
     from experiments_kbrl import BatchedEvaluator
     from ranslice.kbrl_dev import VecKBRL, deploy_pool_bytes, fork_pool_bytes
@@ -80,6 +155,15 @@ def main():
     rec = dict(scenario=args.scenario, agents=n, train_steps=args.train_steps, train_wall_s=time.perf_counter() - t0, replicas=N)
     sizes = agent.dictionary_sizes()
     rec['dictionary'] = dict(max=int(sizes.max()), mean=float(sizes.mean()))
+    if args.by_reference:
+        del rec['replicas']
+        rec['sizes'] = by_reference_leg(agent, args.scenario, args.ref_sizes, args.steps, args.ref_repeats)
+        ev.release()
+        with open(args.out, 'w') as f:
+            json.dump(rec, f, indent=1, sort_keys=True)
+            f.write('\n')
+        print(json.dumps(rec, sort_keys=True))
+        return
     index = (np.arange(N) % n).astype(np.int32)
     need = fork_pool_bytes(sizes[index])
     full = VecKBRL(N, agent.dims, agent.n_prbs, alfa=sc.alfa, accuracy_range=(0.99, 0.999), capacity=agent.capacity,
