@@ -493,6 +493,51 @@ int kb_deploy(kb_handle* src, const int32_t* src_index, int32_t n, kb_handle** o
  * kb_deploy, kb_deploy_ref and kb_fork with the by-reference handle as source.  RS_EINVAL: a shared-dictionary src, an index
  * out of range, n <= 0.  Ordered as kb_deploy: after src's queued work, and src's later work after the gather. */
 int kb_deploy_ref(kb_handle* src, const int32_t* src_index, int32_t n, kb_handle** out);
+/* ---- agent files: trained agents leave the process in the form they are deployed in, and come back as inference-only handles.
+ *
+ * The file ("KBAGENT1", little-endian, every array 8-byte aligned; DESIGN.md §8e, ranslice/agent_file.py reads and writes the
+ * same bytes on the host): a 120-byte header (magic, total bytes, FNV-1a of everything behind the hash field, agents n, and
+ * n_slices, n_prbs, capacity, dims[8], alfa, acc_lo, acc_hi, gamma, eta of kb_config, then the doubles of all dictionaries
+ * together); dense agent-major tables of what kb_fork copies per agent (sizes m[n][S], the float32 marks, action, security
+ * factors, margins, adjusted, accuracies, seeds, tie-break counters, the observation the resident loop chose its last action
+ * in, the flag word verbatim); then per dictionary, in (agent, slice) order, landmarks[m][dims[s] + 1] as f64 landmark-major
+ * (the shape kb_get_learner returns) and coeff[m].  Slot j of the file is slot j of the dictionary.  No Kinv, no shell
+ * offsets, no padding: landmarks, coefficients and control state -- what scoring reads.
+ *
+ * kb_export_bytes / kb_export_agents: agent j of the file := agent src_index[j] of src (repeats and permutations allowed).
+ * Arguments and checks are kb_deploy's; src is a learning handle or a copy-deployed inference-only one.  The blob must be
+ * exactly *bytes of kb_export_bytes long.  The file is a function of the arguments and the agents' state alone: two exports
+ * give identical bytes, and so does the export of a handle imported from the file.  Nothing in src is written.  Ordered on
+ * src's stream, after its queued work; the host waits once for the sizes in kb_export_bytes, and in kb_export_agents for the
+ * scan's totals and for the copy.  RS_ESTATE: a by-reference handle (export from its source instead), src not reset.
+ * RS_EINVAL: a shared-dictionary handle, an index out of range, n <= 0, `bytes` other than kb_export_bytes' (blob untouched).
+ *
+ * kb_agents_info: host only, no device call; the one function that parses untrusted bytes.  Validates a blob and returns the
+ * configuration kb_import_agents would create (n_envs = the file's agents, pool_bytes = 512 + 15,360 x the started 64
+ * landmarks of its dictionaries, shared_dictionary = 0) and, where m != NULL, the dictionary sizes [agents][S].  Checked, in
+ * this order and each before anything behind it is read: the magic, the length against the header's, kb_create's limits
+ * (<= 8 learners, n_prbs <= 255, 2 <= capacity <= 65536, dims <= 15), finite alfa, gamma, eta and accuracy range, the size the
+ * header's own fields imply against `bytes`, the hash, 0 <= m <= capacity with the sizes adding up to the header's total, and
+ * 0 <= action <= n_prbs.  RS_EINVAL otherwise; with no handle to hold the reason it is left in a per-thread string that
+ * kb_last_error(NULL) returns (also after a failed kb_import_agents).
+ *
+ * kb_import_agents: runs kb_agents_info, then creates an inference-only handle on `device` that holds the file's agents in
+ * file order, in a pool of exactly the pool_bytes above: an ordinary kb_deploy handle -- what works and what is refused is
+ * that list, and kb_deploy / kb_deploy_ref fan it out.  Pages are written whole: coordinates, their float32 copy (dims == 10),
+ * coefficients, the grid index of the last coordinate as an insertion computes it, zeros everywhere else and in every lane
+ * from m on; the newest-landmark heads, the chain links and the off-grid counts are rebuilt; the float32 mark is recomputed
+ * from the values and ORed with the file's.  Restarted as after kb_reset / kb_fork: statistics, stored select scores, the
+ * cache of the last kb_predict, versions, retained hits -- no result depends on them, so every score, action, margin, tie
+ * draw and counter is bit for bit that of kb_deploy(src, src_index) of the exported agents.  A coordinate or coefficient
+ * that is not finite: RS_EINVAL.  On any failure *out stays NULL and nothing stays allocated. */
+int kb_export_bytes(kb_handle* src, const int32_t* src_index, int32_t n, uint64_t* bytes);
+int kb_export_agents(kb_handle* src, const int32_t* src_index, int32_t n, void* blob, uint64_t bytes);
+int kb_agents_info(const void* blob, uint64_t bytes, kb_config* cfg, int32_t* m /* [agents][S], may be NULL */);
+int kb_import_agents(const void* blob, uint64_t bytes, int device, kb_handle** out);
+/* Device time (HIP events around the one launch) of the transposing kernel of this thread's last kb_export_agents (ms[0],
+ * the pack) and kb_import_agents (ms[1], the build), and the bytes its work plan counts, read plus written: the pack reads
+ * dims + 2 whole rows of every vector page and writes the file's dictionaries; the build reads those and writes whole pages. */
+int kb_agents_kernel_times(double ms[2], uint64_t bytes[2]);
 /* on = 0: the resident loop (kb_step_resident, each step of kb_run_resident) runs select_action(new obs) only -- the
  * reference's loop body past learning_time (kbrl_control.py:131-133): dictionaries, accuracies and security factors stay as
  * they are; margins, adjusted, action and the tie-break counters move as select_action moves them; a history column is still

@@ -464,7 +464,10 @@ extern "C" void kb_destroy(kb_handle* k) {
     delete k;
 }
 
-extern "C" const char* kb_last_error(const kb_handle* k) { return k ? k->err.c_str() : "null handle"; }
+// a call that has no handle to leave its reason in (kb_agents_info, a failed kb_import_agents: kb_agents.hip) leaves it here, per
+// thread: kb_last_error(NULL)
+static thread_local std::string kb_nohandle_err = "null handle";
+extern "C" const char* kb_last_error(const kb_handle* k) { return k ? k->err.c_str() : kb_nohandle_err.c_str(); }
 
 extern "C" int kb_reset(kb_handle* k, const int32_t* initial_action, const int32_t* security_factor,
                         const uint64_t* seeds) {

@@ -9,6 +9,8 @@
 //                      with fewer than two landmarks hold no W: select_bin_* leaves them alone)
 //   kb_dev_get_rows    the first min(m, max_m) entries of one learner's KB_ROW_D0 / KB_ROW_E / KB_ROW_IDX rows, its
 //                      coefficients and last coordinates, and the handle's G table (256 entries)
+//   kb_dev_get_chains  the newest-landmark heads (KB_HEAD entries), the first min(m, max_m) chain links of KB_ROW_IDX and the
+//                      off-grid count of one learner's dictionary: what agents_finish_kernel (kb_agents.hip) rebuilds
 // By-reference handles (kb_ref.hip) answer both: their scores are per task as everywhere (they keep no W: zeros), their rows are
 // those of the store's dictionary the map names for (e, s) -- which no selection may ever have changed.
 
@@ -71,6 +73,41 @@ extern "C" int kb_dev_get_rows(kb_handle* k, int e, int s, int32_t max_m, int32_
             if (coeff) coeff[j] = page[KB_ROW_CO * KB_CH + l];
             if (lam) lam[j] = page[(d - 1) * KB_CH + l];
         }
+    }
+    return RS_OK;
+}
+
+extern "C" int kb_dev_get_chains(kb_handle* k, int e, int s, int32_t max_m, int32_t* m_out, int32_t* head, int32_t* link, int32_t* offgrid) {
+    if (!k || e < 0 || e >= k->cfg.n_envs || s < 0 || s >= k->cfg.n_slices || max_m < 0) return RS_EINVAL;
+    if (k->ref || k->D.shared) {
+        k->err = "kb_dev_get_chains: a handle that owns one dictionary per learner only";
+        return RS_ESTATE;
+    }
+    HIPCHK(k, hipSetDevice(k->device));
+    HIPCHK(k, hipStreamSynchronize(k->stream));
+    const size_t dict = (size_t)e * k->cfg.n_slices + s;
+    int32_t m = 0;
+    HIPCHK(k, hipMemcpy(&m, k->K.m + dict, sizeof m, hipMemcpyDeviceToHost));
+    if (m_out) *m_out = m;
+    if (head) HIPCHK(k, hipMemcpy(head, k->K.head + dict * KB_HEAD, sizeof(int32_t) * KB_HEAD, hipMemcpyDeviceToHost));
+    if (offgrid) HIPCHK(k, hipMemcpy(offgrid, k->K.offgrid + dict, sizeof(int32_t), hipMemcpyDeviceToHost));
+    const int take = m < max_m ? m : max_m;
+    if (take <= 0 || !link) return RS_OK;
+    const int nch = (take + KB_CH - 1) / KB_CH;
+    if (nch > k->D.max_shells) {
+        k->err = "kb_dev_get_chains: more landmarks than the shell table holds";
+        return RS_ESTATE;
+    }
+    std::vector<uint64_t> sh((size_t)nch);
+    HIPCHK(k, hipMemcpy(sh.data(), k->K.shell + dict * (size_t)k->D.max_shells, sizeof(uint64_t) * (size_t)nch, hipMemcpyDeviceToHost));
+    for (int b = 0; b < nch; ++b) {
+        if (sh[b] == 0 || sh[b] + KB_VEC > k->D.pool_doubles) {
+            k->err = "kb_dev_get_chains: shell table entry out of the pool";
+            return RS_ESTATE;
+        }
+        const int cnt = take - KB_CH * b < KB_CH ? take - KB_CH * b : KB_CH;
+        HIPCHK(k, hipMemcpy(link + KB_CH * b, (const int32_t*)(k->K.pool + sh[b] + KB_ROW_IDX * KB_CH) + 64, sizeof(int32_t) * (size_t)cnt,
+                            hipMemcpyDeviceToHost));
     }
     return RS_OK;
 }

@@ -15,7 +15,11 @@ For each (scenario, accuracy range):
      own last window -- the reference's method: one trajectory per agent, the agent still learning in the window.
 
   python experiments_trained.py [--scenarios 0] [--runs 30] [--train-steps 40000] [--eval-replicas 64] [--eval-steps 9500]
-                                [--learning-control]
+                                [--learning-control] [--save-agents DIR | --load-agents DIR]
+
+--save-agents DIR writes the trained agents of every cell to DIR/scenario_N_KBRL_xx.kbagent (an agent file: landmarks,
+coefficients and control state, ranslice.agent_file) right after training; --load-agents DIR skips step 1 and evaluates the
+fleet from that file -- in another process, on another day -- with the evaluation arrays of steps 2-4 equal number for number.
 """
 import argparse
 import os
@@ -81,18 +85,68 @@ def _fleet_run(agent, scenario, n_replicas, eval_steps, device, graph):
     return h
 
 
+def agents_path(directory, scenario, a_range):
+    """the agent file of one (scenario, accuracy range) under --save-agents / --load-agents"""
+    return os.path.join(directory, 'scenario_{}_{}_{}.kbagent'.format(scenario, name, int(a_range[0] * 100)))
+
+
+def _write_evaluation(h, scenario, a_range, runs, R, eval_steps, out_dir):
+    """the fleet's histories -> one evaluation_K.npz per trained run; -> (path, violation, resources [n, R, steps], statistics)"""
+    path = '{}/scenario_{}/{}_{}_deployed/'.format(out_dir, scenario, name, int(a_range[0] * 100))
+    os.makedirs(path, exist_ok=True)
+    shape = (len(runs), R, eval_steps)
+    viol, res, rew = h['violation'].reshape(shape), h['resources'].reshape(shape), h['reward'].reshape(shape)
+    for k, i in enumerate(runs):
+        np.savez('{}evaluation_{}.npz'.format(path, i), violation=viol[k], resources=res[k], reward=rew[k])
+    return path, viol, res, window_statistics(viol, res, sc.scenarios[scenario]['n_prbs'])
+
+
+def _evaluate_loaded(scenario, a_range, runs, R, eval_steps, out_dir, device, graph, verbose, by_reference, directory):
+    """steps 2-4 of a cell whose agents come from their file: agent k of the file is trained run runs[k]"""
+    from ranslice import agent_file
+    from ranslice.kbrl_dev import VecKBRL
+    n = len(runs)
+    t1 = time.perf_counter()
+    with open(agents_path(directory, scenario, a_range), 'rb') as f:
+        blob = f.read()
+    sizes = agent_file.info(blob)['m']
+    if sizes.shape[0] != n:
+        raise ValueError('{} holds {} agents, the cell has {} runs'.format(agents_path(directory, scenario, a_range), sizes.shape[0], n))
+    deployed = VecKBRL.load_agents(blob, np.repeat(np.arange(n, dtype=np.int32), R), by_reference=by_reference, device=device)
+    pool = deployed.pool()
+    h = _fleet_run(deployed, scenario, n * R, eval_steps, device, graph)
+    t_eval = time.perf_counter() - t1
+    deployed.close()
+    path, viol, res, dep = _write_evaluation(h, scenario, a_range, runs, R, eval_steps, out_dir)
+    if verbose:
+        fmt = '{:.4f} +- {:.4f}'
+        print('scenario {} KBRL {}: {} agents loaded from their file, {} replicas each for {} steps in inference mode ({:.1f} s)'
+              .format(scenario, a_range[0], n, R, eval_steps, t_eval))
+        print('  deployed (frozen, {} unseen traffic realisations per agent): violations per stage {}, resource occupation {}'
+              .format(R, fmt.format(*dep['violations']), fmt.format(*dep['occupation'])))
+    return dict(scenario=scenario, accuracy_range=list(a_range), runs=n, train_steps=None, eval_replicas=R, eval_steps=eval_steps,
+                window=None, train_wall_s=0.0, eval_wall_s=t_eval, deployed=dep, training_window=None, max_dictionary=int(sizes.max()),
+                mean_dictionary=float(sizes.mean()), deployed_pool_bytes=int(pool['used_bytes']), by_reference=bool(by_reference),
+                path=path, loaded=True)
+
+
 def train_and_deploy(scenario, a_range, runs=range(RUNS), train_steps=TRAIN_STEPS, eval_replicas=EVAL_REPLICAS, eval_steps=EVAL_STEPS,
                      out_dir='./results', device=0, capacity=16384, pool_bytes=32 << 30, graph=GRAPH, verbose=True,
-                     learning_control=False, by_reference=False):
+                     learning_control=False, by_reference=False, save_agents=None, load_agents=None):
     """one (scenario, accuracy range): writes the evaluation files and returns a summary with both pairs of numbers.
     learning_control: also run FULL forks of the same agents, learning left on, against the same fresh fleet -- what separates
     "the agent is frozen" from "the environment is new" in the difference between the two pairs (summary['learning_control'];
     no files).  by_reference: the fleet shares each agent's dictionaries (VecKBRL.deploy(index, by_reference=True)): the pool is
-    the trained agents', not the replicas'; the results are the copy's bit for bit."""
+    the trained agents', not the replicas'; the results are the copy's bit for bit.
+    save_agents / load_agents: a directory; the cell's agent file (agents_path) is written after training, or read INSTEAD of
+    training -- the evaluation arrays are the same either way (summary['training_window'] is None for a loaded cell, and
+    learning_control needs the training handle)."""
     from ranslice.kbrl_dev import VecKBRL, fork_pool_bytes
     runs = list(runs)
     n, R = len(runs), int(eval_replicas)
     n_prbs = sc.scenarios[scenario]['n_prbs']
+    if load_agents is not None:
+        return _evaluate_loaded(scenario, a_range, runs, R, eval_steps, out_dir, device, graph, verbose, by_reference, load_agents)
     t0 = time.perf_counter()
     ev = BatchedEvaluator(scenario, a_range, steps=train_steps, out_dir=out_dir)
     agent, env = ev.train(runs, device=device, capacity=capacity, pool_bytes=pool_bytes, graph=graph)
@@ -103,6 +157,10 @@ def train_and_deploy(scenario, a_range, runs=range(RUNS), train_steps=TRAIN_STEP
     trained = window_statistics(hist['violation'], hist['resources'], n_prbs, start=train_steps - window)
     sizes = agent.dictionary_sizes()
     t_train = time.perf_counter() - t0
+    if save_agents is not None:
+        os.makedirs(save_agents, exist_ok=True)
+        with open(agents_path(save_agents, scenario, a_range), 'wb') as f:
+            f.write(agent.export_agents(np.arange(n, dtype=np.int32)))
     # freeze and fan out: replicas k * R .. k * R + R - 1 carry trained run k
     t1 = time.perf_counter()
     index = np.repeat(np.arange(n, dtype=np.int32), R)
@@ -118,13 +176,8 @@ def train_and_deploy(scenario, a_range, runs=range(RUNS), train_steps=TRAIN_STEP
     h = _fleet_run(deployed, scenario, n * R, eval_steps, device, graph)
     t_eval = time.perf_counter() - t1
     deployed.close()
-    path = '{}/scenario_{}/{}_{}_deployed/'.format(out_dir, scenario, name, int(a_range[0] * 100))
-    os.makedirs(path, exist_ok=True)
+    path, viol, res, dep = _write_evaluation(h, scenario, a_range, runs, R, eval_steps, out_dir)
     shape = (n, R, eval_steps)
-    viol, res, rew = h['violation'].reshape(shape), h['resources'].reshape(shape), h['reward'].reshape(shape)
-    for k, i in enumerate(runs):
-        np.savez('{}evaluation_{}.npz'.format(path, i), violation=viol[k], resources=res[k], reward=rew[k])
-    dep = window_statistics(viol, res, n_prbs)
     summary = dict(scenario=scenario, accuracy_range=list(a_range), runs=n, train_steps=train_steps, eval_replicas=R,
                    eval_steps=eval_steps, window=window, train_wall_s=t_train, eval_wall_s=t_eval, deployed=dep, training_window=trained,
                    max_dictionary=int(sizes.max()), mean_dictionary=float(sizes.mean()), deployed_pool_bytes=int(pool['used_bytes']),
@@ -161,8 +214,12 @@ if __name__ == '__main__':
                     help='also run full forks of the agents, learning left on, against the same fresh environments')
     ap.add_argument('--by-reference', action='store_true',
                     help="the replicas of an agent share one read-only copy of its dictionaries (kb_deploy_ref): same results, the agents' pool")
+    ap.add_argument('--save-agents', metavar='DIR', help='write the trained agents of every cell to DIR (one agent file per cell)')
+    ap.add_argument('--load-agents', metavar='DIR', help='skip training: evaluate the agents --save-agents wrote to DIR')
     args = ap.parse_args()
+    if args.load_agents and (args.save_agents or args.learning_control):
+        ap.error('--load-agents evaluates agents from their files: it neither trains (--learning-control) nor saves')
     for scenario, a_range in product(args.scenarios, accuracy_list):
         train_and_deploy(scenario, a_range, range(args.runs), train_steps=args.train_steps, eval_replicas=args.eval_replicas,
                          eval_steps=args.eval_steps, out_dir=args.out, learning_control=args.learning_control,
-                         by_reference=args.by_reference)
+                         by_reference=args.by_reference, save_agents=args.save_agents, load_agents=args.load_agents)

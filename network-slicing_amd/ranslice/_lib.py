@@ -21,6 +21,7 @@ KB_EXPORTS = (
     'kb_fork', 'kb_deploy', 'kb_set_learning',
     'kb_prune', 'kb_get_pruned', 'kb_prune_time_ms', 'kb_get_prune_work',
     'kb_deploy_ref',
+    'kb_export_bytes', 'kb_export_agents', 'kb_agents_info', 'kb_import_agents', 'kb_agents_kernel_times',
 )
 
 EXPORTS = (
@@ -189,6 +190,11 @@ def load(dev=None):
     L.kb_deploy.argtypes = [vp, ip, C.c_int32, C.POINTER(vp)]
     L.kb_deploy_ref.argtypes = [vp, ip, C.c_int32, C.POINTER(vp)]
     L.kb_set_learning.argtypes = [vp, C.c_int]
+    L.kb_export_bytes.argtypes = [vp, ip, C.c_int32, up]
+    L.kb_export_agents.argtypes = [vp, ip, C.c_int32, vp, C.c_uint64]
+    L.kb_agents_info.argtypes = [vp, C.c_uint64, C.POINTER(KbConfig), ip]
+    L.kb_import_agents.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(vp)]
+    L.kb_agents_kernel_times.argtypes = [dp, up]
     L.kb_prune.argtypes = [vp, C.c_int32, up]
     L.kb_get_pruned.argtypes = [vp, i64p]
     L.kb_prune_time_ms.argtypes = [vp, dp, i64p]

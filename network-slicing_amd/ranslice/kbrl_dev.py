@@ -310,6 +310,45 @@ class VecKBRL:
         cfg.pool_bytes = d.pool()['total_bytes']
         return d
 
+    # ---- agent files --------------------------------------------------------------------------
+    def export_agents(self, index):
+        """-> the agent file (bytes, ranslice.agent_file) of agents index[0], index[1], ... of this handle (kb_export_agents):
+        landmarks, coefficients and control state, no Kinv -- what load_agents turns back into deployed agents, in this process
+        or another.  A learning handle or a copy-deployed one; repeats and permutations allowed; the handle is not changed."""
+        index = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        n = C.c_uint64()
+        self._check(self.L.kb_export_bytes(self.h, index.ctypes.data_as(_ip), int(index.size), C.byref(n)))
+        blob = np.empty(n.value, dtype=np.uint8)
+        self._check(self.L.kb_export_agents(self.h, index.ctypes.data_as(_ip), int(index.size), blob.ctypes.data_as(C.c_void_p), n.value))
+        return blob.tobytes()
+
+    @classmethod
+    def load_agents(cls, blob, index=None, by_reference=False, device=0):
+        """-> an inference-only VecKBRL (frozen = True) holding the agents of an agent file in file order (kb_import_agents):
+        bit for bit the handle deploy() would have made of the exported agents.  index: fan out instead -- replica j := agent
+        index[j] of the file, through deploy(index, by_reference); the intermediate handle is released."""
+        L = _lib.load()
+        raw = np.frombuffer(bytes(blob), dtype=np.uint8)
+        cfg = KbConfig()
+        if L.kb_agents_info(raw.ctypes.data_as(C.c_void_p) if raw.size else None, raw.size, C.byref(cfg), None) != 0:
+            raise _lib.RanSliceError(_lib.RS_EINVAL, L.kb_last_error(None).decode())
+        h = C.c_void_p()
+        rc = L.kb_import_agents(raw.ctypes.data_as(C.c_void_p), raw.size, int(device), C.byref(h))
+        if rc != 0:
+            raise _lib.RanSliceError(rc, L.kb_last_error(None).decode())
+        d = object.__new__(cls)
+        d.L, d.h, d.cfg = L, h, cfg
+        d.n_envs, d.S, d.n_prbs, d.capacity = int(cfg.n_envs), int(cfg.n_slices), int(cfg.n_prbs), int(cfg.capacity)
+        d.dims = [int(cfg.dims[s]) for s in range(d.S)]
+        d.nv = int(sum(d.dims))
+        d.frozen = True
+        if index is None:
+            return d
+        try:
+            return d.deploy(index, by_reference=by_reference)
+        finally:
+            d.close()
+
     def set_learning(self, on):
         """on=False: step_resident / run_resident select only (KBRL_Control.run past learning_time); True resumes learning"""
         self._check(self.L.kb_set_learning(self.h, int(bool(on))))

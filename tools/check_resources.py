@@ -16,6 +16,8 @@ KB_SCRATCH = {'update_small_kernel': 64, 'update_heavy_kernel': 16, 'update_cont
 PRUNE = ['prune_list_kernel', 'prune_choose_kernel', 'prune_plan_kernel', 'prune_downdate_kernel', 'prune_move_kernel', 'prune_finish_kernel']
 # kb_deploy_ref's kernels (kb_ref.hip): reported, and held to no scratch at all, as they are built and documented
 REF_SCRATCH = {'select_ref_kernel': 0, 'ref_gather_kernel': 0}
+# the agent-file kernels (kb_agents.hip): reported, and held to no scratch at all -- pack and build are pure streaming kernels
+AGENTS = ['agents_count_kernel', 'agents_tables_kernel', 'agents_pack_kernel', 'agents_build_kernel', 'agents_finish_kernel']
 PRODUCTION = ["embb_step_kernelILi16ELb0ELb0ELb1E", "embb_step_kernelILi16ELb0ELb1ELb1E"]   # <16, false, plain | BLOCK, FDIV>
 
 
@@ -56,6 +58,16 @@ def check(path=LOG):
         elif res[hit[0]].get('ScratchSize', 0) > limit:
             bad.append('%s spills %d B/lane (> %d)' % (key, res[hit[0]]['ScratchSize'], limit))
     for key in PRUNE:
+        hit = [k for k in res if key in k]
+        if not hit:
+            bad.append('%s: not found in %s' % (key, path))
+            continue
+        r = res[hit[0]]
+        print('%s: VGPRs %s, scratch %s B/lane, occupancy %s, LDS %s B' % (key, r.get('VGPRs'), r.get('ScratchSize'), r.get('Occupancy'),
+                                                                           r.get('LDS Size')))
+        if r.get('ScratchSize', 0) > 0:
+            bad.append('%s spills %d B/lane (> 0)' % (key, r['ScratchSize']))
+    for key in AGENTS:
         hit = [k for k in res if key in k]
         if not hit:
             bad.append('%s: not found in %s' % (key, path))
