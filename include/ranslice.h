@@ -538,6 +538,39 @@ int kb_import_agents(const void* blob, uint64_t bytes, int device, kb_handle** o
  * the pack) and kb_import_agents (ms[1], the build), and the bytes its work plan counts, read plus written: the pack reads
  * dims + 2 whole rows of every vector page and writes the file's dictionaries; the build reads those and writes whole pages. */
 int kb_agents_kernel_times(double ms[2], uint64_t bytes[2]);
+/* ---- resuming learning on agents that hold no Kinv (a kb_deploy handle, a kb_import_agents handle).
+ *
+ * kb_fork_rebuild: kb_fork for such sources -- agent j of dst := agent src_index[j] of src, and dst's Kinv is REBUILT on the
+ * device.  dst: a learning handle (kb_create), same kb_config as src except n_envs and pool_bytes, same device.  src: a
+ * copy-deployed inference-only handle, an imported one, or a learning handle (whose Kinv is then ignored).  Travels, as with
+ * kb_fork: the vector pages (coordinates, their float32 copy, coefficients, grid index and chain links), sizes, heads, the
+ * off-grid / float32 marks, versions, the control state, the tie-break stream, the observation the resident loop chose its last
+ * action in, and the flag word verbatim.  Restarts: everything kb_fork restarts, and the cache of the last kb_predict (the
+ * replay uses its rows: kb_update answers RS_ESTATE until a new kb_predict).  Layout: kb_fork's (full shells at an exclusive
+ * scan of their sizes); Kinv tiles and their partial-sum areas are zeroed, then filled by replaying the insertions in slot
+ * order -- step j inserts landmark j into the dictionary of landmarks 0 .. j - 1 with the arithmetic of Projectron.update's
+ * insertion branch, statement for statement (the float32 roundings of the first pair included); coefficients, versions,
+ * flags and chains are the copied ones and are not written.  Over landmarks that were never reordered (no kb_prune, not packed
+ * on the host in another order) the result is the source's Kinv BIT FOR BIT, and continuing dst agent j gives, bit for bit,
+ * what continuing the learning handle the agent came from would.  Over any other slot order the same recurrence yields the
+ * landmarks' inverse Gram matrix to rounding.  Ordered as kb_fork, by events on both streams; never captured into a graph;
+ * the host waits for the scan's total (and the sizes), and once for the result words.
+ * RS_EINVAL: everything kb_fork returns it for.  RS_ESTATE: a by-reference handle on either side, src not reset, different
+ * devices, an inference-only dst, or a step of the replay that met a delta that is not finite or not above zero (a host-packed
+ * file with a repeated landmark): the other dictionaries finish, dst is then left reset with the sources' control state and
+ * empty dictionaries, kb_get_rebuild still reports every min_delta and kb_last_error counts the dictionaries and names the
+ * first.  RS_EOVERFLOW: the full shells do not fit dst's pool -- dst is left as kb_fork leaves it.
+ * kb_get_rebuild: per dictionary of the last kb_fork_rebuild into k that replayed, the smallest delta met, [n_envs][S] (1.0
+ * below two landmarks).  A min_delta at or below eta is legitimate: it says that the slot order is not one the Projectron
+ * inserted in (the dictionary was pruned, or it is foreign), not that Kinv is wrong.  work, counted from the plan: [0] Kinv
+ * tiles (32 KB + 1 KB of partial sums) read by the mat-vecs, [1] rank-1 units (8 KB read, 8 KB written), [2] rounds (steps
+ * that ran chip-wide, beyond the first 192 of every dictionary), [3] dictionaries that hold a landmark.  RS_ESTATE: no replay
+ * ran into k (never called, or the last call ended before it: a refusal, an overflow).
+ * kb_rebuild_time_ms: with kb_set_kernel_timing on in dst at the call, device ms of the last call's replay (one pair of HIP
+ * events around it, on dst's stream); 0 otherwise. */
+int kb_fork_rebuild(kb_handle* dst, kb_handle* src, const int32_t* src_index);
+int kb_get_rebuild(kb_handle* k, double* min_delta /* [n_envs][S] */, uint64_t work[4]);
+int kb_rebuild_time_ms(kb_handle* k, double* ms);
 /* on = 0: the resident loop (kb_step_resident, each step of kb_run_resident) runs select_action(new obs) only -- the
  * reference's loop body past learning_time (kbrl_control.py:131-133): dictionaries, accuracies and security factors stay as
  * they are; margins, adjusted, action and the tie-break counters move as select_action moves them; a history column is still

@@ -5,6 +5,7 @@
 
 struct kb_prune_state;  // kb_prune.hip
 struct kb_ref_state;    // kb_ref.hip
+struct kb_rebuild_state;  // kb_rebuild.hip
 
 struct kb_handle {
     kb_config cfg;
@@ -75,6 +76,7 @@ struct kb_handle {
     uint64_t* d_fork_base = nullptr; // [n_dict + 1] first pool double of every dictionary (exclusive scan of its shells' sizes)
     uint64_t* h_fork_total = nullptr;  // pinned: the scan's total
     kb_prune_state* prune = nullptr; // kb_prune's lists and the pruned counters: NOT a saved region (kb_prune.hip)
+    kb_rebuild_state* rebuild = nullptr;  // kb_fork_rebuild into this handle: its plan, result words and timing (kb_rebuild.hip)
     kb_ref_state* ref = nullptr;     // a by-reference handle (kb_deploy_ref): the store of shared dictionaries, the map, the groups (kb_ref.hip)
     EventSpans spans;  // kernel timing (kb_set_kernel_timing), by kind: 0 update phase, 1 select phase; ONE launch of: 2 heavy_matvec_kernel,
                        // 3 heavy_rank1_kernel, 4 select_bin_kernel, 5 heavy_finish_kernel, 6 select_gemm_kernel, 7 update_small_kernel
@@ -87,6 +89,7 @@ static void kb_prune_release(kb_handle* k);  // kb_prune.hip
 static void kb_prune_restart(kb_handle* k);  // the pruned counters start over (kb_reset, kb_load_state, kb_fork)
 // by-reference handles (kb_ref.hip): their dictionaries live in a store handle, (replica, slice) -> dictionary through a map
 static void kb_ref_release(kb_handle* k);
+static void kb_rebuild_release(kb_handle* k);  // kb_rebuild.hip
 static kb_handle* kb_ref_store(kb_handle* k);
 static int kb_ref_dict(kb_handle* k, size_t task);
 static int kb_ref_select(kb_handle* k, const float* d_state);  // the scoring of launch_select: one fused kernel
@@ -458,6 +461,7 @@ extern "C" void kb_destroy(kb_handle* k) {
     if (k->h_fork_total) (void)hipHostFree(k->h_fork_total);
     kb_prune_release(k);
     kb_ref_release(k);
+    kb_rebuild_release(k);
     if (k->h_seen) (void)hipHostFree(k->h_seen);
     if (k->h_total) (void)hipHostFree(k->h_total);
     if (k->stream) (void)hipStreamDestroy(k->stream);

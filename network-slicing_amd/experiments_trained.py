@@ -20,6 +20,8 @@ For each (scenario, accuracy range):
 --save-agents DIR writes the trained agents of every cell to DIR/scenario_N_KBRL_xx.kbagent (an agent file: landmarks,
 coefficients and control state, ranslice.agent_file) right after training; --load-agents DIR skips step 1 and evaluates the
 fleet from that file -- in another process, on another day -- with the evaluation arrays of steps 2-4 equal number for number.
+--load-agents DIR --learning-control runs the control leg from the file as well: the agents come back as LEARNING agents
+(VecKBRL.load_agents(blob, index, learning=True): Kinv is rebuilt on the device) and go on learning on the fleet.
 """
 import argparse
 import os
@@ -101,10 +103,12 @@ def _write_evaluation(h, scenario, a_range, runs, R, eval_steps, out_dir):
     return path, viol, res, window_statistics(viol, res, sc.scenarios[scenario]['n_prbs'])
 
 
-def _evaluate_loaded(scenario, a_range, runs, R, eval_steps, out_dir, device, graph, verbose, by_reference, directory):
-    """steps 2-4 of a cell whose agents come from their file: agent k of the file is trained run runs[k]"""
+def _evaluate_loaded(scenario, a_range, runs, R, eval_steps, out_dir, device, graph, verbose, by_reference, directory,
+                     learning_control=False, pool_bytes=32 << 30):
+    """steps 2-4 of a cell whose agents come from their file: agent k of the file is trained run runs[k].  learning_control: the
+    same agents loaded once more with learning left on (their Kinv rebuilt on the device), against the same fleet"""
     from ranslice import agent_file
-    from ranslice.kbrl_dev import VecKBRL
+    from ranslice.kbrl_dev import VecKBRL, fork_pool_bytes
     n = len(runs)
     t1 = time.perf_counter()
     with open(agents_path(directory, scenario, a_range), 'rb') as f:
@@ -112,22 +116,40 @@ def _evaluate_loaded(scenario, a_range, runs, R, eval_steps, out_dir, device, gr
     sizes = agent_file.info(blob)['m']
     if sizes.shape[0] != n:
         raise ValueError('{} holds {} agents, the cell has {} runs'.format(agents_path(directory, scenario, a_range), sizes.shape[0], n))
-    deployed = VecKBRL.load_agents(blob, np.repeat(np.arange(n, dtype=np.int32), R), by_reference=by_reference, device=device)
+    index = np.repeat(np.arange(n, dtype=np.int32), R)
+    deployed = VecKBRL.load_agents(blob, index, by_reference=by_reference, device=device)
     pool = deployed.pool()
     h = _fleet_run(deployed, scenario, n * R, eval_steps, device, graph)
     t_eval = time.perf_counter() - t1
     deployed.close()
     path, viol, res, dep = _write_evaluation(h, scenario, a_range, runs, R, eval_steps, out_dir)
+    lc = None
+    if learning_control:
+        t2 = time.perf_counter()
+        control = VecKBRL.load_agents(blob, index, device=device, learning=True, pool_bytes=fork_pool_bytes(sizes[index]) + pool_bytes)
+        rebuilt = control.rebuild_stats()
+        hc = _fleet_run(control, scenario, n * R, eval_steps, device, graph)
+        shape = (n, R, eval_steps)
+        lc = dict(window_statistics(hc['violation'].reshape(shape), hc['resources'].reshape(shape), sc.scenarios[scenario]['n_prbs']),
+                  wall_s=time.perf_counter() - t2, pool=control.pool(), rebuild_rounds=rebuilt['rounds'],
+                  rebuild_min_delta=float(rebuilt['min_delta'].min()))
+        control.close()
     if verbose:
         fmt = '{:.4f} +- {:.4f}'
         print('scenario {} KBRL {}: {} agents loaded from their file, {} replicas each for {} steps in inference mode ({:.1f} s)'
               .format(scenario, a_range[0], n, R, eval_steps, t_eval))
         print('  deployed (frozen, {} unseen traffic realisations per agent): violations per stage {}, resource occupation {}'
               .format(R, fmt.format(*dep['violations']), fmt.format(*dep['occupation'])))
-    return dict(scenario=scenario, accuracy_range=list(a_range), runs=n, train_steps=None, eval_replicas=R, eval_steps=eval_steps,
-                window=None, train_wall_s=0.0, eval_wall_s=t_eval, deployed=dep, training_window=None, max_dictionary=int(sizes.max()),
-                mean_dictionary=float(sizes.mean()), deployed_pool_bytes=int(pool['used_bytes']), by_reference=bool(by_reference),
-                path=path, loaded=True)
+        if lc is not None:
+            print('  the same agents on the same fleet with learning left on (loaded with Kinv rebuilt): violations per stage {}, resource '
+                  'occupation {}'.format(fmt.format(*lc['violations']), fmt.format(*lc['occupation'])))
+    out = dict(scenario=scenario, accuracy_range=list(a_range), runs=n, train_steps=None, eval_replicas=R, eval_steps=eval_steps,
+               window=None, train_wall_s=0.0, eval_wall_s=t_eval, deployed=dep, training_window=None, max_dictionary=int(sizes.max()),
+               mean_dictionary=float(sizes.mean()), deployed_pool_bytes=int(pool['used_bytes']), by_reference=bool(by_reference),
+               path=path, loaded=True)
+    if lc is not None:
+        out['learning_control'] = lc
+    return out
 
 
 def train_and_deploy(scenario, a_range, runs=range(RUNS), train_steps=TRAIN_STEPS, eval_replicas=EVAL_REPLICAS, eval_steps=EVAL_STEPS,
@@ -139,14 +161,16 @@ def train_and_deploy(scenario, a_range, runs=range(RUNS), train_steps=TRAIN_STEP
     no files).  by_reference: the fleet shares each agent's dictionaries (VecKBRL.deploy(index, by_reference=True)): the pool is
     the trained agents', not the replicas'; the results are the copy's bit for bit.
     save_agents / load_agents: a directory; the cell's agent file (agents_path) is written after training, or read INSTEAD of
-    training -- the evaluation arrays are the same either way (summary['training_window'] is None for a loaded cell, and
-    learning_control needs the training handle)."""
+    training -- the evaluation arrays are the same either way (summary['training_window'] is None for a loaded cell; its
+    learning_control leg loads the agents with their Kinv rebuilt, which continues exactly as full forks of the trained handle
+    would)."""
     from ranslice.kbrl_dev import VecKBRL, fork_pool_bytes
     runs = list(runs)
     n, R = len(runs), int(eval_replicas)
     n_prbs = sc.scenarios[scenario]['n_prbs']
     if load_agents is not None:
-        return _evaluate_loaded(scenario, a_range, runs, R, eval_steps, out_dir, device, graph, verbose, by_reference, load_agents)
+        return _evaluate_loaded(scenario, a_range, runs, R, eval_steps, out_dir, device, graph, verbose, by_reference, load_agents,
+                                learning_control=learning_control, pool_bytes=pool_bytes)
     t0 = time.perf_counter()
     ev = BatchedEvaluator(scenario, a_range, steps=train_steps, out_dir=out_dir)
     agent, env = ev.train(runs, device=device, capacity=capacity, pool_bytes=pool_bytes, graph=graph)
@@ -217,8 +241,8 @@ if __name__ == '__main__':
     ap.add_argument('--save-agents', metavar='DIR', help='write the trained agents of every cell to DIR (one agent file per cell)')
     ap.add_argument('--load-agents', metavar='DIR', help='skip training: evaluate the agents --save-agents wrote to DIR')
     args = ap.parse_args()
-    if args.load_agents and (args.save_agents or args.learning_control):
-        ap.error('--load-agents evaluates agents from their files: it neither trains (--learning-control) nor saves')
+    if args.load_agents and args.save_agents:
+        ap.error('--load-agents evaluates agents from their files: it neither trains nor saves')
     for scenario, a_range in product(args.scenarios, accuracy_list):
         train_and_deploy(scenario, a_range, range(args.runs), train_steps=args.train_steps, eval_replicas=args.eval_replicas,
                          eval_steps=args.eval_steps, out_dir=args.out, learning_control=args.learning_control,

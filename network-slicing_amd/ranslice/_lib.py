@@ -22,6 +22,7 @@ KB_EXPORTS = (
     'kb_prune', 'kb_get_pruned', 'kb_prune_time_ms', 'kb_get_prune_work',
     'kb_deploy_ref',
     'kb_export_bytes', 'kb_export_agents', 'kb_agents_info', 'kb_import_agents', 'kb_agents_kernel_times',
+    'kb_fork_rebuild', 'kb_get_rebuild', 'kb_rebuild_time_ms',
 )
 
 EXPORTS = (
@@ -195,6 +196,9 @@ def load(dev=None):
     L.kb_agents_info.argtypes = [vp, C.c_uint64, C.POINTER(KbConfig), ip]
     L.kb_import_agents.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(vp)]
     L.kb_agents_kernel_times.argtypes = [dp, up]
+    L.kb_fork_rebuild.argtypes = [vp, vp, ip]
+    L.kb_get_rebuild.argtypes = [vp, dp, up]
+    L.kb_rebuild_time_ms.argtypes = [vp, dp]
     L.kb_prune.argtypes = [vp, C.c_int32, up]
     L.kb_get_pruned.argtypes = [vp, i64p]
     L.kb_prune_time_ms.argtypes = [vp, dp, i64p]

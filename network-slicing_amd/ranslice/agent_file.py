@@ -6,6 +6,7 @@ library (kb_agents_info, which makes no device call).
     pack(config, agents)    -> bytes, the device's bytes exactly, hash included; pack(unpack(blob)) == blob
     info(blob)              -> the configuration and pool kb_import_agents would create, validated by the library
     from_reference(agent)   -> bytes, from anything shaped like the reference's kbrl_control.KBRL_Control
+    with_capacity(blob, c)  -> bytes, the same agents under another capacity (room to grow for imported learners)
 
 config: dict(n_prbs, capacity, dims [S], alfa, accuracy_range (lo, hi), gamma, eta).
 An agent: dict(landmarks = S arrays [m, dims[s] + 1], coeff = S arrays [m], action, security_factors, margins [S], adjusted,
@@ -118,6 +119,24 @@ def read_header(blob):
     S = f[4]
     return dict(magic=f[0], bytes=f[1], hash=f[2], n_agents=f[3], n_slices=S, n_prbs=f[5], capacity=f[6], dims=list(f[7:15]),
                 alfa=f[15], accuracy_range=(f[16], f[17]), gamma=f[18], eta=f[19], dict_doubles=f[20])
+
+
+def with_capacity(blob, capacity):
+    """-> the same file with the header's capacity replaced (and the hash with it): the limit per dictionary of the handle an
+    import creates.  VecKBRL.load_agents(blob, learning=True, capacity=...) uses it to give imported learners room to grow."""
+    blob = bytes(blob)
+    f = list(struct.unpack(_HEADER, blob[:HEADER_BYTES]))
+    if f[0] != MAGIC:
+        raise ValueError('agent_file.with_capacity: not an agent file')
+    if int(capacity) == f[6]:
+        return blob
+    f[6] = int(capacity)
+    f[2] = 0
+    out = bytearray(blob)
+    out[:HEADER_BYTES] = struct.pack(_HEADER, *f)
+    f[2] = fnv1a(memoryview(out)[HASH_FROM:])
+    out[:HEADER_BYTES] = struct.pack(_HEADER, *f)
+    return bytes(out)
 
 
 def unpack(blob, check=True):

@@ -276,16 +276,33 @@ class VecKBRL:
         self._check(self.L.kb_synchronize(self.h))
 
     # ---- agent fork, deployment, inference mode --------------------------------------------
-    def fork_from(self, src, index):
+    def fork_from(self, src, index, rebuild=False):
         """agent j of this handle := agent index[j] of `src` (kb_fork): a VecKBRL of the same configuration but n_envs and
         pool_bytes, on the same device.  Dictionaries (Kinv included), control state, tie-break stream and flags travel;
-        statistics and caches restart.  Continuing agent j gives, bit for bit, what continuing src agent index[j] would."""
+        statistics and caches restart.  Continuing agent j gives, bit for bit, what continuing src agent index[j] would.
+        rebuild=True (kb_fork_rebuild): `src` may be an inference-only VecKBRL (deploy(index), load_agents(blob)), which holds
+        no Kinv -- it is rebuilt on the device by replaying the insertions in slot order, bit for bit the Kinv of the learning
+        handle the agents came from as long as their landmarks were never reordered (rebuild_stats())."""
         index = np.ascontiguousarray(index, dtype=np.int32)
         if index.shape != (self.n_envs,):
             raise ValueError('fork_from: index must have n_envs = %d entries' % self.n_envs)
         if src.L is not self.L:
             raise RuntimeError('the two agents were created from different builds of libranslice')
-        self._check(self.L.kb_fork(self.h, src.h, index.ctypes.data_as(_ip)))
+        fork = self.L.kb_fork_rebuild if rebuild else self.L.kb_fork
+        self._check(fork(self.h, src.h, index.ctypes.data_as(_ip)))
+
+    def rebuild_stats(self):
+        """of the last fork_from(..., rebuild=True) into this handle: dict(min_delta [n_envs, S] = the smallest delta the replay
+        met per dictionary (1.0 below two landmarks; at or below eta: the slot order is not an insertion order -- pruned or
+        foreign --, which is legitimate), matvec_tiles, rank1_units, matvec_bytes read, rank1_bytes read + written, rounds,
+        dictionaries, replay_ms = device time of the replay when set_kernel_timing was on at the call, else 0)"""
+        md = np.zeros((self.n_envs, self.S))
+        w = (C.c_uint64 * 4)()
+        self._check(self.L.kb_get_rebuild(self.h, md.ctypes.data_as(_dp), w))
+        ms = C.c_double()
+        self._check(self.L.kb_rebuild_time_ms(self.h, C.byref(ms)))
+        return dict(min_delta=md, matvec_tiles=int(w[0]), rank1_units=int(w[1]), matvec_bytes=int(w[0]) * (32768 + 1024),
+                    rank1_bytes=int(w[1]) * 16384, rounds=int(w[2]), dictionaries=int(w[3]), replay_ms=ms.value)
 
     def deploy(self, index, by_reference=False):
         """-> an inference-only VecKBRL (frozen = True) of len(index) agents, agent j := agent index[j] of this one
@@ -323,11 +340,22 @@ class VecKBRL:
         return blob.tobytes()
 
     @classmethod
-    def load_agents(cls, blob, index=None, by_reference=False, device=0):
+    def load_agents(cls, blob, index=None, by_reference=False, device=0, learning=False, capacity=None, pool_bytes=None):
         """-> an inference-only VecKBRL (frozen = True) holding the agents of an agent file in file order (kb_import_agents):
         bit for bit the handle deploy() would have made of the exported agents.  index: fan out instead -- replica j := agent
-        index[j] of the file, through deploy(index, by_reference); the intermediate handle is released."""
+        index[j] of the file, through deploy(index, by_reference); the intermediate handle is released.
+        learning=True: -> a LEARNING VecKBRL of the file's agents (index: replica j := agent index[j]; default all, in file
+        order) whose Kinv is rebuilt on the device (fork_from(..., rebuild=True)): update_control, update, run_resident,
+        save_state and fork_from work, and the agents continue as the handle they were exported from would.  capacity: the
+        learning handle's limit per dictionary (default: the file's; at least its largest dictionary); pool_bytes: default
+        fork_pool_bytes of the chosen dictionaries plus room for each to grow by two shells."""
+        if learning and by_reference:
+            raise ValueError('load_agents: learning=True builds a handle with dictionaries (and Kinv) of its own; by_reference=True '
+                             'shares read-only ones -- choose one')
         L = _lib.load()
+        if learning and capacity is not None:
+            from . import agent_file
+            blob = agent_file.with_capacity(blob, capacity)
         raw = np.frombuffer(bytes(blob), dtype=np.uint8)
         cfg = KbConfig()
         if L.kb_agents_info(raw.ctypes.data_as(C.c_void_p) if raw.size else None, raw.size, C.byref(cfg), None) != 0:
@@ -342,6 +370,24 @@ class VecKBRL:
         d.dims = [int(cfg.dims[s]) for s in range(d.S)]
         d.nv = int(sum(d.dims))
         d.frozen = True
+        if learning:
+            try:
+                idx = np.arange(d.n_envs, dtype=np.int32) if index is None else np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+                if idx.size == 0 or idx.min() < 0 or idx.max() >= d.n_envs:
+                    raise ValueError('load_agents: index must name agents 0 .. %d of the file' % (d.n_envs - 1))
+                if pool_bytes is None:
+                    sizes = d.dictionary_sizes()[idx]
+                    pool_bytes = fork_pool_bytes(np.minimum(sizes + 128, d.capacity))
+                ag = cls(int(idx.size), d.dims, d.n_prbs, alfa=cfg.alfa, accuracy_range=(cfg.acc_lo, cfg.acc_hi), gamma=cfg.gamma,
+                         eta=cfg.eta, capacity=d.capacity, device=device, pool_bytes=int(pool_bytes))
+                try:
+                    ag.fork_from(d, idx, rebuild=True)
+                except Exception:
+                    ag.close()
+                    raise
+                return ag
+            finally:
+                d.close()
         if index is None:
             return d
         try:

@@ -18,6 +18,10 @@ PRUNE = ['prune_list_kernel', 'prune_choose_kernel', 'prune_plan_kernel', 'prune
 REF_SCRATCH = {'select_ref_kernel': 0, 'ref_gather_kernel': 0}
 # the agent-file kernels (kb_agents.hip): reported, and held to no scratch at all -- pack and build are pure streaming kernels
 AGENTS = ['agents_count_kernel', 'agents_tables_kernel', 'agents_pack_kernel', 'agents_build_kernel', 'agents_finish_kernel']
+# kb_fork_rebuild's kernels (kb_rebuild.hip): reported; the two streaming kernels of the rounds are held to no scratch at all, the
+# per-dictionary ones to what update_small_kernel is allowed (they inline the same triangle mat-vec)
+REBUILD_SCRATCH = {'rebuild_sizes_kernel': 0, 'rebuild_pages_kernel': 0, 'rebuild_small_kernel': 64, 'rebuild_matvec_kernel': 0,
+                   'rebuild_finish_kernel': 0, 'rebuild_rank1_kernel': 0}
 PRODUCTION = ["embb_step_kernelILi16ELb0ELb0ELb1E", "embb_step_kernelILi16ELb0ELb1ELb1E"]   # <16, false, plain | BLOCK, FDIV>
 
 
@@ -84,6 +88,16 @@ def check(path=LOG):
             continue
         r = res[hit[0]]
         print('%s: VGPRs %s, scratch %s B/lane, occupancy %s' % (key, r.get('VGPRs'), r.get('ScratchSize'), r.get('Occupancy')))
+        if r.get('ScratchSize', 0) > limit:
+            bad.append('%s spills %d B/lane (> %d)' % (key, r['ScratchSize'], limit))
+    for key, limit in REBUILD_SCRATCH.items():
+        hit = [k for k in res if key in k]
+        if not hit:
+            bad.append('%s: not found in %s' % (key, path))
+            continue
+        r = res[hit[0]]
+        print('%s: VGPRs %s, scratch %s B/lane, occupancy %s, LDS %s B' % (key, r.get('VGPRs'), r.get('ScratchSize'), r.get('Occupancy'),
+                                                                           r.get('LDS Size')))
         if r.get('ScratchSize', 0) > limit:
             bad.append('%s spills %d B/lane (> %d)' % (key, r['ScratchSize'], limit))
     return bad
