@@ -995,11 +995,11 @@ static int launch_step(rs_handle* h) {
             if (g == 8) {
                 if (tr) RS_LAUNCH_STEP(8, true, true);
                 else if (h->block_hint) RS_LAUNCH_STEP(8, false, true);
-                else hipLaunchKernelGGL((embb_step_kernel<8, false, false, true>), grid, block, 0, lstream, a);
+                else RS_LAUNCH_STEP(8, false, false);
             } else if (g == 16) {
                 if (tr) RS_LAUNCH_STEP(16, true, true);
                 else if (h->block_hint) RS_LAUNCH_STEP(16, false, true);
-                else hipLaunchKernelGGL((embb_step_kernel<16, false, false, true>), grid, block, 0, lstream, a);  // (run-time flag inside)
+                else RS_LAUNCH_STEP(16, false, false);
             } else {
                 if (tr) RS_LAUNCH_STEP(32, true, true);
                 else RS_LAUNCH_STEP(32, false, true);

@@ -213,6 +213,11 @@ __device__ __forceinline__ double max_finite(double a, double b) {
     return r;
 }
 
+// lane >> 3 == k, the k-th 8-lane team of the wave, as a CONSTANT lane mask.  Written as a compare, each of the eight masks is
+// formed once, above the slot loop, and then held in an SGPR pair for the whole step -- spilled, and fetched back with two
+// v_readlane each in every round that deals spans to teams.  As a constant the mask is an s_mov where it is used.
+__device__ __forceinline__ bool team_is(int k) { return __builtin_amdgcn_inverse_ballot_w64(0xffull << (8 * k)); }
+
 // ballot restricted to this lane's G-lane group (bit u = lane u of the group)
 template <int G>
 __device__ __forceinline__ unsigned group_ballot(bool c, int gbase) {
@@ -527,11 +532,20 @@ struct StepArgs {
                               // the split step: the head of the cost ranking on the 16-lane instance, the rest on the 8-lane one
 };
 
-// select among three wave-uniform values by a per-lane index 0..2
+// select among three wave-uniform values by a per-lane index 0..2 (rs_mux.hip)
 template <class T>
 __device__ __forceinline__ T sel3(int i, T a, T b, T c) {
     return i == 0 ? a : (i == 1 ? b : c);
 }
+
+// What the kernel needs of a fading trace, one LDS row per trace type (a UE's `ftype`, flags bits 1-2): as twelve launch
+// constants selected by ftype at every use they sat in SGPRs for the whole step, most of them spilled
+struct alignas(16) TraceRow {
+    int T;   // time samples (RsDev.T)
+    int co;  // columns of the traces before it (RsDev.col_off)
+    int fo;  // element offset inside the table buffer (RsDev.fad_off, < 2^31: rs_load_fading)
+    int vo;  // byte offset inside the column-valid buffer (RsDev.valid_off)
+};
 
 // SINRSelectiveFading.get_snr's index walk (channel_models.py:171-191): one step, redraw on leaving [0, T)
 // (time-addressed, include/rs_philox.h), skipping columns that contain NaN (Q10)
@@ -552,6 +566,7 @@ __device__ __forceinline__ void walker_advance(int& findex, int& fstep, int Tn, 
 // remainder.  No per-RB values are stored anywhere.  Returns the lane's own sum (or `keep` if it has no span).
 // mi: the logistic curves' (x0, k) per modulation in LDS, mi[md] and mi[4 + md] (six doubles held in registers across the
 // response were what pushed five loop-long values out to scratch in every slot)
+template <bool TEAMC = false>
 __device__ __forceinline__ double team_response(const double* mi, const double* fad, const double* nom_wave, bool mine,
                                                 int rbs, int span_col, int mod, double keep) {
     const int lane = (int)(threadIdx.x & 63u);
@@ -568,7 +583,7 @@ __device__ __forceinline__ double team_response(const double* mi, const double* 
         for (int k = 0; k < 8; ++k) {
             const int o = rest ? __builtin_ctzll(rest) : 0;
             rest &= rest - 1ull;
-            owner = team == k ? o : owner;
+            owner = (TEAMC ? team_is(k) : team == k) ? o : owner;
         }
         const bool on = round * 8 + team < n_sp;
         const int c0 = bperm(span_col, owner);
@@ -670,7 +685,7 @@ __device__ __forceinline__ float fast_quad(rs_f4u q, int k0, int n, float hi, fl
 // S~ of the spans flagged `mine` (2..64 RBs), dealt to 8-lane teams like team_response: lane j of a team takes elements
 // 4 j .. 4 j + 3 and 32 + 4 j .. 35 + 4 j -- two 16-byte loads, both in flight; any order of summation will do
 #define RS_FAST_WIDE 64
-template <class F>
+template <bool TEAMC, class F>
 __device__ __forceinline__ double fast_team_sums(const double* mi, const float* c1s, const float* fad32, const double* nom_wave,
                                                  bool mine, int rbs, int span_col, int mod, F meanwhile) {
     const int lane = (int)(threadIdx.x & 63u);
@@ -686,7 +701,7 @@ __device__ __forceinline__ double fast_team_sums(const double* mi, const float* 
         for (int k = 0; k < 8; ++k) {
             const int o = rest ? __builtin_ctzll(rest) : 0;
             rest &= rest - 1ull;
-            owner = team == k ? o : owner;
+            owner = (TEAMC ? team_is(k) : team == k) ? o : owner;
         }
         const bool on = round * 8 + team < n_sp;
         const int c0 = bperm(span_col, owner);
@@ -755,11 +770,17 @@ __device__ __forceinline__ double fast_wide_sums(const double* mi, const float* 
 // BLOCK: the contested PF allocation may hand out RB pairs in block rounds (wide slices); without it the instance
 // carries only the trip loop (fewer live registers: the whole point at 5 waves per SIMD).
 // FDIV: pf_b * bits / slot_length by the verified reciprocal form (rs_create checks every reachable `bits`; RsDev.pf_div_fast)
-// -- a template parameter since round 4: as a run-time flag it put a branch into every one of the four shares a block-round
-// iteration forms and kept their (independent) chains from being interleaved.
+// -- a template parameter: as a run-time flag it put a branch into every one of the four shares a block-round iteration forms
+// and kept their (independent) chains from being interleaved, and in the trip loop it was one more lane mask to hold.
 template <int G, bool TRACE, bool BLOCK, bool FDIV>
 __global__ __launch_bounds__(256, (G == 16 && !TRACE) ? RS_OCC : RS_OCC_OTHER) void embb_step_kernel(StepArgs A) {
     static_assert(G == 8 || G == 16 || G == 32, "lanes per task");
+    // The plain instances (the random script's narrow slices: bench.py's headline) take the traces' constants from the LDS table
+    // L_tr and the span dealing's team masks as constants (team_is); the BLOCK instances keep both as launch constants in
+    // SGPRs.  Under the agents' allocations the constant team masks cost the 16-lane BLOCK instance 4 % (VGPR spill instructions
+    // 49 -> 83 beside the table) and the table alone gains it nothing (profiles/step_sgpr_ab.txt).
+    constexpr bool TABLE = !BLOCK;
+    constexpr bool TEAMC = !BLOCK;
     constexpr int TPB = 256 / G;                     // tasks per block
     constexpr int TPW = 64 / G;                      // tasks per wave
     constexpr int CH = 12;                           // slots per chunk of channel estimates (table row = 24 B)
@@ -777,6 +798,7 @@ __global__ __launch_bounds__(256, (G == 16 && !TRACE) ? RS_OCC : RS_OCC_OTHER) v
     __shared__ double L_ref[32];             // MCS reference SNR (estimate_rx_prob)
     __shared__ double L_mi[8];               // logistic MI curves: x0 of the three modulations, pad, k of the three, pad
     __shared__ float L_c1[4];                // -k log2(e) of the three modulations in float32 (the reception test by guard band)
+    __shared__ TraceRow L_tr[4];             // per fading trace (row 3: unused, zero); TABLE instances
     __shared__ int L_task[TPB][4];           // per task: cbr_at, vbr_at, slice draw counter, next UE serial
     __shared__ double W_mi[4][RS_WIDE_MAX];  // per wave: MI values of one WIDE span (response of 65..192 RBs); sized so
                                              // that a block stays within 25 LDS granules of 1280 B: 5 blocks per CU
@@ -786,6 +808,12 @@ __global__ __launch_bounds__(256, (G == 16 && !TRACE) ? RS_OCC : RS_OCC_OTHER) v
     if (tid >= 64 && tid < 96) L_ref[tid - 64] = D->mcs_ref[tid - 64];
     if (tid >= 96 && tid < 104) L_mi[tid - 96] = (tid & 3) == 3 ? 0.0 : (tid < 100 ? D->mi_x0[tid - 96] : D->mi_k[tid - 100]);
     if (tid >= 104 && tid < 108) L_c1[tid - 104] = tid < 107 ? D->rx_c1[tid - 104] : 0.0f;
+    if (TABLE && tid >= 112 && tid < 116) {
+        const int f = tid - 112;
+        TraceRow tr = {0, 0, 0, 0};
+        if (f < RS_N_TRACES) tr = {D->T[f], D->col_off[f], (int)D->fad_off[f], (int)D->valid_off[f]};
+        L_tr[f] = tr;
+    }
     __syncthreads();
     const RsState& S = *A.S;
     const int clock0 = (int)A.run[0];
@@ -810,18 +838,25 @@ __global__ __launch_bounds__(256, (G == 16 && !TRACE) ? RS_OCC : RS_OCC_OTHER) v
     const double slot_len = D->slot_length;
     const double pf_a = D->pf_a, pf_b = D->pf_b;
     const double slot_rc = D->slot_rc;
-    // (the plain 16-lane instance keeps the run-time flag: its trip loop has one share per iteration, and it measured 1.5 %
-    // slower with the constant -- a different schedule at the same 96 registers)
-    const bool pf_div_fast = BLOCK ? FDIV : (D->pf_div_fast != 0);
+    // (a constant in every instance.  The plain 16-lane one kept a run-time flag -- a 64-bit lane mask, spilled and fetched back
+    // inside the leader's run -- while that measured 1.5 % faster than the constant; with the traces' constants out of the
+    // SGPRs it no longer does: profiles/step_sgpr_ab.txt)
+    constexpr bool pf_div_fast = FDIV;
+    // one field of trace type ft: from the row read from L_tr, or selected among the three launch constants.  (Macros, not a
+    // lambda: with the constants captured by a closure the state pointers loaded through A.S were no longer proven global and
+    // the BLOCK instances loaded their state with flat loads; and selected where the parent selected them, the BLOCK instances'
+    // code stays what it was.)
+#define RS_TRACE_ROW(ft) (TABLE ? L_tr[ft] : TraceRow{0, 0, 0, 0})
+#define RS_TR(ft, row, field, a, b, c) (TABLE ? (row).field : sel3(ft, a, b, c))
     const int gran = D->gran;
     const bool has_nan = D->has_nan != 0;
     const bool rx_fast = D->rx_band > 0.0;  // the reception test by guard band is available for this configuration
     const double est_band = D->est_band;
     const bool est_fast = !TRACE && est_band > 0.0 && A.fps != nullptr;
-    const int co0 = D->col_off[0], co1 = D->col_off[1], co2 = D->col_off[2];
-    const int T0 = D->T[0], T1 = D->T[1], T2 = D->T[2];
-    const int fo0 = (int)D->fad_off[0], fo1 = (int)D->fad_off[1], fo2 = (int)D->fad_off[2];  // < 2^31 (rs_load_fading)
-    const int vo0 = (int)D->valid_off[0], vo1 = (int)D->valid_off[1], vo2 = (int)D->valid_off[2];
+    const int co0 = TABLE ? 0 : D->col_off[0], co1 = TABLE ? 0 : D->col_off[1], co2 = TABLE ? 0 : D->col_off[2];
+    const int T0 = TABLE ? 0 : D->T[0], T1 = TABLE ? 0 : D->T[1], T2 = TABLE ? 0 : D->T[2];
+    const int fo0 = TABLE ? 0 : (int)D->fad_off[0], fo1 = TABLE ? 0 : (int)D->fad_off[1], fo2 = TABLE ? 0 : (int)D->fad_off[2];
+    const int vo0 = TABLE ? 0 : (int)D->valid_off[0], vo1 = TABLE ? 0 : (int)D->valid_off[1], vo2 = TABLE ? 0 : (int)D->valid_off[2];
 
     // set_prbs (node_b.py:71-74): contiguous ranges in slice order
     int prb_lo = 0;
@@ -1090,7 +1125,7 @@ __global__ __launch_bounds__(256, (G == 16 && !TRACE) ? RS_OCC : RS_OCC_OTHER) v
                 if (hold_at != now) {  // Q13: a one-slot holding time never joins the slice
                     // SINRSelectiveFading.insert_user (channel_models.py:163-169)
                     ftype = (int)rs_stream_integers(&st, RS_N_TRACES);
-                    findex = (int)rs_stream_integers(&st, sel3(ftype, T0, T1, T2));
+                    findex = (int)rs_stream_integers(&st, RS_TR(ftype, L_tr[ftype], T, T0, T1, T2));
                     fstep = rs_stream_pm1(&st);
                     const MacroCell mc = macro_cell_draw(D, st);
                     nominal = mc.x;
@@ -1158,13 +1193,14 @@ __global__ __launch_bounds__(256, (G == 16 && !TRACE) ? RS_OCC : RS_OCC_OTHER) v
                 const bool on = have && clock0 + t0 + tt + 1 < dep;
                 const int ftype = (fl >> 1) & 3;
                 int fs = (fl & 8) ? 1 : -1;
-                const int Tn = sel3(ftype, T0, T1, T2);
+                const TraceRow tr = RS_TRACE_ROW(ftype);
+                const int Tn = RS_TR(ftype, tr, T, T0, T1, T2);
                 int f = f0 + fs * adv;
                 const bool straight = !has_nan && f >= 0 && f < Tn;
                 if (wave_any(on && !straight)) {
                     if (on && !straight) {
                         const uint32_t ser = L_serial[wb + src];
-                        const uint8_t* vcol = A.fad_valid + sel3(ftype, vo0, vo1, vo2);
+                        const uint8_t* vcol = A.fad_valid + RS_TR(ftype, tr, vo, vo0, vo1, vo2);
                         f = f0;
                         for (int a = 0; a < adv; ++a)
                             walker_advance(f, fs, Tn, has_nan, vcol, k0, k1, (uint32_t)isl, ser, (uint32_t)(now + a));
@@ -1175,7 +1211,7 @@ __global__ __launch_bounds__(256, (G == 16 && !TRACE) ? RS_OCC : RS_OCC_OTHER) v
                 // instances' every estimate, numpy's pairwise sum of the samples themselves decides
                 bool todo = on;
                 if (est_fast) {
-                    const double* __restrict__ ps = A.fps + (on ? (sel3(ftype, co0, co1, co2) + f) * (P + 1) + plo : 0);
+                    const double* __restrict__ ps = A.fps + (on ? (RS_TR(ftype, tr, co, co0, co1, co2) + f) * (P + 1) + plo : 0);
                     const double pa = ps[0], pb = ps[on ? np : 0];
                     const double mean = (pb - pa) / (double)np + nom;
                     const double rr = RS_RINT(mean);
@@ -1184,7 +1220,7 @@ __global__ __launch_bounds__(256, (G == 16 && !TRACE) ? RS_OCC : RS_OCC_OTHER) v
                     todo = on && !sure;
                 }
                 if (wave_any(todo)) {
-                    const double* __restrict__ colp = A.fad + (todo ? sel3(ftype, fo0, fo1, fo2) + f * P + plo : 0);
+                    const double* __restrict__ colp = A.fad + (todo ? RS_TR(ftype, tr, fo, fo0, fo1, fo2) + f * P + plo : 0);
                     const double sum = lane_pairwise(np, todo, [&](int i) { return colp[i] + nom; });
                     if (todo) T_esnr[wb + src][tt] = (short)(int)RS_RINT(sum / (double)np);  // round(np.mean(...)): half-to-even (Q7)
                 }
@@ -1302,10 +1338,11 @@ __global__ __launch_bounds__(256, (G == 16 && !TRACE) ? RS_OCC : RS_OCC_OTHER) v
         const int ftype = (flags >> 1) & 3;
         if (n_prb > 0 && active) {
             int fstep = (flags & 8) ? 1 : -1;
-            walker_advance(findex, fstep, sel3(ftype, T0, T1, T2), has_nan, A.fad_valid + sel3(ftype, vo0, vo1, vo2), key0,
+            const TraceRow tr = RS_TRACE_ROW(ftype);
+            walker_advance(findex, fstep, RS_TR(ftype, tr, T, T0, T1, T2), has_nan, A.fad_valid + RS_TR(ftype, tr, vo, vo0, vo1, vo2), key0,
                            key1, (uint32_t)sl, L_serial[lt], (uint32_t)now);
             flags = (flags & ~8) | ((fstep > 0 ? 1 : 0) << 3);
-            col = sel3(ftype, fo0, fo1, fo2) + findex * P;
+            col = RS_TR(ftype, tr, fo, fo0, fo1, fo2) + findex * P;
             e_snr = T_esnr[lt][tt0];
         }
         stat += (unsigned)n_ue;
@@ -1635,7 +1672,7 @@ __global__ __launch_bounds__(256, (G == 16 && !TRACE) ? RS_OCC : RS_OCC_OTHER) v
                 double S = 0.0;
                 bool thr_done = false;
                 if (wave_any(multi && !fw)) {
-                    S = fast_team_sums(L_mi, L_c1, A.fad32, &L_nom[wb], multi && !fw, rbs, span_col, mod, threshold);
+                    S = fast_team_sums<TEAMC>(L_mi, L_c1, A.fad32, &L_nom[wb], multi && !fw, rbs, span_col, mod, threshold);
                     thr_done = true;
                 }
                 if (wave_any(fw)) {
@@ -1660,7 +1697,7 @@ __global__ __launch_bounds__(256, (G == 16 && !TRACE) ? RS_OCC : RS_OCC_OTHER) v
                 constexpr int WIDE = RS_WIDE_SPAN;
                 const bool wide_sp = exact && rbs > WIDE && rbs <= RS_WIDE_MAX;
                 if (wave_any(wide_sp)) sum_rx = wide_response(L_mi, A.fad, W_mi[tid >> 6], &L_nom[wb], wide_sp, rbs, span_col, mod);
-                sum_rx = team_response(L_mi, A.fad, &L_nom[wb], exact && !wide_sp, rbs, span_col, mod, sum_rx);
+                sum_rx = team_response<TEAMC>(L_mi, A.fad, &L_nom[wb], exact && !wide_sp, rbs, span_col, mod, sum_rx);
                 // R3: effective SNR and reception probability, every evaluated UE in its own lane
                 if (exact) {
                     const double x0 = L_mi[mod], kk = L_mi[4 + mod];
@@ -1845,6 +1882,8 @@ __global__ __launch_bounds__(256, (G == 16 && !TRACE) ? RS_OCC : RS_OCC_OTHER) v
             for (int k = 0; k < RS_BURSTS; ++k) SE.u_burst[(task * RS_BURSTS + k) * RS_GROUP + gl] = L_burst[k][tid];
         }
     }
+#undef RS_TRACE_ROW
+#undef RS_TR
 }
 
 }  // namespace rs

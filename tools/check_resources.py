@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Register/scratch budget of the step-kernel instances, from the remarks of the last build
-(network-slicing_amd/csrc/build/resources.log).  The two 16-lane production instances are built for 5 waves per
+(network-slicing_amd/csrc/build/resources.log): VGPRs, scratch, occupancy, spilled SGPRs and VGPRs and LDS of every instance.  The two 16-lane production instances are built for 5 waves per
 SIMD (96 VGPRs) and spill; instances that spilled more than ~256 B per lane have twice been seen to compute wrong
 values on this toolchain, so the build fails if a change pushes them past 240 B."""
 import os
@@ -23,6 +23,16 @@ AGENTS = ['agents_count_kernel', 'agents_tables_kernel', 'agents_pack_kernel', '
 REBUILD_SCRATCH = {'rebuild_sizes_kernel': 0, 'rebuild_pages_kernel': 0, 'rebuild_small_kernel': 64, 'rebuild_matvec_kernel': 0,
                    'rebuild_finish_kernel': 0, 'rebuild_rank1_kernel': 0}
 PRODUCTION = ["embb_step_kernelILi16ELb0ELb0ELb1E", "embb_step_kernelILi16ELb0ELb1ELb1E"]   # <16, false, plain | BLOCK, FDIV>
+PLAIN = PRODUCTION[0]          # the instance bench.py's headline runs
+STEP_KERNEL = 'embb_step_kernelIL'
+LDS_LIMIT = 32768              # per block: five blocks of the 16-lane instances share a CU's 160 KiB
+# SGPRs the plain instance may spill.  Every spilled SGPR is parked in a lane of a VGPR the 96-register allocation then lacks, and
+# fetched back with a v_readlane -- a VALU issue slot in a kernel bound by VALU issue -- wherever it is used (tools/spill_sites.py
+# lists the sites).  The parent of this ceiling spilled 137; the value is what the build that introduced it reports
+# (profiles/HISTORY.md, "Step kernel: launch constants and spilled SGPRs").
+SGPR_SPILL_CEILING = 105
+# the device listing of the same build (csrc/Makefile: build/rs_api.s): the plain instance's two hottest loops hold no spill reload
+LISTING = os.path.join(ROOT, 'network-slicing_amd', 'csrc', 'build', 'rs_api.s')
 
 
 def parse(path=LOG):
@@ -39,20 +49,48 @@ def parse(path=LOG):
     return out
 
 
+def step_instances(res):
+    """{template arguments as mangled, e.g. 'ILi16ELb0ELb0ELb1E' (<lanes, TRACE, BLOCK, FDIV>): remarks} of every step-kernel instance"""
+    out = {}
+    for k, r in res.items():
+        m = re.search(r'embb_step_kernel(ILi\d+ELb[01]ELb[01]ELb[01]E)', k)
+        if m:
+            out[m.group(1)] = r
+    return out
+
+
 def check(path=LOG):
     res = parse(path)
     bad = []
+    # every instance of the step kernel, the spilled registers of both files beside the allocation: the tracing, 8- and 32-lane
+    # instances come from the same template, and what a change does to the production pair it does to them
+    for targs, r in sorted(step_instances(res).items()):
+        print('embb_step_kernel%s: VGPRs %s, scratch %s B/lane, occupancy %s, SGPRs spilled %s, VGPRs spilled %s, LDS %s B' % (
+            targs, r.get('VGPRs'), r.get('ScratchSize'), r.get('Occupancy'), r.get('SGPRs Spill'), r.get('VGPRs Spill'), r.get('LDS Size')))
     for key in PRODUCTION:
         hit = [k for k in res if key in k]
         if not hit:
             bad.append('%s: not found in %s' % (key, path))
             continue
         r = res[hit[0]]
-        print('%s: VGPRs %s, scratch %s B/lane, occupancy %s' % (key, r.get('VGPRs'), r.get('ScratchSize'), r.get('Occupancy')))
         if r.get('ScratchSize', 0) > LIMIT:
             bad.append('%s spills %d B/lane (> %d)' % (key, r['ScratchSize'], LIMIT))
         if r.get('Occupancy', 0) < 5:
             bad.append('%s: occupancy %s < 5 waves/SIMD' % (key, r.get('Occupancy')))
+        if r.get('LDS Size', 0) > LDS_LIMIT:
+            bad.append('%s: %d B of LDS per block (> %d: five blocks no longer fit a CU)' % (key, r['LDS Size'], LDS_LIMIT))
+        if key == PLAIN and r.get('SGPRs Spill', 0) > SGPR_SPILL_CEILING:
+            bad.append('%s spills %d SGPRs (> %d)' % (key, r['SGPRs Spill'], SGPR_SPILL_CEILING))
+    # where the plain instance's remaining reloads sit: none in the fast reception round loop, none in the PF leader's run
+    if path == LOG:
+        if not os.path.exists(LISTING):
+            bad.append('%s: no device listing (make -C network-slicing_amd/csrc)' % LISTING)
+        else:
+            sys.path.insert(0, os.path.join(ROOT, 'tools'))
+            import spill_sites
+            problems = spill_sites.check_step_loops(LISTING, PLAIN)
+            print('%s: fast reception round loop and PF leader-run loop: %s' % (PLAIN, '; '.join(problems) if problems else 'no spill reload'))
+            bad += problems
     # The agent's per-learner kernels sit at their register limit too: a refactoring of a helper they inline (round 5: lambdas in the
     # triangle mat-vec) put 608 B per lane of scratch into update_small_kernel / update_heavy_kernel and doubled their time unnoticed.
     for key, limit in KB_SCRATCH.items():
