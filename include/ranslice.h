@@ -571,6 +571,53 @@ int kb_agents_kernel_times(double ms[2], uint64_t bytes[2]);
 int kb_fork_rebuild(kb_handle* dst, kb_handle* src, const int32_t* src_index);
 int kb_get_rebuild(kb_handle* k, double* min_delta /* [n_envs][S] */, uint64_t work[4]);
 int kb_rebuild_time_ms(kb_handle* k, double* ms);
+/* ---- the bridge between shared-dictionary handles (kb_config.shared_dictionary = 1) and per-replica ones.
+ * kb_fork, kb_deploy, kb_deploy_ref, kb_export_agents, kb_fork_rebuild, kb_prune and kb_set_learning keep refusing shared
+ * handles; kb_unshare is the way to all of them, kb_share the way back.  The two storages differ in Kinv alone: a per-replica
+ * dictionary keeps the lower block triangle and a partial-sum area per tile, a shared one both triangles.
+ *
+ * kb_unshare: agent j of dst receives a private copy of each of src's S dictionaries, and the control state of src's replica
+ * src_index[j] (host array of dst->n_envs entries, 0 <= index < src->n_envs, repeats allowed).  src: a shared-dictionary handle,
+ * reset.  dst: a per-replica LEARNING handle (kb_create), same kb_config as src except n_envs, pool_bytes, shared_dictionary,
+ * first_env and capacity (every dictionary must fit dst's); same device.  Per dictionary: the vector pages whole (coordinates,
+ * their float32 copy, coefficients, grid index and chain links), Kinv as the lower block triangle, copied tile for tile from
+ * the full storage, the partial-sum areas zeroed (scratch that every mat-vec writes before it reads), and the sizes, heads,
+ * off-grid / float32 marks and versions.  Per agent, from replica src_index[j], exactly what kb_fork copies: action, security
+ * factors, margins, adjusted, accuracies, the tie-break stream (seed and counters), the observation the resident loop chose its
+ * last action in, and the flag word verbatim.  Restarted as after kb_fork: statistics, repair-work counters, launch-order
+ * lists, stored select scores -- and the cache of the last kb_predict (kb_update answers RS_ESTATE until a new kb_predict).
+ * Layout: kb_fork's (full shells at an exclusive scan of their sizes in (dictionary, shell) order), so two calls with the same
+ * arguments give byte-identical kb_save_state blobs.  The DATA crosses bit for bit; CONTINUING does not promise the bits the
+ * shared handle would have produced -- the triangle forms d* = Kinv K_f in another summation order than the full storage.
+ * Ordered as kb_fork, by events on both streams: after src's queued work, src's later work after the gather; the host waits once,
+ * for the scan's total; never captured into a graph.  src is not written, and a handle whose communicator was aborted can
+ * still be unshared: that is how its dictionaries are rescued.
+ * RS_EINVAL: src is not a shared-dictionary handle or dst is one, the configurations differ, an index out of range.
+ * RS_ESTATE: src not reset, dst inference-only, a by-reference handle on either side, different devices, src between
+ * kb_shared_scan and kb_shared_commit of a round (proposals scanned or applied, the round not committed).  RS_EOVERFLOW: the
+ * shells do not fit dst's pool, or a dictionary exceeds dst's capacity -- dst is then left as kb_fork leaves it: reset, with
+ * the sources' control state and empty dictionaries.
+ *
+ * kb_share: the other direction.  dst: a shared-dictionary LEARNING handle; src: a per-replica learning handle (it holds Kinv;
+ * an inference-only source goes through kb_fork_rebuild first), same kb_config except n_envs, pool_bytes, shared_dictionary and
+ * first_env; same device.  dst's S dictionaries become those of src agent dict_agent: pages whole, the lower tiles as they
+ * are, every upper tile (bi, bj), bi < bj, the transpose of the lower tile (bj, bi) -- what the shared mode's own symmetric
+ * update would have stored --, and the sizes, heads, marks and versions.  Control state, tie-break stream, last observation and
+ * flag word of dst replica j come from src agent ctl_index[j] (host array of dst->n_envs entries; NULL: dict_agent for every
+ * replica).  dst becomes reset; its previous dictionaries are dropped as by kb_reset, and everything the shared mode derives
+ * from a dictionary (the scoring operands and products, the proposal cursors) is rebuilt by the next step.  The call does not
+ * touch dst's communicator and nothing in it depends on the rank: ranks that each call it with identical sources hold
+ * identical dictionaries.  Ordering, restarts and the one host wait (here: the S sizes) as kb_unshare.  RS_EINVAL: dst is not
+ * a shared-dictionary handle or src is one, the configurations differ (a different capacity included: dst is not touched),
+ * dict_agent or an index out of range.  RS_ESTATE: as kb_unshare (here dst is the handle that must not be inside a round).
+ * RS_EOVERFLOW: the shells do not fit dst's pool -- dst is left reset, with the sources' control state and empty dictionaries.
+ *
+ * kb_bridge_time_ms: of the last kb_unshare / kb_share into k -- with kb_set_kernel_timing on in k at the call, device ms of
+ * its gather (one pair of HIP events on k's stream around the table and shell kernels; 0 otherwise), and the bytes its work
+ * plan counts: bytes[0] read, bytes[1] written. */
+int kb_unshare(kb_handle* dst, kb_handle* src, const int32_t* src_index);
+int kb_share(kb_handle* dst, kb_handle* src, int32_t dict_agent, const int32_t* ctl_index);
+int kb_bridge_time_ms(kb_handle* k, double* ms, uint64_t bytes[2]);
 /* on = 0: the resident loop (kb_step_resident, each step of kb_run_resident) runs select_action(new obs) only -- the
  * reference's loop body past learning_time (kbrl_control.py:131-133): dictionaries, accuracies and security factors stay as
  * they are; margins, adjusted, action and the tie-break counters move as select_action moves them; a history column is still

@@ -6,6 +6,7 @@
 struct kb_prune_state;  // kb_prune.hip
 struct kb_ref_state;    // kb_ref.hip
 struct kb_rebuild_state;  // kb_rebuild.hip
+struct kb_bridge_state;   // kb_bridge.hip
 
 struct kb_handle {
     kb_config cfg;
@@ -77,6 +78,9 @@ struct kb_handle {
     uint64_t* h_fork_total = nullptr;  // pinned: the scan's total
     kb_prune_state* prune = nullptr; // kb_prune's lists and the pruned counters: NOT a saved region (kb_prune.hip)
     kb_rebuild_state* rebuild = nullptr;  // kb_fork_rebuild into this handle: its plan, result words and timing (kb_rebuild.hip)
+    kb_bridge_state* bridge = nullptr;    // kb_unshare / kb_share into this handle: result words, timing and plan bytes (kb_bridge.hip)
+    bool round_open = false;         // shared mode, host-driven rounds: proposals were scanned or applied and kb_shared_commit has not closed
+                                     // the round yet -- the dictionaries are between two states of a step (kb_unshare / kb_share refuse)
     kb_ref_state* ref = nullptr;     // a by-reference handle (kb_deploy_ref): the store of shared dictionaries, the map, the groups (kb_ref.hip)
     EventSpans spans;  // kernel timing (kb_set_kernel_timing), by kind: 0 update phase, 1 select phase; ONE launch of: 2 heavy_matvec_kernel,
                        // 3 heavy_rank1_kernel, 4 select_bin_kernel, 5 heavy_finish_kernel, 6 select_gemm_kernel, 7 update_small_kernel
@@ -90,6 +94,7 @@ static void kb_prune_restart(kb_handle* k);  // the pruned counters start over (
 // by-reference handles (kb_ref.hip): their dictionaries live in a store handle, (replica, slice) -> dictionary through a map
 static void kb_ref_release(kb_handle* k);
 static void kb_rebuild_release(kb_handle* k);  // kb_rebuild.hip
+static void kb_bridge_release(kb_handle* k);   // kb_bridge.hip
 static kb_handle* kb_ref_store(kb_handle* k);
 static int kb_ref_dict(kb_handle* k, size_t task);
 static int kb_ref_select(kb_handle* k, const float* d_state);  // the scoring of launch_select: one fused kernel
@@ -462,6 +467,7 @@ extern "C" void kb_destroy(kb_handle* k) {
     kb_prune_release(k);
     kb_ref_release(k);
     kb_rebuild_release(k);
+    kb_bridge_release(k);
     if (k->h_seen) (void)hipHostFree(k->h_seen);
     if (k->h_total) (void)hipHostFree(k->h_total);
     if (k->stream) (void)hipStreamDestroy(k->stream);
@@ -513,6 +519,7 @@ extern "C" int kb_reset(kb_handle* k, const int32_t* initial_action, const int32
     HIPCHK(k, hipMemset(k->K.big, 0, sizeof(int32_t) * 2 * (1 + KB_BIG_MAX)));
     HIPCHK(k, hipMemset(k->K.isbig, 0, sizeof(int32_t) * 2 * T));
     (void)hipFree(dseed);
+    k->round_open = false;
     k->is_reset = true;
     return RS_OK;
 }
@@ -1209,6 +1216,10 @@ extern "C" int kb_shared_scan(kb_handle* k, const float* state, const int32_t* a
     HIPCHK(k, hipMemcpyAsync(counts, k->d_counts, sizeof(int32_t) * S, hipMemcpyDeviceToHost, k->stream));
     HIPCHK(k, hipMemcpyAsync(props, k->d_props, sizeof(double) * S * budget * KB_PROP_W, hipMemcpyDeviceToHost, k->stream));
     HIPCHK(k, hipStreamSynchronize(k->stream));
+    // a round with local proposals is open until kb_shared_commit closes it (a scan that found none ends the step: the caller
+    // neither applies nor commits -- unless another rank proposed, and then kb_shared_apply opens the round)
+    k->round_open = false;
+    for (size_t s = 0; s < S; ++s) k->round_open = k->round_open || counts[s] > 0;
     return RS_OK;
 }
 
@@ -1223,6 +1234,7 @@ extern "C" int kb_shared_apply(kb_handle* k, const int32_t* counts, const double
     HIPCHK(k, hipMemcpyAsync(k->d_counts, counts, sizeof(int32_t) * S, hipMemcpyHostToDevice, k->stream));
     HIPCHK(k, hipMemcpyAsync(k->d_props, props, sizeof(double) * S * budget * KB_PROP_W, hipMemcpyHostToDevice, k->stream));
     k->gemm_fresh = false;
+    k->round_open = true;
     launch_shared_apply(k, k->d_props, k->d_counts, (int)budget);
     HIPCHK(k, hipGetLastError());
     return kb_check(k);
@@ -1238,6 +1250,7 @@ extern "C" int kb_shared_commit(kb_handle* k, const int32_t* n_accept) {
                        k->d_cursor);
     HIPCHK(k, hipGetLastError());
     HIPCHK(k, hipStreamSynchronize(k->stream));
+    k->round_open = false;
     return RS_OK;
 }
 
@@ -1691,6 +1704,7 @@ extern "C" int kb_load_state(kb_handle* k, const void* blob, uint64_t bytes) {
         k->h_seen[1] = hd.seen1;
     }
     k->gemm_fresh = false;
+    k->round_open = false;
     return RS_OK;
 }
 

@@ -23,6 +23,7 @@ KB_EXPORTS = (
     'kb_deploy_ref',
     'kb_export_bytes', 'kb_export_agents', 'kb_agents_info', 'kb_import_agents', 'kb_agents_kernel_times',
     'kb_fork_rebuild', 'kb_get_rebuild', 'kb_rebuild_time_ms',
+    'kb_unshare', 'kb_share', 'kb_bridge_time_ms',
 )
 
 EXPORTS = (
@@ -199,6 +200,9 @@ def load(dev=None):
     L.kb_fork_rebuild.argtypes = [vp, vp, ip]
     L.kb_get_rebuild.argtypes = [vp, dp, up]
     L.kb_rebuild_time_ms.argtypes = [vp, dp]
+    L.kb_unshare.argtypes = [vp, vp, ip]
+    L.kb_share.argtypes = [vp, vp, C.c_int32, ip]
+    L.kb_bridge_time_ms.argtypes = [vp, dp, up]
     L.kb_prune.argtypes = [vp, C.c_int32, up]
     L.kb_get_pruned.argtypes = [vp, i64p]
     L.kb_prune_time_ms.argtypes = [vp, dp, i64p]

@@ -43,6 +43,13 @@ def fork_pool_bytes(sizes):
     return POOL_PREAMBLE_BYTES + int((VEC_PAGE_BYTES * nsh + (32768 + 1024) * nsh * (nsh + 1) // 2).sum())
 
 
+def shared_pool_bytes(sizes):
+    """bytes of pool a shared-dictionary handle needs to take dictionaries of these sizes through to_shared: per shell b of a
+    dictionary one vector page and 2 b + 1 Kinv tiles of 32 KB (both block triangles, no partial-sum areas), plus the preamble"""
+    nsh = (np.asarray(sizes, dtype=np.int64) + 63) // 64
+    return POOL_PREAMBLE_BYTES + int((VEC_PAGE_BYTES * nsh + 32768 * nsh * nsh).sum())
+
+
 class VecKBRL:
     frozen = False   # True on the inference-only objects deploy() returns
     by_reference = False   # True on those deploy(index, by_reference=True) returns: dictionaries stored once per distinct agent
@@ -62,6 +69,7 @@ class VecKBRL:
         self.n_envs, self.S, self.n_prbs, self.dims = n_envs, len(dims), n_prbs, list(dims)
         self.nv = int(sum(dims))
         self.capacity = capacity
+        self.device = int(device)
         self.h = C.c_void_p()
         self._check(self.L.kb_create(C.byref(cfg), int(device), C.byref(self.h)))
 
@@ -323,6 +331,7 @@ class VecKBRL:
         d.cfg = cfg
         d.n_envs, d.S, d.n_prbs, d.dims, d.nv, d.capacity = int(index.size), self.S, self.n_prbs, list(self.dims), self.nv, self.capacity
         d.frozen = True
+        d.device = self.device
         d.by_reference = bool(by_reference)
         cfg.pool_bytes = d.pool()['total_bytes']
         return d
@@ -369,6 +378,7 @@ class VecKBRL:
         d.n_envs, d.S, d.n_prbs, d.capacity = int(cfg.n_envs), int(cfg.n_slices), int(cfg.n_prbs), int(cfg.capacity)
         d.dims = [int(cfg.dims[s]) for s in range(d.S)]
         d.nv = int(sum(d.dims))
+        d.device = int(device)
         d.frozen = True
         if learning:
             try:
@@ -394,6 +404,47 @@ class VecKBRL:
             return d.deploy(index, by_reference=by_reference)
         finally:
             d.close()
+
+    # ---- the bridge to shared dictionaries ----------------------------------------------------
+    def to_shared(self, agent, n_envs, ctl_index=None, budget=64, max_rounds=4, first_env=0, pool_bytes=None):
+        """-> a SharedVecKBRL of n_envs replicas whose S dictionaries are those of agent `agent` of this (learning, per-replica)
+        handle (kb_share): landmarks, coefficients and Kinv bit for bit, the upper block triangle filled in by transposition.
+        Replica j takes the control state, tie-break stream, last observation and flags of agent ctl_index[j] (default: `agent`
+        for all).  The fleet goes on learning together from there; an inference-only VecKBRL goes through
+        load_agents(..., learning=True) / fork_from(..., rebuild=True) first.  pool_bytes: default the library's own for a
+        shared handle (every dictionary at its capacity, bounded)."""
+        if ctl_index is not None:
+            ctl_index = np.ascontiguousarray(ctl_index, dtype=np.int32).reshape(-1)
+            if ctl_index.shape != (int(n_envs),):
+                raise ValueError('to_shared: ctl_index must have n_envs = %d entries' % n_envs)
+        cfg = self.cfg
+        sh = SharedVecKBRL(int(n_envs), self.dims, self.n_prbs, budget=budget, max_rounds=max_rounds, alfa=cfg.alfa,
+                           accuracy_range=(cfg.acc_lo, cfg.acc_hi), gamma=cfg.gamma, eta=cfg.eta, capacity=self.capacity,
+                           device=self.device, first_env=first_env, pool_bytes=int(pool_bytes or 0))
+        try:
+            sh.share_from(self, agent, ctl_index)
+        except Exception:
+            sh.close()
+            raise
+        return sh
+
+    def bridge_time_ms(self):
+        """of the last to_agents / to_shared INTO this handle: dict(ms = device time of the gather when set_kernel_timing was on
+        at the call, else 0; read_bytes, written_bytes from its work plan) (kb_bridge_time_ms)"""
+        ms = C.c_double()
+        b = (C.c_uint64 * 2)()
+        self._check(self.L.kb_bridge_time_ms(self.h, C.byref(ms), b))
+        return dict(ms=ms.value, read_bytes=int(b[0]), written_bytes=int(b[1]))
+
+    def unshare_from(self, shared, index):
+        """agent j of this (learning, per-replica) handle := a private copy of `shared`'s dictionaries with the control state of
+        its replica index[j] (kb_unshare); what SharedVecKBRL.to_agents does into a handle it creates"""
+        index = np.ascontiguousarray(index, dtype=np.int32)
+        if index.shape != (self.n_envs,):
+            raise ValueError('unshare_from: index must have n_envs = %d entries' % self.n_envs)
+        if shared.L is not self.L:
+            raise RuntimeError('the two agents were created from different builds of libranslice')
+        self._check(self.L.kb_unshare(self.h, shared.h, index.ctypes.data_as(_ip)))
 
     def set_learning(self, on):
         """on=False: step_resident / run_resident select only (KBRL_Control.run past learning_time); True resumes learning"""
@@ -496,6 +547,42 @@ class SharedVecKBRL(VecKBRL):
             raise ValueError('first_env must be rank * n_envs (contiguous replica shards)')
         buf = C.create_string_buffer(bytes(unique_id), 128)
         self._check(self.L.kb_comm_init(self.h, buf, int(rank), int(world)))
+
+    def share_from(self, src, agent, ctl_index=None):
+        """the S dictionaries of this (shared, learning) handle := those of agent `agent` of the per-replica learning handle
+        `src`, replica j's control state := that of src agent ctl_index[j] (default: `agent`) (kb_share); what VecKBRL.to_shared
+        does into a handle it creates"""
+        if ctl_index is not None:
+            ctl_index = np.ascontiguousarray(ctl_index, dtype=np.int32)
+            if ctl_index.shape != (self.n_envs,):
+                raise ValueError('share_from: ctl_index must have n_envs = %d entries' % self.n_envs)
+        if src.L is not self.L:
+            raise RuntimeError('the two agents were created from different builds of libranslice')
+        self._check(self.L.kb_share(self.h, src.h, int(agent), ctl_index.ctypes.data_as(_ip) if ctl_index is not None else None))
+
+    def to_agents(self, index, capacity=None, pool_bytes=None, device=None):
+        """-> a learning VecKBRL of len(index) agents (kb_unshare): each holds a private copy of the S shared dictionaries --
+        landmarks, coefficients and Kinv bit for bit -- and the control state, tie-break stream, last observation and flags of
+        replica index[j] of this handle.  From there every per-replica tool applies: .deploy(...), .export_agents(...),
+        .prune(...), .fork_from(...), .set_learning(...), or learning on per replica.  capacity: the new handle's limit per
+        dictionary (default: this handle's; at least its largest dictionary); pool_bytes: default fork_pool_bytes of the copied
+        dictionaries plus room for each to grow by two shells; device: default this handle's (it must be the same one)."""
+        index = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        if index.size == 0:
+            raise ValueError('to_agents: index names no replica')
+        capacity = self.capacity if capacity is None else int(capacity)
+        if pool_bytes is None:
+            sizes = np.tile(self.dictionary_sizes().astype(np.int64), (index.size, 1))
+            pool_bytes = fork_pool_bytes(np.minimum(sizes + 128, max(capacity, 64)))
+        cfg = self.cfg
+        ag = VecKBRL(int(index.size), self.dims, self.n_prbs, alfa=cfg.alfa, accuracy_range=(cfg.acc_lo, cfg.acc_hi), gamma=cfg.gamma,
+                     eta=cfg.eta, capacity=capacity, device=self.device if device is None else int(device), pool_bytes=int(pool_bytes))
+        try:
+            ag.unshare_from(self, index)
+        except Exception:
+            ag.close()
+            raise
+        return ag
 
     def step_resident(self, env, count_rounds=False):
         """one closed-loop agent step on the device: the shared learning step on the simulator's buffers, then

@@ -22,6 +22,8 @@ AGENTS = ['agents_count_kernel', 'agents_tables_kernel', 'agents_pack_kernel', '
 # per-dictionary ones to what update_small_kernel is allowed (they inline the same triangle mat-vec)
 REBUILD_SCRATCH = {'rebuild_sizes_kernel': 0, 'rebuild_pages_kernel': 0, 'rebuild_small_kernel': 64, 'rebuild_matvec_kernel': 0,
                    'rebuild_finish_kernel': 0, 'rebuild_rank1_kernel': 0}
+# the bridge's kernels (kb_bridge.hip): reported, and held to no scratch at all -- gathers on kb_fork's work line
+BRIDGE = ['unshare_count_kernel', 'unshare_tables_kernel', 'unshare_shells_kernel', 'share_tables_kernel', 'share_shells_kernel']
 PRODUCTION = ["embb_step_kernelILi16ELb0ELb0ELb1E", "embb_step_kernelILi16ELb0ELb1ELb1E"]   # <16, false, plain | BLOCK, FDIV>
 PLAIN = PRODUCTION[0]          # the instance bench.py's headline runs
 STEP_KERNEL = 'embb_step_kernelIL'
@@ -109,7 +111,7 @@ def check(path=LOG):
                                                                            r.get('LDS Size')))
         if r.get('ScratchSize', 0) > 0:
             bad.append('%s spills %d B/lane (> 0)' % (key, r['ScratchSize']))
-    for key in AGENTS:
+    for key in AGENTS + BRIDGE:
         hit = [k for k in res if key in k]
         if not hit:
             bad.append('%s: not found in %s' % (key, path))
