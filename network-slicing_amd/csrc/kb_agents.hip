@@ -133,18 +133,6 @@ __global__ __launch_bounds__(256) void agents_tables_kernel(AgentArgs a) {
     if (jd == 0 && lane == 0) K.pool_top[0] = a.pbase[a.n_dict];
 }
 
-// the dictionary a chunk of the work line belongs to: the last one that starts at or before p (fork_shells_kernel's bisection;
-// empty dictionaries share their start with the next)
-__device__ __forceinline__ int agents_find(const uint64_t* base, int n_dict, uint64_t p) {
-    int lo = 0, hi = n_dict - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (base[mid] <= p) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 // position in the LDS tile of element i of a run of landmark-major rows of d doubles
 __device__ __forceinline__ int agents_tile_at(int i, int d, int ld) {
     const int r = i / d;
@@ -165,7 +153,7 @@ __global__ __launch_bounds__(256) void agents_pack_kernel(AgentArgs a) {
     const uint64_t n_chunks = (a.pbase[a.n_dict] - 64) / KB_VEC;
     for (uint64_t c = (uint64_t)blockIdx.x * 4 + wave; c < n_chunks; c += (uint64_t)gridDim.x * 4) {
         const uint64_t p = 64 + c * KB_VEC;
-        const int jd = agents_find(a.pbase, a.n_dict, p);
+        const int jd = kb_line_find(a.pbase, a.n_dict, p);  // (empty dictionaries share their start with the next)
         const int b = (int)((p - a.pbase[jd]) / KB_VEC);
         const int s = jd % D.S, d = D.dims[s] + 1, ld = d | 1;
         const int sd = agents_dict(a, jd);
@@ -212,7 +200,7 @@ __global__ __launch_bounds__(256) void agents_build_kernel(AgentArgs a) {
     const uint64_t n_chunks = (a.pbase[a.n_dict] - 64) / KB_VEC;
     for (uint64_t c = (uint64_t)blockIdx.x * 4 + wave; c < n_chunks; c += (uint64_t)gridDim.x * 4) {
         const uint64_t p = 64 + c * KB_VEC;
-        const int jd = agents_find(a.pbase, a.n_dict, p);
+        const int jd = kb_line_find(a.pbase, a.n_dict, p);  // (empty dictionaries share their start with the next)
         const int b = (int)((p - a.pbase[jd]) / KB_VEC);
         const int s = jd % D.S, d = D.dims[s] + 1, ld = d | 1;
         const int m = a.F.m[jd];
@@ -601,16 +589,7 @@ extern "C" int kb_import_agents(const void* blob, uint64_t bytes, int device, kb
     if ((rc = kb_agents_scan(d, pl, a, d->n_dict)) != RS_OK) return fail(rc, d->err);
     if (pl.tops[0] != d->D.pool_doubles || pl.tops[1] - 64 != h.dict_doubles)  // (kb_agents_info summed the same sizes)
         return fail(RS_EINVAL, "the sizes on the device do not add up to the file's");
-    // what kb_reset restarts, as kb_fork_core does (the tables kernel writes stats, fver and the retained hits)
-    const size_t T = (size_t)d->T;
-    if ((e = hipMemsetAsync(d->d_gstats, 0, sizeof(uint64_t) * 32, d->stream)) != hipSuccess ||
-        (e = hipMemsetAsync(d->K.hv_work, 0, sizeof(unsigned long long) * 8, d->stream)) != hipSuccess ||
-        (e = hipMemsetAsync(d->K.heavy, 0, sizeof(int32_t) * 4, d->stream)) != hipSuccess ||
-        (e = hipMemsetAsync(d->K.big, 0, sizeof(int32_t) * 2 * (1 + KB_BIG_MAX), d->stream)) != hipSuccess ||
-        (e = hipMemsetAsync(d->K.isbig, 0, sizeof(int32_t) * 2 * T, d->stream)) != hipSuccess ||
-        (e = hipMemsetAsync(d->K.pool, 0, sizeof(double) * 64, d->stream)) != hipSuccess)
-        return fail(RS_EHIP, hipGetErrorString(e));
-    kb_prune_restart(d);
+    if ((rc = kb_restart(d)) != RS_OK) return fail(rc, d->err);
     hipLaunchKernelGGL(kb::agents_tables_kernel, dim3((unsigned)((a.n_dict + 3) / 4)), dim3(256), 0, d->stream, a);
     const uint64_t n_chunks = (pl.tops[0] - 64) / KB_VEC;
     if (n_chunks) {

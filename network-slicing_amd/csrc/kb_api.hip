@@ -479,6 +479,24 @@ extern "C" void kb_destroy(kb_handle* k) {
 static thread_local std::string kb_nohandle_err = "null handle";
 extern "C" const char* kb_last_error(const kb_handle* k) { return k ? k->err.c_str() : kb_nohandle_err.c_str(); }
 
+// The counters since kb_reset start over, on the handle's stream: kb_reset itself, and (kb_restart) every call that leaves a
+// handle as after one
+static int kb_restart_counters(kb_handle* k) {
+    HIPCHK(k, hipMemsetAsync(k->d_gstats, 0, sizeof(uint64_t) * 32, k->stream));
+    HIPCHK(k, hipMemsetAsync(k->K.hv_work, 0, sizeof(unsigned long long) * 8, k->stream));
+    kb_prune_restart(k);
+    return RS_OK;
+}
+// What a transfer of agents into the handle restarts (kb_fork.hip, kb_import_agents): the counters, the repair queue, the
+// launch-order lists and the 64 doubles below every shell (never read).  Its tables kernel writes stats, fver and the retained hits.
+static int kb_restart(kb_handle* k) {
+    HIPCHK(k, hipMemsetAsync(k->K.heavy, 0, sizeof(int32_t) * 4, k->stream));
+    HIPCHK(k, hipMemsetAsync(k->K.big, 0, sizeof(int32_t) * 2 * (1 + KB_BIG_MAX), k->stream));
+    HIPCHK(k, hipMemsetAsync(k->K.isbig, 0, sizeof(int32_t) * 2 * (size_t)k->T, k->stream));
+    HIPCHK(k, hipMemsetAsync(k->K.pool, 0, sizeof(double) * 64, k->stream));
+    return kb_restart_counters(k);
+}
+
 extern "C" int kb_reset(kb_handle* k, const int32_t* initial_action, const int32_t* security_factor,
                         const uint64_t* seeds) {
     if (!k || !initial_action || !security_factor || !seeds) return RS_EINVAL;
@@ -505,11 +523,9 @@ extern "C" int kb_reset(kb_handle* k, const int32_t* initial_action, const int32
     HIPCHK(k, hipMemsetAsync(k->K.f32bad, 0, sizeof(int32_t) * (size_t)k->n_dict, k->stream));
     HIPCHK(k, hipMemsetAsync(k->K.ver, 0, sizeof(int32_t) * (size_t)k->n_dict, k->stream));
     HIPCHK(k, hipMemsetAsync(k->K.fver, 0xFF, sizeof(int32_t) * T, k->stream));  // -1: no stored scores
-    HIPCHK(k, hipMemsetAsync(k->d_gstats, 0, sizeof(uint64_t) * 32, k->stream));
-    HIPCHK(k, hipMemsetAsync(k->K.hv_work, 0, sizeof(unsigned long long) * 8, k->stream));
     // (the hits an inference-mode history column repeats: none yet, kb_set_learning)
     HIPCHK(k, hipMemsetAsync(k->d_hits, 0, sizeof(int32_t) * T, k->stream));
-    kb_prune_restart(k);
+    if (kb_restart_counters(k) != RS_OK) return RS_EHIP;
     HIPCHK(k, hipGetLastError());
     HIPCHK(k, hipStreamSynchronize(k->stream));
     if (k->h_seen) k->h_seen[0] = k->h_seen[1] = 0;

@@ -38,14 +38,13 @@
 #include <stdint.h>
 
 #include "../../include/rs_philox.h"
+#include "kb_layout.h"  // KB_CH, KB_TILE, KB_VEC_ROWS, KB_VEC, KB_TRI_NONE and the shells' sizes
 
 namespace kb {
 
 #define KB_DMAX 16        // max len(x)
 #define KB_NPRB_MAX 255   // candidates 0..n_prbs fit four 64-lane groups
 #define KB_GTAB 264       // G[k], k = 0..255 (+ padding)
-#define KB_CH 64          // landmarks per chunk
-#define KB_TILE 4096      // doubles per Kinv tile
 #define KB_ROW_F32 11     // eMBB dictionaries (ten state coordinates + the allocation: rows 0..10): rows 11..15 hold the ten state
                           //   coordinates again as float32, [coordinate][64 landmarks] -- they ARE float32 observations
                           //   (slice_ran.py:321-325), so the copy is exact and the binning pass of select_action reads 40 B per
@@ -57,8 +56,6 @@ namespace kb {
 #define KB_ROW_DS 20      //   d* = Kinv K_f
 #define KB_ROW_IDX 21     //   64 x int32 grid index a_j of the last coordinate (-1: off the grid), 64 x int32 chain link
 #define KB_ROW_PART 22    //   8 rows: the partial sums of d* over the row classes j mod 8 (matvec_colsum)
-#define KB_VEC_ROWS 30
-#define KB_VEC (KB_VEC_ROWS * KB_CH)
 #ifndef KB_OCC
 #ifndef KB_SCORE_UNROLL1
 #define KB_SCORE_UNROLL1 8  // landmarks per unrolled block of the scoring loop when one group of candidates is scored
@@ -166,17 +163,6 @@ __host__ __device__ inline int kb_capr(int cap) { return (cap + 63) & ~63; }
 __host__ __device__ inline size_t kb_apply_lds_doubles(int cap, int budget) {  // shared_apply_kernel's dynamic LDS
     return (size_t)kb_capr(cap) + 4 * (size_t)budget;
 }
-#define KB_TRI_NONE 2  // KbDev.tri of an inference-only handle
-__host__ __device__ inline uint64_t kb_shell_doubles(int b, int tri) {  // tri 1: b + 1 tiles and their 128 partial sums each
-    if (tri == KB_TRI_NONE) return (uint64_t)KB_VEC;
-    return (uint64_t)KB_VEC + (tri ? (uint64_t)(b + 1) * (KB_TILE + 128) : (uint64_t)(2 * b + 1) * KB_TILE);
-}
-// doubles of the shells 0 .. b - 1 of one dictionary (tri 1 or KB_TRI_NONE): where shell b starts in a dictionary laid out whole
-__host__ __device__ inline uint64_t kb_shells_before(int b, int tri) {
-    const uint64_t v = (uint64_t)b * KB_VEC;
-    return tri == KB_TRI_NONE ? v : v + (uint64_t)(KB_TILE + 128) * ((uint64_t)b * (uint64_t)(b + 1) / 2);
-}
-
 __device__ __forceinline__ const uint64_t* shells_of(const KbDev& D, const KbState& K, int dict) {
     return K.shell + (size_t)dict * D.max_shells;
 }

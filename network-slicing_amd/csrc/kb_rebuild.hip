@@ -1,7 +1,7 @@
 // kb_rebuild.hip -- kb_fork_rebuild: kb_fork for sources that hold no Kinv (kb_deploy, kb_import_agents).  The destination's
 // Kinv is rebuilt on the device by replaying the insertions in slot order.
-// #included by rs_api.hip after kb_agents.hip: it uses the agent handle, the fork's scan, tables kernel and checks, and the
-// forceinline pieces of Projectron.update (kb_kbrl.hip); it changes none of their kernels.
+// #included by rs_api.hip after kb_agents.hip: it uses the agent handle, kb_fork.hip's transfer sequence (scan, tables kernel, work
+// line, checks) and the forceinline pieces of Projectron.update (kb_kbrl.hip).
 //
 // THE RULE.  Kinv changes only when a landmark is inserted (a projection touches coefficients), and the insertion of landmark j
 // is a function of landmarks 0 .. j alone: the kernel column of l_j against l_0 .. l_{j-1}, d* = Kinv K_f, delta = max(1 -
@@ -43,57 +43,20 @@ struct RebuildArgs {
 };
 
 // what the host reads in the fork's one wait besides the scan's total: the destination dictionaries' sizes
-__global__ __launch_bounds__(256) void rebuild_sizes_kernel(ForkArgs a, int32_t* m_out) {
+__global__ __launch_bounds__(256) void rebuild_sizes_kernel(XferArgs a, int32_t* m_out) {
     const int jd = blockIdx.x * blockDim.x + threadIdx.x;
     if (jd < a.n_dict) m_out[jd] = a.Ks.m[fork_src_dict(a, jd)];
 }
 
-// Shell gather of a destination that stores Kinv from a source whose shells need not: fork_shells_kernel's work line (the
-// destination's pool cut into pieces of KB_FORK_BLK doubles, a wave each) with every shell split in two -- its vector page
-// comes from the source's shell, its Kinv tiles and their partial-sum areas are zeroed.
-__global__ __launch_bounds__(256) void rebuild_pages_kernel(ForkArgs a) {
-    const KbDev& D = a.Dd;
+// Shell gather of a destination that stores Kinv from a source whose shells need not: the work line with every shell cut in
+// two -- its vector page comes from the source's shell, its Kinv tiles and their partial-sum areas are zeroed.
+__global__ __launch_bounds__(256) void rebuild_pages_kernel(XferArgs a) {
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint64_t top = a.base[a.n_dict];
-    const uint64_t n_blk = (top - 64 + KB_FORK_BLK - 1) / KB_FORK_BLK;
-    for (uint64_t blk = (uint64_t)blockIdx.x * 4 + wave; blk < n_blk; blk += (uint64_t)gridDim.x * 4) {
-        uint64_t p = 64 + blk * KB_FORK_BLK;
-        const uint64_t pe = p + KB_FORK_BLK < top ? p + KB_FORK_BLK : top;
-        int lo = 0, hi = a.n_dict - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (a.base[mid] <= p) lo = mid;
-            else hi = mid - 1;
-        }
-        int jd = lo;
-        while (p < pe) {
-            while (a.base[jd + 1] <= p) ++jd;  // (p < top = base[n_dict]: ends)
-            const uint64_t q = p - a.base[jd];
-            int b = 0;
-            uint64_t c = 0, sz = kb_shell_doubles(0, D.tri);
-            while (q >= c + sz) {
-                c += sz;
-                ++b;
-                sz = kb_shell_doubles(b, D.tri);
-            }
-            const uint64_t in = q - c;
-            const bool page = in < KB_VEC;
-            const uint64_t end = page ? KB_VEC : sz;
-            const uint64_t seg = end - in < pe - p ? end - in : pe - p;
-            const uint64_t so = b < D.max_shells ? a.Ks.shell[(size_t)fork_src_dict(a, jd) * D.max_shells + b] : 0ull;
-            double* __restrict__ d = a.Kd.pool + p;
-            // a source page that is missing or does not lie inside the source's pool is never read (zeros instead)
-            if (page && so >= 64 && so + KB_VEC <= a.src_pool_doubles) {
-                const double* __restrict__ sp = a.Ks.pool + so + in;
-                for (uint64_t o = (uint64_t)lane * 2; o < seg; o += 128) *(kb_f64x2*)(d + o) = *(const kb_f64x2*)(sp + o);
-            } else {
-                const kb_f64x2 z = {0.0, 0.0};
-                for (uint64_t o = (uint64_t)lane * 2; o < seg; o += 128) *(kb_f64x2*)(d + o) = z;
-            }
-            p += seg;
-        }
-    }
+    line_walk(a.base, a.n_dict, a.Dd.tri, KbCutPage(), [&](int jd, int b, uint64_t in, uint64_t p, uint64_t seg) {
+        const uint64_t so = in < KB_VEC ? src_shell(a, fork_src_dict(a, jd), b, KB_VEC) : 0ull;
+        if (so) wave_copy(a.Kd.pool + p, a.Ks.pool + so + in, seg, lane);
+        else wave_zero(a.Kd.pool + p, seg, lane);
+    });
 }
 
 // landmark j of the dictionary -> x[0 .. d - 1] (LDS), for the whole block
@@ -301,80 +264,27 @@ static int kb_rebuild_prepare(kb_handle* k) {
 static int kb_rebuild_core(kb_handle* dst, kb_handle* src, const int32_t* src_index) {
     const char* who = "kb_fork_rebuild";
     int rc;
-    std::string why;
-    if ((rc = kb_fork_classify(src, &why)) != RS_OK || (rc = kb_fork_classify(dst, &why)) != RS_OK) {
-        dst->err = std::string(who) + ": " + why;
-        return rc;
-    }
-    const int n_dst = dst->cfg.n_envs, ND = dst->n_dict;
-    const size_t T = (size_t)dst->T;
-    HIPCHK(dst, hipSetDevice(dst->device));
-    kb_drop_graph(dst);
+    if ((rc = kb_xfer_enter(dst, src, src_index, who)) != RS_OK) return rc;
     if ((rc = kb_rebuild_prepare(dst)) != RS_OK) return rc;
     kb_rebuild_state* r = dst->rebuild;
     r->have = false;
     r->last_ms = 0.0;
     for (int q = 0; q < 4; ++q) r->work[q] = 0;
-    if (!dst->d_fork_idx) HIPCHK(dst, hipMalloc((void**)&dst->d_fork_idx, sizeof(int32_t) * n_dst));
-    if (!dst->d_fork_base) HIPCHK(dst, hipMalloc((void**)&dst->d_fork_base, sizeof(uint64_t) * ((size_t)ND + 2)));
-    if (!dst->h_fork_idx) HIPCHK(dst, hipHostMalloc((void**)&dst->h_fork_idx, sizeof(int32_t) * n_dst, hipHostMallocDefault));
-    if (!dst->h_fork_total) HIPCHK(dst, hipHostMalloc((void**)&dst->h_fork_total, sizeof(uint64_t), hipHostMallocDefault));
-    memcpy(dst->h_fork_idx, src_index, sizeof(int32_t) * n_dst);
-    if ((rc = stream_after(dst, &dst->ev_fork_in, src->stream, dst->stream)) != RS_OK) return rc;
-    HIPCHK(dst, hipMemcpyAsync(dst->d_fork_idx, dst->h_fork_idx, sizeof(int32_t) * n_dst, hipMemcpyHostToDevice, dst->stream));
-    // what kb_reset restarts (the tables kernel writes stats, fver and the retained hits)
-    HIPCHK(dst, hipMemsetAsync(dst->d_gstats, 0, sizeof(uint64_t) * 32, dst->stream));
-    HIPCHK(dst, hipMemsetAsync(dst->K.hv_work, 0, sizeof(unsigned long long) * 8, dst->stream));
-    HIPCHK(dst, hipMemsetAsync(dst->K.heavy, 0, sizeof(int32_t) * 4, dst->stream));
-    HIPCHK(dst, hipMemsetAsync(dst->K.big, 0, sizeof(int32_t) * 2 * (1 + KB_BIG_MAX), dst->stream));
-    HIPCHK(dst, hipMemsetAsync(dst->K.isbig, 0, sizeof(int32_t) * 2 * T, dst->stream));
-    HIPCHK(dst, hipMemsetAsync(dst->K.pool, 0, sizeof(double) * 64, dst->stream));  // (below every shell; never read)
-    kb_prune_restart(dst);
-    kb::ForkArgs a;
-    memset(&a, 0, sizeof a);
-    a.Dd = dst->D;
-    a.Kd = dst->K;
-    a.Ks = src->K;
-    a.src_pool_doubles = src->D.pool_doubles;
-    a.src_tri = src->D.tri;
-    a.n_dict = ND;
-    a.index = dst->d_fork_idx;
-    a.base = dst->d_fork_base;
-    a.total = dst->d_fork_base + ND + 1;
-    a.prev_s = src->d_prev_state;
-    a.prev_d = dst->d_prev_state;
-    a.hits_d = dst->d_hits;
-    hipLaunchKernelGGL(kb::fork_count_kernel, dim3((unsigned)((ND + 255) / 256)), dim3(256), 0, dst->stream, a);
-    hipLaunchKernelGGL(kb::fork_scan_kernel, dim3(1), dim3(1024), 0, dst->stream, a.base, ND, a.total);
+    const int ND = dst->n_dict;
+    kb::XferArgs a = kb_xfer_args(dst, src, ND);
+    uint64_t top;
+    kb_xfer_launch(dst, kb::fork_count_kernel, a, (size_t)ND, 256);
     hipLaunchKernelGGL(kb::rebuild_sizes_kernel, dim3((unsigned)((ND + 255) / 256)), dim3(256), 0, dst->stream, a, r->d_m);
-    HIPCHK(dst, hipGetLastError());
-    dst->h_fork_total[0] = 0;
-    HIPCHK(dst, hipMemcpyAsync(dst->h_fork_total, a.total, sizeof(uint64_t), hipMemcpyDeviceToHost, dst->stream));
     HIPCHK(dst, hipMemcpyAsync(r->h_m, r->d_m, sizeof(int32_t) * (size_t)ND, hipMemcpyDeviceToHost, dst->stream));
-    HIPCHK(dst, hipStreamSynchronize(dst->stream));
-    const uint64_t top = dst->h_fork_total[0];
+    if ((rc = kb_xfer_scan_wait(dst, a, &top)) != RS_OK) return rc;
     a.empty = top > dst->D.pool_doubles ? 1 : 0;
-    hipLaunchKernelGGL(kb::fork_tables_kernel, dim3((unsigned)((ND + 3) / 4)), dim3(256), 0, dst->stream, a);
+    kb_xfer_launch(dst, kb::fork_tables_kernel, a, (size_t)ND, 4);
     HIPCHK(dst, hipGetLastError());
-    auto leave = [&]() -> int {  // the destination is reset whatever the outcome, as after kb_fork
-        const int rc2 = stream_after(dst, &dst->ev_fork_out, dst->stream, src->stream);
-        if (dst->h_seen) dst->h_seen[0] = dst->h_seen[1] = 0;
-        dst->gemm_fresh = false;
-        dst->big_par = 0;
-        dst->is_reset = true;
-        return rc2;
-    };
     if (a.empty) {
-        if ((rc = leave()) != RS_OK) return rc;
-        dst->err = std::string(who) + ": the source dictionaries need " + std::to_string(top * 8) + " bytes of pool, the destination's pool has " +
-                   std::to_string((uint64_t)dst->D.pool_doubles * 8) + "; the destination was left reset with empty dictionaries";
-        return RS_EOVERFLOW;
+        if ((rc = kb_xfer_leave(dst, src)) != RS_OK) return rc;
+        return kb_xfer_overflow(dst, who, top);
     }
-    if (top > 64) {
-        const uint64_t n_blk = (top - 64 + KB_FORK_BLK - 1) / KB_FORK_BLK;
-        const uint64_t grid = (n_blk + 3) / 4;
-        hipLaunchKernelGGL(kb::rebuild_pages_kernel, dim3((unsigned)(grid < 16384 ? grid : 16384)), dim3(256), 0, dst->stream, a);
-    }
+    kb_xfer_launch_line(dst, kb::rebuild_pages_kernel, a, top);
     // the plan: the dictionaries that go on in the rounds by decreasing size (ties by index), and what the replay will stream
     int n_big = 0, max_m = 0;
     for (int jd = 0; jd < ND; ++jd) {
@@ -436,10 +346,10 @@ static int kb_rebuild_core(kb_handle* dst, kb_handle* src, const int32_t* src_in
     const int n_bad = r->h_nbad[0], first = r->h_nbad[1];
     if (n_bad) {  // as after an overflow: the control state of the sources and empty dictionaries
         a.empty = 1;
-        hipLaunchKernelGGL(kb::fork_tables_kernel, dim3((unsigned)((ND + 3) / 4)), dim3(256), 0, dst->stream, a);
+        kb_xfer_launch(dst, kb::fork_tables_kernel, a, (size_t)ND, 4);
         HIPCHK(dst, hipGetLastError());
     }
-    if ((rc = leave()) != RS_OK) return rc;
+    if ((rc = kb_xfer_leave(dst, src)) != RS_OK) return rc;
     if (n_bad) {
         const int S = dst->cfg.n_slices;
         dst->err = std::string(who) + ": the replay of " + std::to_string(n_bad) + " dictionaries met a delta that is not finite or not above zero, first " +

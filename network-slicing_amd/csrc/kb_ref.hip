@@ -270,7 +270,7 @@ __global__ __launch_bounds__(256) void select_ref_kernel(RefArgs A) {
     }
 }
 
-// What is private to a replica, from its source agent: fork_tables_kernel's per-agent and per-learner words, without a dictionary
+// What is private to a replica, from its source agent: the per-agent and per-learner words of kb_fork.hip's gather, without a dictionary
 struct RefGatherArgs {
     KbDev Dd;
     KbState Kd, Ks;
@@ -288,24 +288,11 @@ __global__ __launch_bounds__(256) void ref_gather_kernel(RefGatherArgs a) {
     const int r = a.index[j], sd = r * D.S + s;
     for (int c = lane; c < D.n_prbs; c += 64) a.Kd.acc[(size_t)jd * D.n_prbs + c] = a.Ks.acc[(size_t)sd * D.n_prbs + c];
     if (lane == 0) {
+        gather_task_words(a.Kd, a.Ks, a.hits_d, jd, sd);
         a.Kd.m[jd] = 0;  // (the handle's own tables hold no dictionary: the map leads to the store)
         a.Kd.kf_owner[jd] = -1;
-        a.Kd.tie_ctr[jd] = a.Ks.tie_ctr[sd];
-        a.Kd.action[jd] = a.Ks.action[sd];
-        a.Kd.security[jd] = a.Ks.security[sd];
-        a.Kd.margins[jd] = a.Ks.margins[sd];
-        a.Kd.fver[jd] = -1;
-        for (int q = 0; q < 4; ++q) a.Kd.stats[(size_t)jd * 4 + q] = 0;
-        a.hits_d[jd] = 0;
     }
-    if (s == 0) {
-        if (lane == 0) {
-            a.Kd.seeds[j] = a.Ks.seeds[r];
-            a.Kd.adjusted[j] = a.Ks.adjusted[r];
-            a.Kd.err[j] = a.Ks.err[r];  // verbatim, as through kb_fork
-        }
-        for (int q = lane; q < D.nv; q += 64) a.prev_d[(size_t)j * D.nv + q] = a.prev_s[(size_t)r * D.nv + q];
-    }
+    if (s == 0) gather_agent_words(D, a.Kd, a.Ks, a.prev_d, a.prev_s, j, r, lane);
     if (jd == 0 && lane == 0) a.Kd.pool_top[0] = 64ull;
 }
 

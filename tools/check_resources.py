@@ -24,6 +24,8 @@ REBUILD_SCRATCH = {'rebuild_sizes_kernel': 0, 'rebuild_pages_kernel': 0, 'rebuil
                    'rebuild_finish_kernel': 0, 'rebuild_rank1_kernel': 0}
 # the bridge's kernels (kb_bridge.hip): reported, and held to no scratch at all -- gathers on kb_fork's work line
 BRIDGE = ['unshare_count_kernel', 'unshare_tables_kernel', 'unshare_shells_kernel', 'share_tables_kernel', 'share_shells_kernel']
+# kb_fork's own kernels (kb_fork.hip), whose gather helpers and work line the bridge's and kb_fork_rebuild's call: the same
+FORK = ['fork_count_kernel', 'fork_scan_kernel', 'fork_tables_kernel', 'fork_shells_kernel']
 PRODUCTION = ["embb_step_kernelILi16ELb0ELb0ELb1E", "embb_step_kernelILi16ELb0ELb1ELb1E"]   # <16, false, plain | BLOCK, FDIV>
 PLAIN = PRODUCTION[0]          # the instance bench.py's headline runs
 STEP_KERNEL = 'embb_step_kernelIL'
@@ -111,8 +113,8 @@ def check(path=LOG):
                                                                            r.get('LDS Size')))
         if r.get('ScratchSize', 0) > 0:
             bad.append('%s spills %d B/lane (> 0)' % (key, r['ScratchSize']))
-    for key in AGENTS + BRIDGE:
-        hit = [k for k in res if key in k]
+    for key in AGENTS + BRIDGE + FORK:
+        hit = [k for k in res if re.search(r'\d' + key, k)]  # (the whole mangled name: share_* is not unshare_*)
         if not hit:
             bad.append('%s: not found in %s' % (key, path))
             continue
