@@ -651,6 +651,44 @@ int kb_prune(kb_handle* k, int32_t target, uint64_t* removed_total);
 int kb_get_pruned(kb_handle* k, int64_t* removed /* [n_dictionaries] since kb_reset */);
 int kb_prune_time_ms(kb_handle* k, double ms[3], int64_t n[3]);   /* choose, downdate, move: HIP events, when kernel timing is on */
 int kb_get_prune_work(kb_handle* k, uint64_t work[2]);
+/* ---- the learner's own surface, batched (csrc/kb_fit.hip): sample sequences in, trained learners out; query
+ * sets in, scores out.  Build-defined: the reference has Projectron.predict(x) / update(x, y), one sample per call.
+ *
+ * kb_fit: teacher-forced online learning.  task[i] = e * n_slices + s names learner i of the call (all distinct); it owns rows
+ * first[i] .. first[i + 1] - 1 of x ([first[n]][16] doubles per row, entries past dims[s] + 1 ignored) and y (+1 / -1).  For
+ * every listed learner, independently, for its samples in order: (y_pred, f) = predict(x_t), then update(x_t, y_t) -- exactly
+ * the sequence kb_predict(e, s, x_t); kb_update(e, s, x_t, y_t), with every rule it carries (the float32 roundings while one
+ * landmark is held, f y <= 0 as the mistake test, projection against insertion on delta > eta, saturation at the capacity and
+ * pool exhaustion -- which flag the replica and project --, the float32 mark and grid index of an inserted landmark, the chain
+ * links and version bump, an exact tie f == 0 with a populated dictionary drawing from the learner's tie stream, the
+ * per-learner statistics).  One 256-thread workgroup per learner runs the same device functions as the two one-sample
+ * kernels, so dictionaries (landmarks, coefficients, all of Kinv, sizes), tie counters, statistics, flags and every returned
+ * value are BIT FOR BIT what the one-by-one sequence leaves, whenever the pool suffices for both (with learners growing in
+ * parallel, WHICH learner meets the end of the pool is not the sequential one; each learner then still equals some one-by-one
+ * run with its flag set).  chunk: most samples of one learner per kernel launch (0: the default, 256) -- launches are enqueued
+ * back to back, no result depends on it.  y_pred, f, branch (0 none, 1 projection, 2 dictionary grew), delta and m_after (the
+ * dictionary's size after the sample) are [first[n]] each, written at the same rows as the samples; any may be NULL.
+ * Afterwards the cache of the last kb_predict of every learner that was given samples is invalid (kb_update answers RS_ESTATE
+ * until a new kb_predict), stored select scores are not reused (the version moved), and learners not listed or listed with no
+ * samples are untouched bit for bit.  The host waits for the call.
+ * RS_EINVAL: a task out of range or listed twice, y not +1 / -1, first decreasing, n or chunk negative.  RS_ESTATE: kb_reset
+ * missing; an inference-only handle (kb_deploy, kb_import_agents); a by-reference handle (kb_deploy_ref); a shared-dictionary
+ * handle (several tasks map to one dictionary).
+ *
+ * kb_score: read-only scoring.  Same (task, n, first, x) layout; task may repeat.  f[q] is bit for bit the f kb_predict would
+ * return for that learner and point; y_pred (may be NULL) its sign, 0 on an exact tie or an empty dictionary.  NOTHING is
+ * written into the handle -- no kernel row, no cache, no counter, no tie draw -- so it works on every kind of handle: learning,
+ * kb_deploy, kb_import_agents, kb_deploy_ref (where kb_predict is refused) and shared-dictionary.  One launch per call.
+ * RS_EINVAL: a task out of range, first decreasing, n negative.  RS_ESTATE: kb_reset missing.
+ *
+ * kb_fit_time_ms: of the last calls on the handle.  ms[0]: device time (HIP events) summed over the launches of the last kb_fit,
+ * ms[1]: of the last kb_score's launch -- both 0 unless kb_set_kernel_timing was on at the call.  work[0] samples, work[1]
+ * mistakes, work[2] insertions of the last kb_fit; work[3] kernel evaluations (landmarks x samples) of the last kb_fit plus
+ * those (landmarks x queries) of the last kb_score. */
+int kb_fit(kb_handle* k, const int32_t* task, int32_t n, const int64_t* first, const double* x, const int8_t* y, int32_t chunk,
+           int32_t* y_pred, double* f, int32_t* branch, double* delta, int32_t* m_after);
+int kb_score(kb_handle* k, const int32_t* task, int32_t n, const int64_t* first, const double* x, double* f, int32_t* y_pred);
+int kb_fit_time_ms(kb_handle* k, double ms[2], uint64_t work[4]);
 
 #ifdef __cplusplus
 }

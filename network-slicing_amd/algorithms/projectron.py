@@ -84,6 +84,30 @@ class Projectron:
         self._ensure(x)
         self._agent.update(self._e, self._s, x, int(y))
 
+    # ---- build-defined conveniences (the reference has none of them)
+    def fit(self, X, y):
+        """BUILD-DEFINED: predict(x_t) then update(x_t, y_t) over the rows of X in order, in one device call (VecKBRL.fit) -- the
+        dictionary, f and every prediction are bit for bit what the loop over predict / update leaves.  -> the predictions
+        [len(X)].  The cached (f, k) of predict is invalid afterwards: call predict before the next update."""
+        X = np.asarray(X, dtype=np.float64)
+        X = X.reshape(1, -1) if X.ndim == 1 else X
+        if X.shape[0] == 0:
+            return np.zeros(0, dtype=np.int32)
+        self._ensure(X[0])
+        out = self._agent.fit([(self._e, self._s)], [X], [np.asarray(y).reshape(-1)])
+        self.f = float(out['f'][0][-1])
+        return out['y_pred'][0]
+
+    def decision_function(self, X):
+        """BUILD-DEFINED: f(x) for the rows of X (VecKBRL.score), each bit for bit the f that predict(x) leaves in self.f;
+        read-only: no cached row, no tie draw, self.f untouched.  -> [len(X)] float64 (zeros while the dictionary is empty)"""
+        X = np.asarray(X, dtype=np.float64)
+        X = X.reshape(1, -1) if X.ndim == 1 else X
+        if X.shape[0] == 0:
+            return np.zeros(0)
+        self._ensure(X[0])
+        return self._agent.score([(self._e, self._s)], [X])[0][0]
+
     def get_set_size(self):
         """projectron.py:62-64: landmarks.shape[0] (the vector length while a single landmark is held)"""
         d = self._get()

@@ -7,6 +7,7 @@ struct kb_prune_state;  // kb_prune.hip
 struct kb_ref_state;    // kb_ref.hip
 struct kb_rebuild_state;  // kb_rebuild.hip
 struct kb_bridge_state;   // kb_bridge.hip
+struct kb_fit_state;      // kb_fit.hip
 
 struct kb_handle {
     kb_config cfg;
@@ -79,6 +80,7 @@ struct kb_handle {
     kb_prune_state* prune = nullptr; // kb_prune's lists and the pruned counters: NOT a saved region (kb_prune.hip)
     kb_rebuild_state* rebuild = nullptr;  // kb_fork_rebuild into this handle: its plan, result words and timing (kb_rebuild.hip)
     kb_bridge_state* bridge = nullptr;    // kb_unshare / kb_share into this handle: result words, timing and plan bytes (kb_bridge.hip)
+    kb_fit_state* fit = nullptr;          // kb_fit / kb_score on this handle: the counters and the timing of the last calls (kb_fit.hip)
     bool round_open = false;         // shared mode, host-driven rounds: proposals were scanned or applied and kb_shared_commit has not closed
                                      // the round yet -- the dictionaries are between two states of a step (kb_unshare / kb_share refuse)
     kb_ref_state* ref = nullptr;     // a by-reference handle (kb_deploy_ref): the store of shared dictionaries, the map, the groups (kb_ref.hip)
@@ -95,6 +97,7 @@ static void kb_prune_restart(kb_handle* k);  // the pruned counters start over (
 static void kb_ref_release(kb_handle* k);
 static void kb_rebuild_release(kb_handle* k);  // kb_rebuild.hip
 static void kb_bridge_release(kb_handle* k);   // kb_bridge.hip
+static void kb_fit_release(kb_handle* k);      // kb_fit.hip
 static kb_handle* kb_ref_store(kb_handle* k);
 static int kb_ref_dict(kb_handle* k, size_t task);
 static int kb_ref_select(kb_handle* k, const float* d_state);  // the scoring of launch_select: one fused kernel
@@ -468,6 +471,7 @@ extern "C" void kb_destroy(kb_handle* k) {
     kb_ref_release(k);
     kb_rebuild_release(k);
     kb_bridge_release(k);
+    kb_fit_release(k);
     if (k->h_seen) (void)hipHostFree(k->h_seen);
     if (k->h_total) (void)hipHostFree(k->h_total);
     if (k->stream) (void)hipStreamDestroy(k->stream);

@@ -1,0 +1,467 @@
+// kb_fit.hip -- the learner's own surface, batched: kb_fit teaches many learners their recorded sample sequences in one call,
+// kb_score evaluates dictionaries on query sets without writing anything.  #included by rs_api.hip after kb_bridge.hip: it uses
+// the agent handle and the Projectron routines of kb_kbrl.hip (predict_column, apply_update) and changes none of their kernels.
+//
+// kb_fit.  The sequence kb_predict(e, s, x_t); kb_update(e, s, x_t, y_t) over a learner's samples is sequentially dependent, so a
+// LEARNER IS A WORKGROUP and the parallelism is across learners: fit_kernel runs one 256-thread workgroup per listed learner,
+// persistent over the learner's samples of the launch.  Per sample it runs what the two one-sample kernels run, by the same
+// functions on the same block size: predict_column (the kernel column into the K_f row, f), the decision (an exact tie with a
+// populated dictionary draws from the learner's stream), the mistake test f y <= 0, apply_update.  Nothing in those functions
+// depends on what ran before them in the same launch but the dictionary itself, which the one-sample kernels pass from launch to
+// launch through the same global memory -- so every f, delta, coefficient and Kinv entry is bit for bit the one-by-one path's.
+// (Chip-wide rounds for ONE large dictionary, the heavy_* shape of update_control, are not used here: a dictionary of thousands
+// of landmarks is taught at the pace of one workgroup.)
+//
+// kb_score.  f of kb_predict for many points, and nothing else: no K_f row, no cache, no counter, no tie draw.  score_kernel's
+// workgroup takes one dictionary and KB_SCORE_Q of its queries, staged in LDS; thread t walks the landmarks j = t, t + 256, ...
+// in increasing j, loads a landmark's coordinates and coefficient once and feeds Q accumulators with predict_column's
+// operations in predict_column's order; each accumulator is then reduced as block_sum reduces.  A query's bits do not depend on
+// the other queries of its block.  The kernel reads dictionaries through (KbDev, KbState) of whatever handle owns the pool, so it
+// serves learning, copy-deployed, imported, by-reference (the store's pool) and shared-dictionary handles alike.
+
+#include <algorithm>
+
+namespace kb {
+
+#define KB_SCORE_Q 8       // queries per workgroup of score_kernel: 8 distances + 8 sums in registers beside rs_exp's, no scratch
+#define KB_FIT_CHUNK 256   // kb_fit's default: samples of one learner per launch
+
+struct FitArgs {
+    KbDev D;
+    KbState K;
+    const int32_t* task;       // [n]
+    const long long* first;    // [n + 1] rows of learner i, relative to the staged block
+    const double* x;           // [rows][KB_DMAX]
+    const int8_t* y;           // [rows]
+    long long from;            // this launch teaches rows first[i] + from .. first[i] + from + chunk - 1 of every learner
+    int chunk;
+    int32_t* y_pred;           // [rows] each
+    double* f;
+    int32_t* branch;
+    double* delta;
+    int32_t* m_after;
+    unsigned long long* work;  // [0..3] samples, mistakes, insertions, kernel evaluations of the call
+};
+
+__global__ __launch_bounds__(256) void fit_kernel(FitArgs A) {
+    const KbDev& D = A.D;
+    const KbState& K = A.K;
+    __shared__ Lds sm;
+    const int i = blockIdx.x;
+    const long long r0 = A.first[i] + A.from;
+    const long long r1 = A.first[i + 1] < r0 + A.chunk ? A.first[i + 1] : r0 + A.chunk;
+    if (r0 >= r1) return;
+    const int task = A.task[i], env = task / D.S, s = task - env * D.S;
+    const int dt = task;  // (per-replica dictionaries only: kb_fit refuses shared ones)
+    const uint64_t* sh = shells_of(D, K, dt);
+    const int d = D.dims[s] + 1;
+    int m = K.m[dt];
+    unsigned long long n_mist = 0, n_grow = 0, n_eval = 0;
+    double f = 0.0;
+    for (long long r = r0; r < r1; ++r) {
+        __syncthreads();  // (the previous sample's readers of sm.x are done)
+        if (threadIdx.x < KB_DMAX) sm.x[threadIdx.x] = A.x[r * KB_DMAX + threadIdx.x];
+        __syncthreads();
+        // Projectron.predict (projectron.py:32-37)
+        f = predict_column(D, K, sh, d, m, sm.x, sm);
+        int yp = 0;
+        if (m > 0) {
+            yp = f > 0.0 ? 1 : (f < 0.0 ? -1 : 0);
+            if (yp == 0) {  // (block-uniform: every thread holds the same f)
+                if (threadIdx.x == 0) sm.ired[0] = tie_draw(K, task, env, s);
+                __syncthreads();
+                yp = sm.ired[0];
+                __syncthreads();
+            }
+        } else {
+            f = 0.0;
+        }
+        n_eval += (unsigned long long)m;
+        // Projectron.update (projectron.py:39-60) on the (f, K_f) just formed
+        const int y = (int)A.y[r];
+        int branch = 0, m_new = m;
+        double delta = 0.0;
+        if (f * (double)y <= 0.0) {
+            const double t_last = sm.x[d - 1];
+            m_new = apply_update(D, K, dt, env, m, d, sm.x, t_last, grid_index(t_last, D.n_prbs), y, sm, &branch, &delta);
+            n_mist += 1;
+            if (branch == 2 && m_new > m) n_grow += 1;
+        }
+        if (threadIdx.x == 0) {
+            A.y_pred[r] = yp;
+            A.f[r] = f;
+            A.branch[r] = branch;
+            A.delta[r] = delta;
+            A.m_after[r] = m_new;
+        }
+        m = m_new;
+    }
+    if (threadIdx.x == 0) {
+        K.m[dt] = m;
+        K.f_last[task] = f;
+        K.m_last[task] = -1;   // the cache of the last kb_predict is gone: kb_update answers RS_ESTATE until a new kb_predict
+        K.kf_owner[dt] = -1;
+        const unsigned long long ns = (unsigned long long)(r1 - r0);
+        K.stats[(size_t)task * 4 + 0] += ns;
+        K.stats[(size_t)task * 4 + 1] += n_mist;
+        K.stats[(size_t)task * 4 + 2] += n_grow;
+        atomicAdd(&A.work[0], ns);
+        atomicAdd(&A.work[1], n_mist);
+        atomicAdd(&A.work[2], n_grow);
+        atomicAdd(&A.work[3], n_eval);
+    }
+}
+
+// a workgroup of score_kernel: cnt <= KB_SCORE_Q consecutive queries (rows q0 .. of the staged block) against one dictionary
+struct ScoreBlock {
+    long long q0;
+    int32_t dict, cnt;
+};
+
+struct ScoreArgs {
+    KbDev D;   // of the handle whose pool holds the dictionaries (a by-reference handle: its store)
+    KbState K;
+    const ScoreBlock* blk;     // [gridDim.x]
+    const double* x;           // [rows][KB_DMAX]
+    double* f;                 // [rows]
+    int32_t* y_pred;           // [rows]
+    unsigned long long* work;  // [0] kernel evaluations of the call
+};
+
+__global__ __launch_bounds__(256) void score_kernel(ScoreArgs A) {
+    const KbDev& D = A.D;
+    const KbState& K = A.K;
+    __shared__ double xs[KB_SCORE_Q][KB_DMAX];
+    __shared__ double red[KB_SCORE_Q][4];
+    __shared__ double k1[KB_SCORE_Q];  // the kernel value of the only landmark (m == 1), as the K_f row would hold it
+    const ScoreBlock B = A.blk[blockIdx.x];
+    const int dict = B.dict, cnt = B.cnt;
+    const int s = dict % D.S, d = D.dims[s] + 1;
+    const uint64_t* sh = shells_of(D, K, dict);
+    const int m = K.m[dict];
+    if (threadIdx.x < KB_SCORE_Q * KB_DMAX) {
+        const int u = threadIdx.x / KB_DMAX, c = threadIdx.x - u * KB_DMAX;
+        xs[u][c] = u < cnt ? A.x[(B.q0 + u) * KB_DMAX + c] : 0.0;
+    }
+    __syncthreads();
+    double acc[KB_SCORE_Q];
+#pragma unroll
+    for (int u = 0; u < KB_SCORE_Q; ++u) acc[u] = 0.0;
+    for (int j = threadIdx.x; j < m; j += 256) {
+        const double* P = vec_page(K, sh, j >> 6);
+        const int l = j & 63;
+        const double co = P[KB_ROW_CO * KB_CH + l];
+        double dist[KB_SCORE_Q];
+#pragma unroll
+        for (int u = 0; u < KB_SCORE_Q; ++u) dist[u] = 0.0;
+        for (int q = 0; q < d; ++q) {
+            const double v = P[q * KB_CH + l];
+#pragma unroll
+            for (int u = 0; u < KB_SCORE_Q; ++u) {
+                const double t = v - xs[u][q];
+                dist[u] += t * t;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < KB_SCORE_Q; ++u) {
+            if (u < cnt) {  // (block-uniform)
+                double k = rs_exp(-D.gamma * dist[u]);
+                if (m == 1) {
+                    k = (double)(float)k;
+                    k1[u] = k;  // (thread 0 alone is here)
+                }
+                acc[u] += k * co;
+            }
+        }
+    }
+    // block_sum, per query: the butterfly per wave, the four wave totals in order
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int u = 0; u < KB_SCORE_Q; ++u) {
+        double v = acc[u];
+        for (int dd = 32; dd >= 1; dd >>= 1) v += __shfl_xor(v, dd);
+        if (lane == 0) red[u][wv] = v;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < cnt) {
+        const int u = threadIdx.x;
+        double f = 0.0;
+        for (int w = 0; w < 4; ++w) f += red[u][w];
+        if (m == 1) f = (double)(float)((float)k1[u] * (float)*vec_at(K, sh, KB_ROW_CO, 0));
+        if (m == 0) f = 0.0;
+        A.f[B.q0 + u] = f;
+        A.y_pred[B.q0 + u] = m > 0 ? (f > 0.0 ? 1 : (f < 0.0 ? -1 : 0)) : 0;
+    }
+    if (threadIdx.x == 0) atomicAdd(&A.work[0], (unsigned long long)m * (unsigned long long)cnt);
+}
+
+}  // namespace kb
+
+// what kb_fit / kb_score keep on the handle: the counters of the last calls and their kernel timing
+struct kb_fit_state {
+    unsigned long long* d_work = nullptr;  // [8]: [0..3] the last kb_fit's samples, mistakes, insertions, kernel evaluations; [4] the last kb_score's
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    EventSpans fit_spans, score_spans;     // a pair per launch of the last call, when kernel timing was on at the call
+    double fit_ms = 0.0, score_ms = 0.0;   // their sums, once drained (kb_fit_time_ms)
+};
+
+static void kb_fit_release(kb_handle* k) {
+    kb_fit_state* p = k->fit;
+    if (!p) return;
+    if (p->d_work) (void)hipFree(p->d_work);
+    if (p->ev_in) (void)hipEventDestroy(p->ev_in);
+    if (p->ev_out) (void)hipEventDestroy(p->ev_out);
+    p->fit_spans.release();
+    p->score_spans.release();
+    delete p;
+    k->fit = nullptr;
+}
+
+static int kb_fit_prepare(kb_handle* k) {
+    if (k->fit) return RS_OK;
+    kb_fit_state* p = new kb_fit_state();
+    k->fit = p;  // (kb_destroy frees whatever was allocated)
+    HIPCHK(k, hipMalloc((void**)&p->d_work, sizeof(unsigned long long) * 8));
+    HIPCHK(k, hipMemsetAsync(p->d_work, 0, sizeof(unsigned long long) * 8, k->stream));
+    return RS_OK;
+}
+
+// one device block for a call's staged arrays, released when the call returns
+struct FitStage {
+    char* base = nullptr;
+    size_t used = 0;
+    ~FitStage() {
+        if (base) (void)hipFree(base);
+    }
+    static size_t pad(size_t b) { return (b + 255) & ~(size_t)255; }
+    template <class Tp>
+    Tp* take(size_t n) {
+        Tp* p = (Tp*)(base + used);
+        used += pad(sizeof(Tp) * (n ? n : 1));
+        return p;
+    }
+};
+
+// the checks kb_fit and kb_score share: the sample ranges.  *rows = first[n] - first[0]
+static int kb_fit_ranges(kb_handle* k, const char* who, const int64_t* first, int32_t n, int64_t* rows) {
+    if (first[0] < 0) {
+        k->err = std::string(who) + ": first[0] is negative";
+        return RS_EINVAL;
+    }
+    for (int32_t i = 0; i < n; ++i)
+        if (first[i + 1] < first[i]) {
+            k->err = std::string(who) + ": first[] must not decrease (first[" + std::to_string(i + 1) + "] < first[" + std::to_string(i) + "])";
+            return RS_EINVAL;
+        }
+    *rows = first[n] - first[0];
+    return RS_OK;
+}
+
+extern "C" int kb_fit(kb_handle* k, const int32_t* task, int32_t n, const int64_t* first, const double* x, const int8_t* y,
+                      int32_t chunk, int32_t* y_pred, double* f, int32_t* branch, double* delta, int32_t* m_after) {
+    if (!k) return RS_EINVAL;
+    if (!k->is_reset) {
+        k->err = "kb_fit: call kb_reset first";
+        return RS_ESTATE;
+    }
+    if (k->ref) {
+        k->err = "kb_fit: a by-reference handle (kb_deploy_ref) shares read-only dictionaries: it cannot learn";
+        return RS_ESTATE;
+    }
+    if (k->frozen) {
+        k->err = "kb_fit: an inference-only handle (kb_deploy, kb_import_agents) cannot learn: it holds no Kinv";
+        return RS_ESTATE;
+    }
+    if (k->D.shared) {
+        k->err = "kb_fit: shared-dictionary handles are not supported: several learners map to one dictionary";
+        return RS_ESTATE;
+    }
+    if (n < 0 || chunk < 0 || (n > 0 && (!task || !first))) {
+        k->err = "kb_fit: n or chunk is negative, or task / first is NULL";
+        return RS_EINVAL;
+    }
+    if (n == 0) return RS_OK;
+    std::vector<char> seen((size_t)k->T, 0);
+    for (int32_t i = 0; i < n; ++i) {
+        if (task[i] < 0 || task[i] >= k->T) {
+            k->err = "kb_fit: task[" + std::to_string(i) + "] = " + std::to_string(task[i]) + " names no learner (0 .. " + std::to_string(k->T - 1) + ")";
+            return RS_EINVAL;
+        }
+        if (seen[(size_t)task[i]]) {
+            k->err = "kb_fit: learner " + std::to_string(task[i]) + " is listed twice: a learner's samples form ONE sequence";
+            return RS_EINVAL;
+        }
+        seen[(size_t)task[i]] = 1;
+    }
+    int64_t rows = 0;
+    int rc = kb_fit_ranges(k, "kb_fit", first, n, &rows);
+    if (rc != RS_OK) return rc;
+    if (rows == 0) return RS_OK;
+    if (!x || !y) {
+        k->err = "kb_fit: x or y is NULL";
+        return RS_EINVAL;
+    }
+    const int64_t base = first[0];
+    int64_t longest = 0;
+    for (int32_t i = 0; i < n; ++i) longest = std::max<int64_t>(longest, first[i + 1] - first[i]);
+    for (int64_t r = 0; r < rows; ++r)
+        if (y[base + r] != 1 && y[base + r] != -1) {
+            k->err = "kb_fit: y[" + std::to_string(base + r) + "] = " + std::to_string((int)y[base + r]) + " is neither +1 nor -1";
+            return RS_EINVAL;
+        }
+    if (chunk == 0) chunk = KB_FIT_CHUNK;
+    HIPCHK(k, hipSetDevice(k->device));
+    if ((rc = kb_fit_prepare(k)) != RS_OK) return rc;
+    kb_fit_state* p = k->fit;
+    k->gemm_fresh = false;
+    std::vector<long long> rel((size_t)n + 1);
+    for (int32_t i = 0; i <= n; ++i) rel[(size_t)i] = (long long)(first[i] - base);
+    const size_t R = (size_t)rows;
+    FitStage st;
+    const size_t bytes = FitStage::pad(sizeof(int32_t) * (size_t)n) + FitStage::pad(sizeof(long long) * ((size_t)n + 1)) +
+                         FitStage::pad(sizeof(double) * KB_DMAX * R) + FitStage::pad(R) + 3 * FitStage::pad(sizeof(int32_t) * R) +
+                         2 * FitStage::pad(sizeof(double) * R);
+    HIPCHK(k, hipMalloc((void**)&st.base, bytes));
+    kb::FitArgs a;
+    memset(&a, 0, sizeof a);
+    a.D = k->D;
+    a.K = k->K;
+    int32_t* d_task = st.take<int32_t>((size_t)n);
+    long long* d_first = st.take<long long>((size_t)n + 1);
+    double* d_x = st.take<double>(KB_DMAX * R);
+    int8_t* d_y = st.take<int8_t>(R);
+    a.y_pred = st.take<int32_t>(R);
+    a.branch = st.take<int32_t>(R);
+    a.m_after = st.take<int32_t>(R);
+    a.f = st.take<double>(R);
+    a.delta = st.take<double>(R);
+    a.task = d_task;
+    a.first = d_first;
+    a.x = d_x;
+    a.y = d_y;
+    a.chunk = chunk;
+    a.work = p->d_work;
+    // behind whatever is queued on either of the handle's streams
+    if (k->side && (rc = stream_after(k, &p->ev_in, k->side, k->stream)) != RS_OK) return rc;
+    HIPCHK(k, hipMemcpyAsync(d_task, task, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, k->stream));
+    HIPCHK(k, hipMemcpyAsync(d_first, rel.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, k->stream));
+    HIPCHK(k, hipMemcpyAsync(d_x, x + (size_t)base * KB_DMAX, sizeof(double) * KB_DMAX * R, hipMemcpyHostToDevice, k->stream));
+    HIPCHK(k, hipMemcpyAsync(d_y, y + base, R, hipMemcpyHostToDevice, k->stream));
+    HIPCHK(k, hipMemsetAsync(p->d_work, 0, sizeof(unsigned long long) * 4, k->stream));
+    p->fit_spans.on = k->spans.on;
+    p->fit_spans.reset();
+    p->fit_ms = 0.0;
+    for (int64_t from = 0; from < longest; from += chunk) {  // (no launch runs longer than `chunk` samples of one learner)
+        a.from = (long long)from;
+        hipEvent_t e;
+        HIPCHK(k, p->fit_spans.begin(k->stream, 0, &e));
+        hipLaunchKernelGGL(kb::fit_kernel, dim3((unsigned)n), dim3(256), 0, k->stream, a);
+        if (e) HIPCHK(k, hipEventRecord(e, k->stream));
+    }
+    HIPCHK(k, hipGetLastError());
+    if (y_pred) HIPCHK(k, hipMemcpyAsync(y_pred + base, a.y_pred, sizeof(int32_t) * R, hipMemcpyDeviceToHost, k->stream));
+    if (f) HIPCHK(k, hipMemcpyAsync(f + base, a.f, sizeof(double) * R, hipMemcpyDeviceToHost, k->stream));
+    if (branch) HIPCHK(k, hipMemcpyAsync(branch + base, a.branch, sizeof(int32_t) * R, hipMemcpyDeviceToHost, k->stream));
+    if (delta) HIPCHK(k, hipMemcpyAsync(delta + base, a.delta, sizeof(double) * R, hipMemcpyDeviceToHost, k->stream));
+    if (m_after) HIPCHK(k, hipMemcpyAsync(m_after + base, a.m_after, sizeof(int32_t) * R, hipMemcpyDeviceToHost, k->stream));
+    if (k->side && (rc = stream_after(k, &p->ev_out, k->stream, k->side)) != RS_OK) return rc;
+    return kb_check(k);  // (waits for the stream)
+}
+
+extern "C" int kb_score(kb_handle* k, const int32_t* task, int32_t n, const int64_t* first, const double* x, double* f,
+                        int32_t* y_pred) {
+    if (!k) return RS_EINVAL;
+    if (!k->is_reset) {
+        k->err = "kb_score: call kb_reset first";
+        return RS_ESTATE;
+    }
+    if (n < 0 || (n > 0 && (!task || !first))) {
+        k->err = "kb_score: n is negative, or task / first is NULL";
+        return RS_EINVAL;
+    }
+    if (n == 0) return RS_OK;
+    for (int32_t i = 0; i < n; ++i)
+        if (task[i] < 0 || task[i] >= k->T) {
+            k->err = "kb_score: task[" + std::to_string(i) + "] = " + std::to_string(task[i]) + " names no learner (0 .. " + std::to_string(k->T - 1) + ")";
+            return RS_EINVAL;
+        }
+    int64_t rows = 0;
+    int rc = kb_fit_ranges(k, "kb_score", first, n, &rows);
+    if (rc != RS_OK) return rc;
+    if (rows == 0) return RS_OK;
+    if (!x || !f) {
+        k->err = "kb_score: x or f is NULL";
+        return RS_EINVAL;
+    }
+    const int64_t base = first[0];
+    kb_handle* own = k->ref ? kb_ref_store(k) : k;  // the handle whose pool holds the dictionaries
+    // the prefix table of query blocks: a learner's queries in blocks of KB_SCORE_Q, the last one ragged
+    std::vector<kb::ScoreBlock> blocks;
+    for (int32_t i = 0; i < n; ++i) {
+        const int dict = k->ref ? kb_ref_dict(k, (size_t)task[i]) : (k->D.shared ? task[i] % k->cfg.n_slices : task[i]);
+        for (int64_t q = first[i]; q < first[i + 1]; q += KB_SCORE_Q) {
+            kb::ScoreBlock b;
+            b.q0 = (long long)(q - base);
+            b.dict = dict;
+            b.cnt = (int32_t)std::min<int64_t>(KB_SCORE_Q, first[i + 1] - q);
+            blocks.push_back(b);
+        }
+    }
+    HIPCHK(k, hipSetDevice(k->device));
+    if ((rc = kb_fit_prepare(k)) != RS_OK) return rc;
+    kb_fit_state* p = k->fit;
+    const size_t R = (size_t)rows, NB = blocks.size();
+    FitStage st;
+    const size_t bytes = FitStage::pad(sizeof(kb::ScoreBlock) * NB) + FitStage::pad(sizeof(double) * KB_DMAX * R) +
+                         FitStage::pad(sizeof(double) * R) + FitStage::pad(sizeof(int32_t) * R);
+    HIPCHK(k, hipMalloc((void**)&st.base, bytes));
+    kb::ScoreArgs a;
+    memset(&a, 0, sizeof a);
+    a.D = own->D;
+    a.K = own->K;
+    kb::ScoreBlock* d_blk = st.take<kb::ScoreBlock>(NB);
+    double* d_x = st.take<double>(KB_DMAX * R);
+    a.f = st.take<double>(R);
+    a.y_pred = st.take<int32_t>(R);
+    a.blk = d_blk;
+    a.x = d_x;
+    a.work = p->d_work + 4;
+    if (k->side && (rc = stream_after(k, &p->ev_in, k->side, k->stream)) != RS_OK) return rc;
+    HIPCHK(k, hipMemcpyAsync(d_blk, blocks.data(), sizeof(kb::ScoreBlock) * NB, hipMemcpyHostToDevice, k->stream));
+    HIPCHK(k, hipMemcpyAsync(d_x, x + (size_t)base * KB_DMAX, sizeof(double) * KB_DMAX * R, hipMemcpyHostToDevice, k->stream));
+    HIPCHK(k, hipMemsetAsync(p->d_work + 4, 0, sizeof(unsigned long long), k->stream));
+    p->score_spans.on = k->spans.on;
+    p->score_spans.reset();
+    p->score_ms = 0.0;
+    hipEvent_t e;
+    HIPCHK(k, p->score_spans.begin(k->stream, 1, &e));
+    hipLaunchKernelGGL(kb::score_kernel, dim3((unsigned)NB), dim3(256), 0, k->stream, a);
+    if (e) HIPCHK(k, hipEventRecord(e, k->stream));
+    HIPCHK(k, hipGetLastError());
+    HIPCHK(k, hipMemcpyAsync(f + base, a.f, sizeof(double) * R, hipMemcpyDeviceToHost, k->stream));
+    if (y_pred) HIPCHK(k, hipMemcpyAsync(y_pred + base, a.y_pred, sizeof(int32_t) * R, hipMemcpyDeviceToHost, k->stream));
+    HIPCHK(k, hipStreamSynchronize(k->stream));
+    return RS_OK;
+}
+
+extern "C" int kb_fit_time_ms(kb_handle* k, double ms[2], uint64_t work[4]) {
+    if (!k || !ms || !work) return RS_EINVAL;
+    ms[0] = ms[1] = 0.0;
+    for (int q = 0; q < 4; ++q) work[q] = 0;
+    kb_fit_state* p = k->fit;
+    if (!p) return RS_OK;
+    HIPCHK(k, hipSetDevice(k->device));
+    HIPCHK(k, hipStreamSynchronize(k->stream));
+    HIPCHK(k, p->fit_spans.drain([&](int, double t) { p->fit_ms += t; }));
+    HIPCHK(k, p->score_spans.drain([&](int, double t) { p->score_ms += t; }));
+    ms[0] = p->fit_ms;
+    ms[1] = p->score_ms;
+    unsigned long long w[8];
+    HIPCHK(k, hipMemcpyAsync(w, p->d_work, sizeof w, hipMemcpyDeviceToHost, k->stream));
+    HIPCHK(k, hipStreamSynchronize(k->stream));
+    work[0] = w[0];
+    work[1] = w[1];
+    work[2] = w[2];
+    work[3] = w[3] + w[4];
+    return RS_OK;
+}

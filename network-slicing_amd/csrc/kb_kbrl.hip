@@ -3243,22 +3243,19 @@ struct OneArgs {
     double* out;  // [4]: y_pred, f, branch, delta
 };
 
-__global__ __launch_bounds__(256) void predict_one_kernel(OneArgs A) {
-    const KbDev& D = A.D;
-    const KbState& K = A.K;
-    __shared__ Lds sm;
-    const int task = A.task, env = task / D.S, s = task - env * D.S;
-    const int dt = dict_of(D, task);
-    const uint64_t* sh = shells_of(D, K, dt);
-    const int d = D.dims[s] + 1;
-    const int m = K.m[dt];
+// GaussianKernel.predict's sum (kernel.py:13-28) by a 256-thread block: the kernel column of x into the K_f row, f = K_f . coeff as
+// per-thread sums over j = t, t + 256, ... in increasing j and block_sum over them; float32 while one landmark is held.  Every
+// thread returns f.  kb_predict's kernel and kb_fit's (kb_fit.hip) both call it; kb_score's kernel forms the same sums, Q queries
+// at a time, and stores nothing (a change here is made there too).
+__device__ __forceinline__ double predict_column(const KbDev& D, const KbState& K, const uint64_t* sh, int d, int m, const double* x,
+                                                 Lds& sm) {
     double p = 0.0;
     for (int j = threadIdx.x; j < m; j += blockDim.x) {
         double* P = vec_page(K, sh, j >> 6);
         const int l = j & 63;
         double dist = 0.0;
         for (int q = 0; q < d; ++q) {
-            double t = P[q * KB_CH + l] - A.x[q];
+            double t = P[q * KB_CH + l] - x[q];
             dist += t * t;
         }
         double k = rs_exp(-D.gamma * dist);
@@ -3268,6 +3265,19 @@ __global__ __launch_bounds__(256) void predict_one_kernel(OneArgs A) {
     }
     double f = block_sum(p, sm);
     if (m == 1) f = (double)(float)((float)*vec_at(K, sh, KB_ROW_KF, 0) * (float)*vec_at(K, sh, KB_ROW_CO, 0));
+    return f;
+}
+
+__global__ __launch_bounds__(256) void predict_one_kernel(OneArgs A) {
+    const KbDev& D = A.D;
+    const KbState& K = A.K;
+    __shared__ Lds sm;
+    const int task = A.task, env = task / D.S, s = task - env * D.S;
+    const int dt = dict_of(D, task);
+    const uint64_t* sh = shells_of(D, K, dt);
+    const int d = D.dims[s] + 1;
+    const int m = K.m[dt];
+    double f = predict_column(D, K, sh, d, m, A.x, sm);
     if (threadIdx.x == 0) {
         int y = 0;
         if (m > 0) {

@@ -24,6 +24,7 @@ KB_EXPORTS = (
     'kb_export_bytes', 'kb_export_agents', 'kb_agents_info', 'kb_import_agents', 'kb_agents_kernel_times',
     'kb_fork_rebuild', 'kb_get_rebuild', 'kb_rebuild_time_ms',
     'kb_unshare', 'kb_share', 'kb_bridge_time_ms',
+    'kb_fit', 'kb_score', 'kb_fit_time_ms',
 )
 
 EXPORTS = (
@@ -207,6 +208,9 @@ def load(dev=None):
     L.kb_get_pruned.argtypes = [vp, i64p]
     L.kb_prune_time_ms.argtypes = [vp, dp, i64p]
     L.kb_get_prune_work.argtypes = [vp, up]
+    L.kb_fit.argtypes = [vp, ip, C.c_int32, i64p, dp, C.POINTER(C.c_int8), C.c_int32, ip, dp, ip, dp, ip]
+    L.kb_score.argtypes = [vp, ip, C.c_int32, i64p, dp, dp, ip]
+    L.kb_fit_time_ms.argtypes = [vp, dp, up]
     for name in EXPORTS:
         if name not in ('rs_last_error', 'rs_destroy', 'kb_last_error', 'kb_destroy'):
             getattr(L, name).restype = C.c_int

@@ -50,6 +50,42 @@ def shared_pool_bytes(sizes):
     return POOL_PREAMBLE_BYTES + int((VEC_PAGE_BYTES * nsh + 32768 * nsh * nsh).sum())
 
 
+def augmented_samples(state, action, labels, dims, n_prbs):
+    """the per-learner sample lists of the reference's sample augmentation (kbrl_control.py:103-112) for a log of control steps,
+    on the host (pure numpy): state [steps, sum(dims)], action [steps, S], labels [steps, S] (+1 fulfilled / -1 not) ->
+    (X, y), lists over the S learners of arrays [n_s, dims[s] + 1] float64 and [n_s] int8.  Step by step in log order, a step
+    with label +1 gives the allocations action .. n_prbs (the same or more PRBs would have fulfilled too), one with -1 the
+    allocations 0 .. action, in that order; a sample is (the learner's state variables, allocation / n_prbs) with the step's
+    label.  The lists feed VecKBRL.fit, whatever produced the log -- the reference, a deployed fleet, the clairvoyant baseline.
+    Limits: fit forms f in predict's summation order, update_control through the binned / MFMA scoring chain, so the two take
+    the same decisions except where f is within rounding of zero -- bit-equality with update_control is not claimed; and the
+    stop of the augmentation at a full dictionary (build-defined in the oracle) is not reproduced."""
+    state = np.asarray(state, dtype=np.float64)
+    state = state.reshape(-1, int(sum(dims)))
+    steps = state.shape[0]
+    action = np.asarray(action, dtype=np.int64).reshape(steps, len(dims))
+    labels = np.asarray(labels, dtype=np.int64).reshape(steps, len(dims))
+    if ((labels != 1) & (labels != -1)).any():
+        raise ValueError('augmented_samples: labels must be +1 or -1')
+    if (action < 0).any() or (action > n_prbs).any():
+        raise ValueError('augmented_samples: actions must lie in 0 .. n_prbs')
+    X, Y, off = [], [], 0
+    for s, d in enumerate(dims):
+        xs, ys = [], []
+        for t in range(steps):
+            a, lab = int(action[t, s]), int(labels[t, s])
+            alloc = np.arange(a, n_prbs + 1) if lab == 1 else np.arange(0, a + 1)
+            x = np.empty((alloc.size, d + 1))
+            x[:, :d] = state[t, off:off + d]
+            x[:, d] = alloc / n_prbs
+            xs.append(x)
+            ys.append(np.full(alloc.size, lab, dtype=np.int8))
+        X.append(np.concatenate(xs) if xs else np.zeros((0, d + 1)))
+        Y.append(np.concatenate(ys) if ys else np.zeros(0, dtype=np.int8))
+        off += d
+    return X, Y
+
+
 class VecKBRL:
     frozen = False   # True on the inference-only objects deploy() returns
     by_reference = False   # True on those deploy(index, by_reference=True) returns: dictionaries stored once per distinct agent
@@ -163,6 +199,77 @@ class VecKBRL:
         br, dl = C.c_int32(), C.c_double()
         self._check(self.L.kb_update(self.h, e, s, x.ctypes.data_as(_dp), int(y), C.byref(br), C.byref(dl)))
         return br.value, dl.value
+
+    def _pack_rows(self, learners, X, who):
+        """(task [n] int32, first [n + 1] int64, rows [first[n], 16] float64) of per-learner arrays [n_i, dims[s] + 1]"""
+        learners = [(int(e), int(s)) for e, s in learners]
+        if len(X) != len(learners):
+            raise ValueError('%s: %d learners but %d arrays' % (who, len(learners), len(X)))
+        for e, s in learners:
+            if not (0 <= e < self.n_envs and 0 <= s < self.S):
+                raise ValueError('%s: (%d, %d) names no learner' % (who, e, s))
+        task = np.array([e * self.S + s for e, s in learners], dtype=np.int32).reshape(-1)
+        first = np.zeros(len(learners) + 1, dtype=np.int64)
+        arrs = []
+        for i, ((e, s), x) in enumerate(zip(learners, X)):
+            d = self.dims[s] + 1
+            x = np.asarray(x, dtype=np.float64)
+            x = x.reshape(-1, d) if x.size else np.zeros((0, d))
+            arrs.append(x)
+            first[i + 1] = first[i] + x.shape[0]
+        rows = np.zeros((int(first[-1]), 16))
+        for i, ((e, s), x) in enumerate(zip(learners, arrs)):
+            rows[first[i]:first[i + 1], :x.shape[1]] = x
+        return task, first, rows
+
+    def fit(self, learners, X, y, chunk=0):
+        """teacher-forced online learning of many learners in one call (kb_fit; build-defined): learners = [(e, s), ...] all
+        distinct, X[i] = [n_i, dims[s] + 1] samples of learner i in order, y[i] = [n_i] labels +1 / -1.  For every learner and
+        sample in order: predict(x_t), then update(x_t, y_t) -- bit for bit what the one-by-one predict / update calls leave,
+        one workgroup per learner on the device.  chunk: most samples of one learner per launch (0: the default); no result
+        depends on it.  -> dict of per-learner lists of arrays: y_pred, f, branch (0 none, 1 projection, 2 grew), delta and
+        m (the dictionary's size after the sample).  The cached predict of the touched learners is invalid afterwards."""
+        task, first, rows = self._pack_rows(learners, X, 'fit')
+        if len(y) != len(task):
+            raise ValueError('fit: %d learners but %d label arrays' % (len(task), len(y)))
+        lab = np.zeros(int(first[-1]), dtype=np.int8)
+        for i, yi in enumerate(y):
+            yi = np.asarray(yi).reshape(-1)
+            if yi.size != first[i + 1] - first[i]:
+                raise ValueError('fit: learner %d has %d samples but %d labels' % (i, first[i + 1] - first[i], yi.size))
+            if ((yi != 1) & (yi != -1)).any():
+                raise ValueError('fit: labels must be +1 or -1')
+            lab[first[i]:first[i + 1]] = yi
+        R = int(first[-1])
+        yp, br, ma = (np.zeros(R, dtype=np.int32) for _ in range(3))
+        f, dl = np.zeros(R), np.zeros(R)
+        i64p, i8p = C.POINTER(C.c_int64), C.POINTER(C.c_int8)
+        self._check(self.L.kb_fit(self.h, task.ctypes.data_as(_ip), int(task.size), first.ctypes.data_as(i64p),
+                                  rows.ctypes.data_as(_dp), lab.ctypes.data_as(i8p), int(chunk), yp.ctypes.data_as(_ip),
+                                  f.ctypes.data_as(_dp), br.ctypes.data_as(_ip), dl.ctypes.data_as(_dp), ma.ctypes.data_as(_ip)))
+        cut = lambda a: [a[first[i]:first[i + 1]] for i in range(task.size)]
+        return dict(y_pred=cut(yp), f=cut(f), branch=cut(br), delta=cut(dl), m=cut(ma))
+
+    def score(self, learners, X):
+        """read-only scoring of query sets (kb_score; build-defined): learners = [(e, s), ...] (repeats allowed), X[i] =
+        [n_i, dims[s] + 1] points -> (f, y_pred), lists of arrays [n_i]: f is bit for bit what predict(e, s, x) returns, y_pred
+        its sign and 0 on an exact tie or an empty dictionary (no draw is taken).  Nothing in the handle changes -- no cached
+        row, counter or tie stream -- so it works on learning, deployed (copy and by reference), imported and shared handles."""
+        task, first, rows = self._pack_rows(learners, X, 'score')
+        R = int(first[-1])
+        f, yp = np.zeros(R), np.zeros(R, dtype=np.int32)
+        self._check(self.L.kb_score(self.h, task.ctypes.data_as(_ip), int(task.size), first.ctypes.data_as(C.POINTER(C.c_int64)),
+                                    rows.ctypes.data_as(_dp), f.ctypes.data_as(_dp), yp.ctypes.data_as(_ip)))
+        return ([f[first[i]:first[i + 1]] for i in range(task.size)], [yp[first[i]:first[i + 1]] for i in range(task.size)])
+
+    def fit_time_ms(self):
+        """of the last fit / score on this handle (kb_fit_time_ms): dict(fit_ms, score_ms = device time of their launches when
+        set_kernel_timing was on at the call, else 0; samples, mistakes, insertions of the last fit; kernel_evals = landmarks x
+        samples of the last fit plus landmarks x queries of the last score)"""
+        ms = (C.c_double * 2)()
+        w = (C.c_uint64 * 4)()
+        self._check(self.L.kb_fit_time_ms(self.h, ms, w))
+        return dict(fit_ms=ms[0], score_ms=ms[1], samples=int(w[0]), mistakes=int(w[1]), insertions=int(w[2]), kernel_evals=int(w[3]))
 
     def learner(self, e, s, with_kinv=False):
         m = C.c_int32()
@@ -526,6 +633,12 @@ class SharedVecKBRL(VecKBRL):
         self.budget, self.max_rounds = budget, max_rounds
         self.exchange = exchange
         self.rounds_last = 0
+
+    def fit(self, learners, X, y, chunk=0):
+        """refused: the replicas' learners map to ONE dictionary per slice, so their sample lists are not independent sequences
+        (kb_fit answers RS_ESTATE); score() works.  Teach a per-replica VecKBRL and to_shared() it instead."""
+        raise _lib.RanSliceError(_lib.RS_ESTATE, 'fit: shared-dictionary handles are not supported: several learners map to one '
+                                 'dictionary (fit a per-replica VecKBRL, then to_shared)')
 
     @staticmethod
     def unique_id():

@@ -26,6 +26,9 @@ REBUILD_SCRATCH = {'rebuild_sizes_kernel': 0, 'rebuild_pages_kernel': 0, 'rebuil
 BRIDGE = ['unshare_count_kernel', 'unshare_tables_kernel', 'unshare_shells_kernel', 'share_tables_kernel', 'share_shells_kernel']
 # kb_fork's own kernels (kb_fork.hip), whose gather helpers and work line the bridge's and kb_fork_rebuild's call: the same
 FORK = ['fork_count_kernel', 'fork_scan_kernel', 'fork_tables_kernel', 'fork_shells_kernel']
+# kb_fit / kb_score (kb_fit.hip): reported; the scoring kernel is held to no scratch at all (KB_SCORE_Q was chosen by that), the
+# fitting kernel -- predict_column and apply_update inlined into one persistent loop -- to what the build shows: none either
+FIT_SCRATCH = {'fit_kernel': 0, 'score_kernel': 0}
 PRODUCTION = ["embb_step_kernelILi16ELb0ELb0ELb1E", "embb_step_kernelILi16ELb0ELb1ELb1E"]   # <16, false, plain | BLOCK, FDIV>
 PLAIN = PRODUCTION[0]          # the instance bench.py's headline runs
 STEP_KERNEL = 'embb_step_kernelIL'
@@ -132,8 +135,8 @@ def check(path=LOG):
         print('%s: VGPRs %s, scratch %s B/lane, occupancy %s' % (key, r.get('VGPRs'), r.get('ScratchSize'), r.get('Occupancy')))
         if r.get('ScratchSize', 0) > limit:
             bad.append('%s spills %d B/lane (> %d)' % (key, r['ScratchSize'], limit))
-    for key, limit in REBUILD_SCRATCH.items():
-        hit = [k for k in res if key in k]
+    for key, limit in list(REBUILD_SCRATCH.items()) + list(FIT_SCRATCH.items()):
+        hit = [k for k in res if re.search(r'\d' + key, k)] if key in FIT_SCRATCH else [k for k in res if key in k]
         if not hit:
             bad.append('%s: not found in %s' % (key, path))
             continue
