@@ -690,6 +690,26 @@ int kb_fit(kb_handle* k, const int32_t* task, int32_t n, const int64_t* first, c
 int kb_score(kb_handle* k, const int32_t* task, int32_t n, const int64_t* first, const double* x, double* f, int32_t* y_pred);
 int kb_fit_time_ms(kb_handle* k, double ms[2], uint64_t work[4]);
 
+/* ---- the update rule of the learner's own surface.  KB_ALG_PROJECTRON (the default): Projectron.update
+ * (projectron.py:39-60), an update on a mistake f y <= 0 only.  KB_ALG_PROJECTRON_PLUS: ProjectronPlus.update (projectron.py:
+ * 71-107, Projectron++): a mistake is handled as Projectron handles it, and a sample classified correctly inside the margin,
+ * 0 < f y < 1, gives a scaled projection coeff += (alpha y) d* when loss - delta / eta > 0 (loss = 1 - f y; alpha = min(min(loss /
+ * norm, 1), 2 (loss - delta / eta) / norm), norm = max(1 - delta, 0)) -- it never adds a landmark -- and nothing otherwise.
+ * kb_update and kb_fit then report branch 3 (margin update: coefficients changed, version bumped) and 4 (margin test, nothing
+ * written) beside 0, 1, 2, and delta for branches 1-4; a "mistake" of the per-learner statistics and of kb_fit_time_ms's work[1]
+ * is a sample that changed the dictionary (branches 1-3).
+ * The algorithm is a property of the HANDLE -- how its next kb_update / kb_fit are done --, not of its dictionaries: it is not
+ * part of kb_save_state blobs or agent files, and kb_fork, kb_deploy, kb_import_agents, kb_unshare and kb_share do not carry it
+ * over (the destination keeps its own).  While a handle is in Projectron++ mode the closed control loop does not learn through
+ * it: kb_update_control, and kb_step_resident / kb_run_resident with learning on, answer RS_ESTATE (kb_set_learning(k, 0), or
+ * kb_set_algorithm back, lifts that); everything that only reads dictionaries or moves them works as before.
+ * kb_set_algorithm: RS_EINVAL for an unknown value; RS_ESTATE for KB_ALG_PROJECTRON_PLUS on an inference-only, a by-reference
+ * or a shared-dictionary handle (they do not learn through kb_update / kb_fit). */
+#define KB_ALG_PROJECTRON 0
+#define KB_ALG_PROJECTRON_PLUS 1
+int kb_set_algorithm(kb_handle* k, int32_t alg);
+int kb_get_algorithm(kb_handle* k, int32_t* alg);
+
 #ifdef __cplusplus
 }
 #endif

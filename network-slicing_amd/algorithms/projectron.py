@@ -1,4 +1,4 @@
-"""SVvariable / Projectron with the reference's surface (reference algorithms/projectron.py:3-64).
+"""SVvariable / Projectron / ProjectronPlus with the reference's surface (reference algorithms/projectron.py:3-107).
 
 The dictionary (landmarks, coefficients, K^-1) lives on the GPU inside a kb_* agent; predict(x) and
 update(x, y) are kb_predict / kb_update calls.  A Projectron created on its own owns a private
@@ -29,6 +29,8 @@ class SVvariable:
 
 
 class Projectron:
+    ALGORITHM = 'projectron'   # the update rule of the private agent (VecKBRL(algorithm=...))
+
     def __init__(self, kernel, eta=0.1, capacity=4096):
         self.kernel = kernel
         self.sv = kernel.sv
@@ -51,7 +53,7 @@ class Projectron:
     def _ensure(self, x):
         if self._agent is None:
             self._agent = VecKBRL(1, [len(x) - 1], 200, gamma=self.kernel.gamma, eta=self.eta,
-                                  capacity=self.capacity)
+                                  capacity=self.capacity, algorithm=self.ALGORITHM)
             self._agent.reset([[0]], [[0]])
             self._e = self._s = 0
 
@@ -114,3 +116,17 @@ class Projectron:
         if d['m'] == 0:
             raise AttributeError("'SVvariable' object has no attribute 'landmarks'")
         return d['landmarks'].shape[1] if d['m'] == 1 else d['m']
+
+
+class ProjectronPlus(Projectron):
+    """Projectron++ (projectron.py:66-107): update(x, y) also acts on a sample classified correctly inside the margin,
+    0 < y f < 1 -- a scaled projection that never adds a landmark.  The private one-learner agent runs in Projectron++ mode
+    (kb_set_algorithm); predict, update, fit, decision_function and Kinv work as on Projectron.  Not accepted by
+    kbrl_control.KBRL_Control, whose closed loop implements Projectron's rule: fit logged control steps instead
+    (ranslice.kbrl_dev.augmented_samples + VecKBRL.fit)."""
+    ALGORITHM = 'projectron_plus'
+
+    def _bind(self, agent, e, s):
+        if agent.algorithm != self.ALGORITHM:
+            raise ValueError('ProjectronPlus: the agent it is bound to runs %r' % agent.algorithm)
+        super()._bind(agent, e, s)

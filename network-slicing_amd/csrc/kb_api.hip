@@ -71,6 +71,7 @@ struct kb_handle {
     bool is_reset = false;
     bool learning = true;          // kb_set_learning: false = the resident loop selects only (KBRL_Control.run past learning_time)
     bool frozen = false;           // an inference-only handle (kb_deploy): no Kinv behind its dictionaries, learning permanently off
+    int32_t alg = KB_ALG_PROJECTRON;  // kb_set_algorithm: the rule of the next kb_update / kb_fit; host state of the handle, never copied or saved
     // kb_fork / kb_deploy into this handle (kb_fork.hip)
     hipEvent_t ev_fork_in = nullptr, ev_fork_out = nullptr;
     int32_t* d_fork_idx = nullptr;   // [n_envs] source agent of every agent
@@ -690,6 +691,17 @@ static int launch_select(kb_handle* k, const float* d_state, int32_t* d_action_o
     return RS_OK;
 }
 
+// Projectron++ mode (kb_set_algorithm): the closed control loop does not learn through such a handle -- its update phase is
+// built around Projectron's rule, under which nine learners in ten have nothing to do in a step
+static int kb_refuse_plus(kb_handle* k, const char* who) {
+    if (k->alg != KB_ALG_PROJECTRON_PLUS) return RS_OK;
+    k->err = std::string(who) +
+             ": the handle is in Projectron++ mode (kb_set_algorithm), which learns through kb_update / kb_fit only -- the control "
+             "loop's update phase implements Projectron's rule (kb_set_algorithm(k, KB_ALG_PROJECTRON) switches back; "
+             "kb_set_learning(k, 0) lets the resident loop select without learning)";
+    return RS_ESTATE;
+}
+
 extern "C" int kb_update_control(kb_handle* k, const float* state, const int32_t* action, const int32_t* labels,
                                  int32_t* hits) {
     if (!k || !state || !action || !labels) return RS_EINVAL;
@@ -697,6 +709,7 @@ extern "C" int kb_update_control(kb_handle* k, const float* state, const int32_t
         k->err = "kb_update_control: call kb_reset first";
         return RS_ESTATE;
     }
+    if (int rc = kb_refuse_plus(k, "kb_update_control")) return rc;
     if (k->D.shared) {
         k->err = "kb_update_control: shared-dictionary handles learn through kb_shared_scan/apply/commit";
         return RS_ESTATE;
@@ -750,6 +763,8 @@ extern "C" int kb_step_resident(kb_handle* k, rs_handle* env) {
         k->err = "kb_step_resident: shared-dictionary handles step through kb_shared_step_resident";
         return RS_ESTATE;
     }
+    if (k->learning)
+        if (int rc = kb_refuse_plus(k, "kb_step_resident")) return rc;
     HIPCHK(k, hipSetDevice(k->device));
     if (env->hint_auto && !env->block_hint) {  // the next steps take agent-made allocations
         rs_set_schedule_hint(env, 1);
@@ -807,6 +822,8 @@ static int enqueue_closed_step(kb_handle* k, rs_handle* env) {
 extern "C" int kb_run_resident(kb_handle* k, rs_handle* env, int n_steps, int use_graph) {
     if (!k || !env || n_steps < 0) return RS_EINVAL;
     int done = 0, rc;
+    // (asked here too: a graph captured before the mode changed would replay the update phase without passing kb_step_resident)
+    if (k->learning && (rc = kb_refuse_plus(k, "kb_run_resident")) != RS_OK) return rc;
     // rocprofv3 (ROCm 7.2) dies with SIGSEGV inside hipGraphLaunch of this loop's graph (kernels, memory copies, memsets; the
     // simulator-only graph of rs_run_random is fine under it): with a profiler tool attached the steps are enqueued one by one,
     // same results.  KBRL_GRAPH_UNDER_PROFILER=1 keeps the graph.
@@ -900,6 +917,7 @@ static int kb_one(kb_handle* k, int e, int s, const double* x, int y, bool updat
     memset(a.x, 0, sizeof a.x);
     for (int q = 0; q < k->cfg.dims[s] + 1; ++q) a.x[q] = x[q];
     a.out = k->d_out;
+    a.alg = k->alg;
     if (update)
         hipLaunchKernelGGL(kb::update_one_kernel, dim3(1), dim3(256), 0, k->stream, a);
     else
@@ -1742,5 +1760,30 @@ extern "C" int kb_set_learning(kb_handle* k, int on) {
     }
     if (k->learning != (on != 0)) kb_drop_graph(k);
     k->learning = on != 0;
+    return RS_OK;
+}
+
+/* The update rule of the handle's next kb_update / kb_fit (ranslice.h): host state of the handle, handed to
+ * their kernels with the launch arguments.  No other kernel knows about it. */
+extern "C" int kb_set_algorithm(kb_handle* k, int32_t alg) {
+    if (!k) return RS_EINVAL;
+    if (alg != KB_ALG_PROJECTRON && alg != KB_ALG_PROJECTRON_PLUS) {
+        k->err = "kb_set_algorithm: " + std::to_string(alg) + " names no algorithm (KB_ALG_PROJECTRON, KB_ALG_PROJECTRON_PLUS)";
+        return RS_EINVAL;
+    }
+    if (alg == KB_ALG_PROJECTRON_PLUS && (k->frozen || k->ref || k->D.shared)) {
+        k->err = std::string("kb_set_algorithm: ") +
+                 (k->ref ? "a by-reference handle (kb_deploy_ref)" : k->frozen ? "an inference-only handle (kb_deploy, kb_import_agents)"
+                                                                               : "a shared-dictionary handle") +
+                 " does not learn through kb_update / kb_fit: Projectron++ has nothing to act on";
+        return RS_ESTATE;
+    }
+    k->alg = alg;
+    return RS_OK;
+}
+
+extern "C" int kb_get_algorithm(kb_handle* k, int32_t* alg) {
+    if (!k || !alg) return RS_EINVAL;
+    *alg = k->alg;
     return RS_OK;
 }

@@ -10,7 +10,8 @@
 // depends on what ran before them in the same launch but the dictionary itself, which the one-sample kernels pass from launch to
 // launch through the same global memory -- so every f, delta, coefficient and Kinv entry is bit for bit the one-by-one path's.
 // (Chip-wide rounds for ONE large dictionary, the heavy_* shape of update_control, are not used here: a dictionary of thousands
-// of landmarks is taught at the pace of one workgroup.)
+// of landmarks is taught at the pace of one workgroup.)  In Projectron++ mode (kb_set_algorithm) the same loop runs as its second
+// instance, fit_plus_kernel: apply_update_plus in place of the mistake test and apply_update, as update_one_kernel does.
 //
 // kb_score.  f of kb_predict for many points, and nothing else: no K_f row, no cache, no counter, no tie draw.  score_kernel's
 // workgroup takes one dictionary and KB_SCORE_Q of its queries, staged in LDS; thread t walks the landmarks j = t, t + 256, ...
@@ -41,12 +42,17 @@ struct FitArgs {
     double* delta;
     int32_t* m_after;
     unsigned long long* work;  // [0..3] samples, mistakes, insertions, kernel evaluations of the call
+    int alg;                   // KB_ALG_* of the handle at the call: the instance kb_fit launches
 };
 
-__global__ __launch_bounds__(256) void fit_kernel(FitArgs A) {
+// The persistent loop of one learner, once per update rule: fit_kernel is the Projectron instance (ALG is a compile-time constant,
+// so it holds none of the margin rule's code and its arithmetic is what it was before the rule existed), fit_plus_kernel the
+// Projectron++ one -- apply_update_plus on every sample, which on a mistake runs apply_update's two steps.  The LDS block is
+// declared by the kernels, as every kernel of kb_kbrl.hip declares its own.
+template <int ALG>
+__device__ __forceinline__ void fit_learner(const FitArgs& A, Lds& sm) {
     const KbDev& D = A.D;
     const KbState& K = A.K;
-    __shared__ Lds sm;
     const int i = blockIdx.x;
     const long long r0 = A.first[i] + A.from;
     const long long r1 = A.first[i + 1] < r0 + A.chunk ? A.first[i + 1] : r0 + A.chunk;
@@ -81,7 +87,13 @@ __global__ __launch_bounds__(256) void fit_kernel(FitArgs A) {
         const int y = (int)A.y[r];
         int branch = 0, m_new = m;
         double delta = 0.0;
-        if (f * (double)y <= 0.0) {
+        if (ALG == KB_ALG_PROJECTRON_PLUS) {
+            // ProjectronPlus.update (projectron.py:71-107): a mistake is a sample that changed the dictionary (branches 1-3)
+            const double t_last = sm.x[d - 1];
+            m_new = apply_update_plus(D, K, dt, env, m, d, sm.x, t_last, grid_index(t_last, D.n_prbs), y, f, sm, &branch, &delta);
+            if (branch >= 1 && branch <= 3) n_mist += 1;
+            if (branch == 2 && m_new > m) n_grow += 1;
+        } else if (f * (double)y <= 0.0) {
             const double t_last = sm.x[d - 1];
             m_new = apply_update(D, K, dt, env, m, d, sm.x, t_last, grid_index(t_last, D.n_prbs), y, sm, &branch, &delta);
             n_mist += 1;
@@ -110,6 +122,16 @@ __global__ __launch_bounds__(256) void fit_kernel(FitArgs A) {
         atomicAdd(&A.work[2], n_grow);
         atomicAdd(&A.work[3], n_eval);
     }
+}
+
+__global__ __launch_bounds__(256) void fit_kernel(FitArgs A) {
+    __shared__ Lds sm;
+    fit_learner<KB_ALG_PROJECTRON>(A, sm);
+}
+
+__global__ __launch_bounds__(256) void fit_plus_kernel(FitArgs A) {
+    __shared__ Lds sm;
+    fit_learner<KB_ALG_PROJECTRON_PLUS>(A, sm);
 }
 
 // a workgroup of score_kernel: cnt <= KB_SCORE_Q consecutive queries (rows q0 .. of the staged block) against one dictionary
@@ -341,6 +363,7 @@ extern "C" int kb_fit(kb_handle* k, const int32_t* task, int32_t n, const int64_
     a.y = d_y;
     a.chunk = chunk;
     a.work = p->d_work;
+    a.alg = k->alg;
     // behind whatever is queued on either of the handle's streams
     if (k->side && (rc = stream_after(k, &p->ev_in, k->side, k->stream)) != RS_OK) return rc;
     HIPCHK(k, hipMemcpyAsync(d_task, task, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, k->stream));
@@ -355,7 +378,10 @@ extern "C" int kb_fit(kb_handle* k, const int32_t* task, int32_t n, const int64_
         a.from = (long long)from;
         hipEvent_t e;
         HIPCHK(k, p->fit_spans.begin(k->stream, 0, &e));
-        hipLaunchKernelGGL(kb::fit_kernel, dim3((unsigned)n), dim3(256), 0, k->stream, a);
+        if (a.alg == KB_ALG_PROJECTRON_PLUS)
+            hipLaunchKernelGGL(kb::fit_plus_kernel, dim3((unsigned)n), dim3(256), 0, k->stream, a);
+        else
+            hipLaunchKernelGGL(kb::fit_kernel, dim3((unsigned)n), dim3(256), 0, k->stream, a);
         if (e) HIPCHK(k, hipEventRecord(e, k->stream));
     }
     HIPCHK(k, hipGetLastError());

@@ -1186,12 +1186,9 @@ __device__ __forceinline__ bool take_shell(const KbDev& D, const KbState& K, int
     return ok;
 }
 
-// The part of Projectron.update (projectron.py:41-60) that follows d* = Kinv K_f (DS row): delta, the decision, and the
-// projection or the insertion.  With defer_rank1 the O(m^2) update of Kinv is left to the caller (rank1_units with the
-// returned delta).  Returns the new m.  branch: 1 = projection onto the dictionary, 2 = dictionary grew.
-__device__ int finish_update(const KbDev& D, const KbState& K, int dict, int err_env, int m, int d, const double* x, double t_last,
-                             int a_last, int y, Lds& sm, int* branch, double* delta_out, bool* saturated, bool defer_rank1) {
-    const uint64_t* sh = shells_of(D, K, dict);
+// delta = max(Kii - d* . K_f, 0) (projectron.py:45) of d* in the DS row and the kernel column in the K_f row; float32 operands
+// while at most one landmark is held.  Every thread returns it.  (finish_update's head, and apply_update_plus's.)
+__device__ __forceinline__ double residual_delta(const KbState& K, const uint64_t* sh, int m, Lds& sm) {
     double dot;
     if (m <= 1) {
         const float kf0 = m == 0 ? 0.0f : (float)*vec_at(K, sh, KB_ROW_KF, 0);
@@ -1208,6 +1205,16 @@ __device__ int finish_update(const KbDev& D, const KbState& K, int dict, int err
     }
     double delta = 1.0 - dot;  // Kii = k(x, x) = 1
     delta = delta > 0.0 ? delta : 0.0;
+    return delta;
+}
+
+// The part of Projectron.update (projectron.py:41-60) that follows d* = Kinv K_f (DS row): delta, the decision, and the
+// projection or the insertion.  With defer_rank1 the O(m^2) update of Kinv is left to the caller (rank1_units with the
+// returned delta).  Returns the new m.  branch: 1 = projection onto the dictionary, 2 = dictionary grew.
+__device__ int finish_update(const KbDev& D, const KbState& K, int dict, int err_env, int m, int d, const double* x, double t_last,
+                             int a_last, int y, Lds& sm, int* branch, double* delta_out, bool* saturated, bool defer_rank1) {
+    const uint64_t* sh = shells_of(D, K, dict);
+    const double delta = residual_delta(K, sh, m, sm);
     *delta_out = delta;
     if (threadIdx.x == 0) atomicAdd(&K.ver[dict], 1);  // the dictionary changes (projection or insertion): stored scores are stale
                                                        // (no return value: nothing waits for it)
@@ -1295,6 +1302,70 @@ __device__ int apply_update(const KbDev& D, const KbState& K, int dict, int err_
             matvec_colsum<2>(K, sh, m);
     }
     return finish_update(D, K, dict, err_env, m, d, x, t_last, a_last, y, sm, branch, delta_out, saturated, false);
+}
+
+// ProjectronPlus.update (projectron.py:71-107) for the same x, whose f the caller holds (kb_predict's, or predict_column's of this
+// launch).  margin = y f decides: >= 1 nothing (branch 0); <= 0 Projectron's update, apply_update's two steps (branches 1, 2); in between
+// the margin rule (projectron.py:74-85): d* and delta as above, loss = 1 - margin, and when loss - delta / eta > 0 the scaled
+// projection coeff += (alpha y) d*, alpha = min(min(loss / norm, 1), 2 (loss - delta / eta) / norm), norm = max(1 - delta, 0)
+// (branch 3; norm == 0: loss / norm is +inf and alpha = 1, as NumPy's).  Otherwise nothing is written and the version stays
+// (branch 4).  The margin rule never inserts, so it takes no shell, touches no Kinv and does not ask for the capacity.
+// While one landmark is held the reference's arrays are float32 and its scalars follow NumPy's promotion: margin and loss are
+// float32, delta, the slack and alpha float64, the new coefficient is formed in float64 and stored as float32.
+__device__ int apply_update_plus(const KbDev& D, const KbState& K, int dict, int err_env, int m, int d, const double* x,
+                                 double t_last, int a_last, int y, double f, Lds& sm, int* branch, double* delta_out) {
+    const double margin = (double)y * f;
+    if (margin >= 1.0) {
+        *branch = 0;
+        *delta_out = 0.0;
+        return m;
+    }
+    // Both remaining cases begin with d* = Kinv K_f, apply_update's head restated (a change there is made here too).  It stands at
+    // ONE place for the two of them: a mistake continues with finish_update, which makes it apply_update statement for statement.
+    // (Behind a call of apply_update itself the mat-vec routines were inlined twice, 672 B per lane of scratch in fit_plus_kernel;
+    // and a helper shared with apply_update moved instructions in the control loop's kernels, which this rule is to leave alone.)
+    const uint64_t* sh = shells_of(D, K, dict);
+    if (m == 1) {
+        // Kinv is the 1-element float32 array [1 / Kii]; K_f is float32 (projectron.py:29,59)
+        __syncthreads();
+        if (threadIdx.x == 0) *vec_at(K, sh, KB_ROW_DS, 0) = (double)(1.0f * (float)*vec_at(K, sh, KB_ROW_KF, 0));
+        __syncthreads();
+    } else if (m >= 2) {
+        if (D.tri)
+            matvec_tri_colsum(K, sh, m);
+        else if (blockDim.x >= 256)
+            matvec_colsum<4>(K, sh, m);
+        else
+            matvec_colsum<2>(K, sh, m);
+    }
+    if (margin <= 0.0) return finish_update(D, K, dict, err_env, m, d, x, t_last, a_last, y, sm, branch, delta_out, nullptr, false);
+    // (0 < margin: f != 0, so m >= 1)
+    const double delta = residual_delta(K, sh, m, sm);
+    *delta_out = delta;
+    double norm = 1.0 - delta;  // Kii - delta
+    norm = norm > 0.0 ? norm : 0.0;
+    const double loss = m == 1 ? (double)(1.0f - (float)margin) : 1.0 - margin;
+    const double slack = loss - delta / D.eta;
+    if (!(slack > 0.0)) {
+        *branch = 4;
+        return m;
+    }
+    *branch = 3;
+    if (threadIdx.x == 0) atomicAdd(&K.ver[dict], 1);  // the coefficients change: stored scores are stale
+    double alpha = loss / norm;
+    alpha = 1.0 < alpha ? 1.0 : alpha;
+    const double by_slack = 2.0 * slack / norm;
+    alpha = by_slack < alpha ? by_slack : alpha;
+    const double ay = alpha * (double)y;
+    for (int j = threadIdx.x; j < m; j += blockDim.x) {
+        double* P = vec_page(K, sh, j >> 6);
+        const int l = j & 63;
+        double nc = P[KB_ROW_CO * KB_CH + l] + ay * P[KB_ROW_DS * KB_CH + l];
+        if (m == 1) nc = (double)(float)nc;
+        P[KB_ROW_CO * KB_CH + l] = nc;
+    }
+    __syncthreads();
+    return m;
 }
 
 struct CtlArgs {
@@ -3241,6 +3312,7 @@ struct OneArgs {
     int y;
     double x[KB_DMAX];
     double* out;  // [4]: y_pred, f, branch, delta
+    int alg;      // KB_ALG_* of the handle at the call (kb_set_algorithm): which update rule update_one_kernel applies
 };
 
 // GaussianKernel.predict's sum (kernel.py:13-28) by a 256-thread block: the kernel column of x into the K_f row, f = K_f . coeff as
@@ -3311,7 +3383,10 @@ __global__ __launch_bounds__(256) void update_one_kernel(OneArgs A) {
         return;
     }
     const double f = K.f_last[task];
-    if (!(f * (double)A.y <= 0.0)) {
+    // Projectron.update returns at once unless f y <= 0.  ProjectronPlus.update (kb_set_algorithm) has no such early return: the
+    // margin 0 < f y < 1 updates too (branches 3, 4), so the rule itself decides -- apply_update_plus, which on f y <= 0 is
+    // apply_update statement for statement (so the mat-vec routines are inlined once for both algorithms).
+    if (A.alg != KB_ALG_PROJECTRON_PLUS && !(f * (double)A.y <= 0.0)) {
         if (threadIdx.x == 0) { A.out[2] = 0.0; A.out[3] = 0.0; }
         return;
     }
@@ -3319,13 +3394,16 @@ __global__ __launch_bounds__(256) void update_one_kernel(OneArgs A) {
     __syncthreads();
     int branch;
     double delta;
-    const int m_new = apply_update(D, K, dt, env, m, d, sm.x, A.x[d - 1], grid_index(A.x[d - 1], D.n_prbs), A.y, sm, &branch, &delta);
+    const int m_new =
+        apply_update_plus(D, K, dt, env, m, d, sm.x, A.x[d - 1], grid_index(A.x[d - 1], D.n_prbs), A.y, f, sm, &branch, &delta);
     if (threadIdx.x == 0) {
         K.m[dt] = m_new;
-        K.kf_owner[dt] = -1;  // update_control reuses the row
         A.out[2] = (double)branch;
         A.out[3] = delta;
-        K.stats[(size_t)task * 4 + 1] += 1;
+        if (branch >= 1 && branch <= 3) {  // the dictionary changed (Projectron: always); after 0 and 4 nothing was written
+            K.kf_owner[dt] = -1;           // update_control reuses the row
+            K.stats[(size_t)task * 4 + 1] += 1;
+        }
         if (branch == 2 && m_new > m) K.stats[(size_t)task * 4 + 2] += 1;
     }
 }

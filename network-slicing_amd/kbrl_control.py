@@ -29,6 +29,14 @@ class KBRL_Control:
         self.n_prbs = n_prbs
         self.alfa = alfa
         self.adjusted = 0
+        # the closed control loop implements Projectron's rule only: no silent training of a ProjectronPlus as a
+        # Projectron, and no refusal deep inside update_control
+        plus = [s for s, h in enumerate(learners) if getattr(h.algorithm, 'ALGORITHM', 'projectron') != 'projectron']
+        if plus:
+            raise ValueError('KBRL_Control: learner(s) %s are ProjectronPlus; the closed control loop (update_control, run) '
+                             'implements the Projectron rule only.  Supported route: log the control steps, turn them into sample '
+                             "lists with ranslice.kbrl_dev.augmented_samples, and VecKBRL.fit them on a handle created with "
+                             "algorithm='projectron_plus' (then deploy / select_action / export_agents as usual)" % plus)
         dims = []
         expect = 0
         for h in learners:

@@ -25,6 +25,7 @@ KB_EXPORTS = (
     'kb_fork_rebuild', 'kb_get_rebuild', 'kb_rebuild_time_ms',
     'kb_unshare', 'kb_share', 'kb_bridge_time_ms',
     'kb_fit', 'kb_score', 'kb_fit_time_ms',
+    'kb_set_algorithm', 'kb_get_algorithm',
 )
 
 EXPORTS = (
@@ -211,6 +212,8 @@ def load(dev=None):
     L.kb_fit.argtypes = [vp, ip, C.c_int32, i64p, dp, C.POINTER(C.c_int8), C.c_int32, ip, dp, ip, dp, ip]
     L.kb_score.argtypes = [vp, ip, C.c_int32, i64p, dp, dp, ip]
     L.kb_fit_time_ms.argtypes = [vp, dp, up]
+    L.kb_set_algorithm.argtypes = [vp, C.c_int32]
+    L.kb_get_algorithm.argtypes = [vp, ip]
     for name in EXPORTS:
         if name not in ('rs_last_error', 'rs_destroy', 'kb_last_error', 'kb_destroy'):
             getattr(L, name).restype = C.c_int

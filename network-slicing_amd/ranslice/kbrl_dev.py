@@ -20,6 +20,7 @@ _up = C.POINTER(C.c_uint64)
 
 VEC_PAGE_BYTES = 30 * 64 * 8   # one shell of an inference-only handle: the vector page of 64 landmarks (KB_VEC doubles)
 POOL_PREAMBLE_BYTES = 64 * 8   # pool offset 0 means "no shell": every pool starts with 64 unused doubles
+ALGORITHMS = {'projectron': 0, 'projectron_plus': 1}   # KB_ALG_PROJECTRON, KB_ALG_PROJECTRON_PLUS (ranslice.h)
 
 
 def deploy_pool_bytes(sizes):
@@ -91,7 +92,9 @@ class VecKBRL:
     by_reference = False   # True on those deploy(index, by_reference=True) returns: dictionaries stored once per distinct agent
 
     def __init__(self, n_envs, dims, n_prbs, alfa=KBRL_ALFA, accuracy_range=(0.99, 0.999), gamma=KBRL_GAMMA,
-                 eta=KBRL_ETA, capacity=4096, device=0, shared=False, first_env=0, pool_bytes=0):
+                 eta=KBRL_ETA, capacity=4096, device=0, shared=False, first_env=0, pool_bytes=0, algorithm='projectron'):
+        if algorithm not in ALGORITHMS:
+            raise ValueError('algorithm must be one of %s, not %r' % (sorted(ALGORITHMS), algorithm))
         self.L = _lib.load()
         cfg = KbConfig()
         cfg.n_envs, cfg.n_slices, cfg.n_prbs, cfg.capacity = n_envs, len(dims), n_prbs, capacity
@@ -108,6 +111,26 @@ class VecKBRL:
         self.device = int(device)
         self.h = C.c_void_p()
         self._check(self.L.kb_create(C.byref(cfg), int(device), C.byref(self.h)))
+        if algorithm != 'projectron':
+            self.set_algorithm(algorithm)
+
+    def set_algorithm(self, algorithm):
+        """the update rule of the next update() / fit() (kb_set_algorithm): 'projectron' (the default; projectron.py:39-60) or
+        'projectron_plus' (Projectron++, projectron.py:71-107: a sample classified correctly inside the margin 0 < y f < 1 gives
+        a scaled projection, never a landmark).  A property of this handle, not of its dictionaries: checkpoints and agent files do
+        not hold it, fork_from / deploy / load_agents / unshare_from do not carry it over.  While in 'projectron_plus',
+        update_control and the learning resident loop are refused (RS_ESTATE); select_action, score, prune, deploy, export work.
+        Refused (RS_ESTATE) on deployed, by-reference and shared-dictionary handles."""
+        if algorithm not in ALGORITHMS:
+            raise ValueError('algorithm must be one of %s, not %r' % (sorted(ALGORITHMS), algorithm))
+        self._check(self.L.kb_set_algorithm(self.h, ALGORITHMS[algorithm]))
+
+    @property
+    def algorithm(self):
+        """'projectron' or 'projectron_plus' (kb_get_algorithm)"""
+        a = C.c_int32()
+        self._check(self.L.kb_get_algorithm(self.h, C.byref(a)))
+        return {v: k for k, v in ALGORITHMS.items()}[a.value]
 
     def _check(self, rc):
         if rc != 0:
@@ -195,6 +218,9 @@ class VecKBRL:
         return y.value, f.value
 
     def update(self, e, s, x, y):
+        """Projectron.update(x, y) on the (f, k) cached by the preceding predict(e, s, x) -> (branch, delta).  branch: 0 nothing,
+        1 projection, 2 the dictionary grew; in 'projectron_plus' mode (set_algorithm) also 3 margin update (coefficients moved,
+        no landmark added) and 4 margin test that changed nothing.  delta is the projection residual, formed for branches 1-4."""
         x = np.ascontiguousarray(x, dtype=np.float64)
         br, dl = C.c_int32(), C.c_double()
         self._check(self.L.kb_update(self.h, e, s, x.ctypes.data_as(_dp), int(y), C.byref(br), C.byref(dl)))
@@ -227,8 +253,9 @@ class VecKBRL:
         distinct, X[i] = [n_i, dims[s] + 1] samples of learner i in order, y[i] = [n_i] labels +1 / -1.  For every learner and
         sample in order: predict(x_t), then update(x_t, y_t) -- bit for bit what the one-by-one predict / update calls leave,
         one workgroup per learner on the device.  chunk: most samples of one learner per launch (0: the default); no result
-        depends on it.  -> dict of per-learner lists of arrays: y_pred, f, branch (0 none, 1 projection, 2 grew), delta and
-        m (the dictionary's size after the sample).  The cached predict of the touched learners is invalid afterwards."""
+        depends on it.  -> dict of per-learner lists of arrays: y_pred, f, branch (0 none, 1 projection, 2 grew; in
+        'projectron_plus' mode also 3 margin update, 4 margin test without update -- see update()), delta and m (the dictionary's
+        size after the sample).  The cached predict of the touched learners is invalid afterwards."""
         task, first, rows = self._pack_rows(learners, X, 'fit')
         if len(y) != len(task):
             raise ValueError('fit: %d learners but %d label arrays' % (len(task), len(y)))
@@ -629,6 +656,9 @@ class SharedVecKBRL(VecKBRL):
     handles side by side in ONE process (tests) and to pin the merge rule on CPU (merge_proposals, gloo test)."""
 
     def __init__(self, n_envs, dims, n_prbs, budget=64, max_rounds=4, exchange=None, **kw):
+        if kw.get('algorithm', 'projectron') != 'projectron':
+            raise ValueError("SharedVecKBRL learns through its proposal rounds, which implement Projectron's rule: "
+                             "algorithm=%r is not supported (fit a per-replica VecKBRL, then to_shared)" % kw['algorithm'])
         super().__init__(n_envs, dims, n_prbs, shared=True, **kw)
         self.budget, self.max_rounds = budget, max_rounds
         self.exchange = exchange

@@ -27,8 +27,9 @@ BRIDGE = ['unshare_count_kernel', 'unshare_tables_kernel', 'unshare_shells_kerne
 # kb_fork's own kernels (kb_fork.hip), whose gather helpers and work line the bridge's and kb_fork_rebuild's call: the same
 FORK = ['fork_count_kernel', 'fork_scan_kernel', 'fork_tables_kernel', 'fork_shells_kernel']
 # kb_fit / kb_score (kb_fit.hip): reported; the scoring kernel is held to no scratch at all (KB_SCORE_Q was chosen by that), the
-# fitting kernel -- predict_column and apply_update inlined into one persistent loop -- to what the build shows: none either
-FIT_SCRATCH = {'fit_kernel': 0, 'score_kernel': 0}
+# fitting kernel -- predict_column and apply_update inlined into one persistent loop -- to what the build shows: none either; so
+# is its Projectron++ instance (fit_plus_kernel: the same loop around apply_update_plus)
+FIT_SCRATCH = {'fit_kernel': 0, 'fit_plus_kernel': 0, 'score_kernel': 0}
 PRODUCTION = ["embb_step_kernelILi16ELb0ELb0ELb1E", "embb_step_kernelILi16ELb0ELb1ELb1E"]   # <16, false, plain | BLOCK, FDIV>
 PLAIN = PRODUCTION[0]          # the instance bench.py's headline runs
 STEP_KERNEL = 'embb_step_kernelIL'
