@@ -11,7 +11,12 @@
 //                      coefficients and last coordinates, and the handle's G table (256 entries)
 //   kb_dev_get_chains  the newest-landmark heads (KB_HEAD entries), the first min(m, max_m) chain links of KB_ROW_IDX and the
 //                      off-grid count of one learner's dictionary: what agents_finish_kernel (kb_agents.hip) rebuilds
-// By-reference handles (kb_ref.hip) answer both: their scores are per task as everywhere (they keep no W: zeros), their rows are
+//   kb_dev_get_update_rows  the first min(m, max_m) entries of one learner's KB_ROW_KF / KB_ROW_DS rows as the last
+//                      Projectron.update left them (the kernel column and d* = Kinv K_f; after an insertion entry m - 1 of d* is
+//                      its -1) and, optionally, the 128 partial sums of every stored tile of the first ceil(min(m, max_m) / 64)
+//                      shells, tile (b_i, b_j) at 128 (b_i (b_i + 1) / 2 + b_j): dpart, then tpart (matvec_tri_tiles); a tile the
+//                      last mat-vec did not cover holds whatever it held before (tests/test_gpu_update_chain.py)
+// By-reference handles (kb_ref.hip) answer the first two: their scores are per task as everywhere (they keep no W: zeros), their rows are
 // those of the store's dictionary the map names for (e, s) -- which no selection may ever have changed.
 
 extern "C" int kb_dev_get_scores(kb_handle* k, double* F, double* W, int32_t* fdirect) {
@@ -108,6 +113,43 @@ extern "C" int kb_dev_get_chains(kb_handle* k, int e, int s, int32_t max_m, int3
         const int cnt = take - KB_CH * b < KB_CH ? take - KB_CH * b : KB_CH;
         HIPCHK(k, hipMemcpy(link + KB_CH * b, (const int32_t*)(k->K.pool + sh[b] + KB_ROW_IDX * KB_CH) + 64, sizeof(int32_t) * (size_t)cnt,
                             hipMemcpyDeviceToHost));
+    }
+    return RS_OK;
+}
+
+extern "C" int kb_dev_get_update_rows(kb_handle* k, int e, int s, int32_t max_m, int32_t* m_out, double* kf, double* ds, double* parts) {
+    if (!k || e < 0 || e >= k->cfg.n_envs || s < 0 || s >= k->cfg.n_slices || max_m < 0) return RS_EINVAL;
+    if (k->ref || k->D.shared || k->D.tri != 1) {
+        k->err = "kb_dev_get_update_rows: a handle that owns one dictionary per learner, with its Kinv, only";
+        return RS_ESTATE;
+    }
+    HIPCHK(k, hipSetDevice(k->device));
+    HIPCHK(k, hipStreamSynchronize(k->stream));
+    const size_t dict = (size_t)e * k->cfg.n_slices + s;
+    int32_t m = 0;
+    HIPCHK(k, hipMemcpy(&m, k->K.m + dict, sizeof m, hipMemcpyDeviceToHost));
+    if (m_out) *m_out = m;
+    const int take = m < max_m ? m : max_m;
+    if (take <= 0) return RS_OK;
+    const int nch = (take + KB_CH - 1) / KB_CH;
+    if (nch > k->D.max_shells) {
+        k->err = "kb_dev_get_update_rows: more landmarks than the shell table holds";
+        return RS_ESTATE;
+    }
+    std::vector<uint64_t> sh((size_t)nch);
+    HIPCHK(k, hipMemcpy(sh.data(), k->K.shell + dict * (size_t)k->D.max_shells, sizeof(uint64_t) * (size_t)nch, hipMemcpyDeviceToHost));
+    for (int b = 0; b < nch; ++b) {
+        if (sh[b] == 0 || sh[b] + kb::kb_shell_doubles(b, 1) > k->D.pool_doubles) {
+            k->err = "kb_dev_get_update_rows: shell table entry out of the pool";
+            return RS_ESTATE;
+        }
+        const int cnt = take - KB_CH * b < KB_CH ? take - KB_CH * b : KB_CH;
+        const double* page = k->K.pool + sh[b];
+        if (kf) HIPCHK(k, hipMemcpy(kf + KB_CH * b, page + KB_ROW_KF * KB_CH, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
+        if (ds) HIPCHK(k, hipMemcpy(ds + KB_CH * b, page + KB_ROW_DS * KB_CH, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
+        if (parts)  // (the partial sums of the shell's b + 1 tiles lie behind them, in the order of the tiles)
+            HIPCHK(k, hipMemcpy(parts + (size_t)128 * ((size_t)b * (b + 1) / 2), page + KB_VEC + (size_t)(b + 1) * KB_TILE,
+                                sizeof(double) * 128 * (size_t)(b + 1), hipMemcpyDeviceToHost));
     }
     return RS_OK;
 }

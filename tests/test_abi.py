@@ -85,14 +85,14 @@ def test_production_library_reads_no_developer_knob():
         pytest.skip('libraries not built')
     prod = open(_lib.LIB_PATH, 'rb').read()
     dev = open(_lib.DEV_LIB_PATH, 'rb').read()
-    knobs = [b'KBRL_INJECT_FAIL_ROUND', b'KBRL_ROUNDS', b'KBRL_HEAVY_M', b'KBRL_SERIAL_APPLY', b'RANSLICE_SNAKE', b'RANSLICE_KEY_W',
+    knobs = [b'KBRL_INJECT_FAIL_ROUND', b'KBRL_ROUNDS', b'KBRL_STREAM_GRID', b'KBRL_HEAVY_M', b'KBRL_SERIAL_APPLY', b'RANSLICE_SNAKE', b'RANSLICE_KEY_W',
              b'RANSLICE_PAIR', b'RANSLICE_ORDER', b'RANSLICE_GUARD', b'RANSLICE_EXACT_DIV', b'RANSLICE_HINT']
     for k in knobs:   # (as a whole NUL-terminated string: the argument of a getenv)
         assert k + b'\0' not in prod, k
         assert k + b'\0' in dev, k
     # the primitive probe (csrc/rs_probe.hip) is test tooling too: neither the entry point nor its kernels are in the product
     # and so are the accessors of the agent's scoring chain (csrc/kb_probe.hip)
-    for k in (b'rs_dev_probe', b'probe_kernel', b'kb_dev_get_scores', b'kb_dev_get_rows'):
+    for k in (b'rs_dev_probe', b'probe_kernel', b'kb_dev_get_scores', b'kb_dev_get_rows', b'kb_dev_get_update_rows'):
         assert k not in prod, k
         assert k in dev, k
     assert not [n for n in _lib.EXPORTS if '_dev_' in n]
