@@ -710,6 +710,30 @@ int kb_fit_time_ms(kb_handle* k, double ms[2], uint64_t work[4]);
 int kb_set_algorithm(kb_handle* k, int32_t alg);
 int kb_get_algorithm(kb_handle* k, int32_t* alg);
 
+/* ---- kb_fit for learners that hold large dictionaries: chip-wide rounds (csrc/kb_fit_wide.hip).  kb_fit teaches
+ * one learner per workgroup; against a dictionary of thousands of landmarks every mistake is an O(m^2) mat-vec and rank-1 update
+ * that this one workgroup streams alone.  kb_set_fit_wide(k, min_landmarks, window): min_landmarks = 0 (the default) leaves
+ * kb_fit exactly as it is; min_landmarks >= 2 hands every listed learner whose dictionary holds at least that many landmarks AT
+ * THE START OF A CHUNK (kb_fit's `chunk`) to rounds of plain launches for that chunk -- a scan of the next `window` samples, the
+ * first mistake, its mat-vec and rank-1 update spread over the whole chip by cost -- while the others go through the one-workgroup
+ * kernel as before.  A dictionary that grows past the threshold inside a call changes path at a chunk boundary.  Every returned
+ * value, dictionary (landmarks, coefficients, all of Kinv), tie counter, statistic and flag, and kb_fit_time_ms's work[4], are BIT
+ * FOR BIT those of the narrow path, whatever min_landmarks, window and chunk; only the time differs.  window: samples per learner
+ * a round scores ahead, 1 .. 256, 0 = the default (64).  The value 1 for min_landmarks is refused: the float32 regime of a single
+ * landmark stays in the narrow path.  In Projectron++ mode (kb_set_algorithm) kb_fit takes the narrow path whatever the setting
+ * -- nearly every sample needs its mat-vec there, and the margin rule is one piece -- and kb_fit_wide_info reports zeros.
+ * Like the algorithm, the setting is host state of the HANDLE: not part of kb_save_state blobs or agent files, not carried over
+ * by kb_fork, kb_deploy, kb_import_agents, kb_share or kb_unshare.  Off by default.
+ * kb_set_fit_wide: RS_EINVAL for a negative value, for min_landmarks = 1 and for a window above 256; RS_ESTATE on an
+ * inference-only, a by-reference or a shared-dictionary handle (they do not learn through kb_fit).
+ * kb_fit_wide_info: of the last kb_fit on the handle -- work[0] samples taught by rounds, work[1] mat-vecs the rounds ran (the
+ * mistakes taught there), work[2] tiles of Kinv those mat-vecs read (n_b (n_b + 1) / 2 each, n_b = ceil(m / 64); 32,768 bytes a
+ * tile), work[3] kernel evaluations of the window scans (samples scored x landmarks; the rescans after a mistake are counted
+ * here and not in kb_fit_time_ms's work[3]). */
+int kb_set_fit_wide(kb_handle* k, int32_t min_landmarks, int32_t window);
+int kb_get_fit_wide(kb_handle* k, int32_t* min_landmarks, int32_t* window);
+int kb_fit_wide_info(kb_handle* k, uint64_t work[4]);   /* of the last kb_fit */
+
 #ifdef __cplusplus
 }
 #endif

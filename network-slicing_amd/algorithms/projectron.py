@@ -87,15 +87,20 @@ class Projectron:
         self._agent.update(self._e, self._s, x, int(y))
 
     # ---- build-defined conveniences (the reference has none of them)
-    def fit(self, X, y):
+    def fit(self, X, y, wide=None):
         """BUILD-DEFINED: predict(x_t) then update(x_t, y_t) over the rows of X in order, in one device call (VecKBRL.fit) -- the
         dictionary, f and every prediction are bit for bit what the loop over predict / update leaves.  -> the predictions
-        [len(X)].  The cached (f, k) of predict is invalid afterwards: call predict before the next update."""
+        [len(X)].  The cached (f, k) of predict is invalid afterwards: call predict before the next update.
+        wide: None keeps the agent's setting; min_landmarks, or (min_landmarks, window), is handed to VecKBRL.set_fit_wide first
+        and stays in force: from that dictionary size on the samples are taught by chip-wide rounds -- same bits, less time once
+        the dictionary holds hundreds of landmarks (0 turns it off again)."""
         X = np.asarray(X, dtype=np.float64)
         X = X.reshape(1, -1) if X.ndim == 1 else X
         if X.shape[0] == 0:
             return np.zeros(0, dtype=np.int32)
         self._ensure(X[0])
+        if wide is not None:
+            self._agent.set_fit_wide(*(wide if isinstance(wide, (tuple, list)) else (wide,)))
         out = self._agent.fit([(self._e, self._s)], [X], [np.asarray(y).reshape(-1)])
         self.f = float(out['f'][0][-1])
         return out['y_pred'][0]

@@ -9,8 +9,8 @@
 // populated dictionary draws from the learner's stream), the mistake test f y <= 0, apply_update.  Nothing in those functions
 // depends on what ran before them in the same launch but the dictionary itself, which the one-sample kernels pass from launch to
 // launch through the same global memory -- so every f, delta, coefficient and Kinv entry is bit for bit the one-by-one path's.
-// (Chip-wide rounds for ONE large dictionary, the heavy_* shape of update_control, are not used here: a dictionary of thousands
-// of landmarks is taught at the pace of one workgroup.)  In Projectron++ mode (kb_set_algorithm) the same loop runs as its second
+// (A dictionary of thousands of landmarks is taught at the pace of one workgroup here; kb_set_fit_wide hands such learners to
+// chip-wide rounds, the heavy_* shape of update_control, with the same bits: kb_fit_wide.hip)  In Projectron++ mode (kb_set_algorithm) the same loop runs as its second
 // instance, fit_plus_kernel: apply_update_plus in place of the mistake test and apply_update, as update_one_kernel does.
 //
 // kb_score.  f of kb_predict for many points, and nothing else: no K_f row, no cache, no counter, no tie draw.  score_kernel's
@@ -43,6 +43,7 @@ struct FitArgs {
     int32_t* m_after;
     unsigned long long* work;  // [0..3] samples, mistakes, insertions, kernel evaluations of the call
     int alg;                   // KB_ALG_* of the handle at the call: the instance kb_fit launches
+    const int32_t* wide;       // [n] 1: the learner is taught this chunk by the rounds of kb_fit_wide.hip; NULL: the wide path is off
 };
 
 // The persistent loop of one learner, once per update rule: fit_kernel is the Projectron instance (ALG is a compile-time constant,
@@ -57,6 +58,7 @@ __device__ __forceinline__ void fit_learner(const FitArgs& A, Lds& sm) {
     const long long r0 = A.first[i] + A.from;
     const long long r1 = A.first[i + 1] < r0 + A.chunk ? A.first[i + 1] : r0 + A.chunk;
     if (r0 >= r1) return;
+    if (A.wide && A.wide[i]) return;  // (kb_set_fit_wide: the rounds teach it this chunk)
     const int task = A.task[i], env = task / D.S, s = task - env * D.S;
     const int dt = task;  // (per-replica dictionaries only: kb_fit refuses shared ones)
     const uint64_t* sh = shells_of(D, K, dt);
@@ -150,20 +152,18 @@ struct ScoreArgs {
     unsigned long long* work;  // [0] kernel evaluations of the call
 };
 
-__global__ __launch_bounds__(256) void score_kernel(ScoreArgs A) {
-    const KbDev& D = A.D;
-    const KbState& K = A.K;
-    __shared__ double xs[KB_SCORE_Q][KB_DMAX];
-    __shared__ double red[KB_SCORE_Q][4];
-    __shared__ double k1[KB_SCORE_Q];  // the kernel value of the only landmark (m == 1), as the K_f row would hold it
-    const ScoreBlock B = A.blk[blockIdx.x];
-    const int dict = B.dict, cnt = B.cnt;
+// score_kernel's body: cnt <= KB_SCORE_Q queries (rows of 16 doubles from x on) against dictionary `dict`, f (and y_pred, unless
+// NULL) written from f[0] / y_pred[0] on.  Returns the dictionary's size.  The LDS blocks are the calling kernel's.  Also the window
+// scan of kb_fit's chip-wide rounds (kb_fit_wide.hip).
+__device__ __forceinline__ int score_queries(const KbDev& D, const KbState& K, int dict, int cnt, const double* x, double* f_out,
+                                             int32_t* y_pred, double (&xs)[KB_SCORE_Q][KB_DMAX], double (&red)[KB_SCORE_Q][4],
+                                             double (&k1)[KB_SCORE_Q]) {
     const int s = dict % D.S, d = D.dims[s] + 1;
     const uint64_t* sh = shells_of(D, K, dict);
     const int m = K.m[dict];
     if (threadIdx.x < KB_SCORE_Q * KB_DMAX) {
         const int u = threadIdx.x / KB_DMAX, c = threadIdx.x - u * KB_DMAX;
-        xs[u][c] = u < cnt ? A.x[(B.q0 + u) * KB_DMAX + c] : 0.0;
+        xs[u][c] = u < cnt ? x[u * KB_DMAX + c] : 0.0;
     }
     __syncthreads();
     double acc[KB_SCORE_Q];
@@ -211,18 +211,55 @@ __global__ __launch_bounds__(256) void score_kernel(ScoreArgs A) {
         for (int w = 0; w < 4; ++w) f += red[u][w];
         if (m == 1) f = (double)(float)((float)k1[u] * (float)*vec_at(K, sh, KB_ROW_CO, 0));
         if (m == 0) f = 0.0;
-        A.f[B.q0 + u] = f;
-        A.y_pred[B.q0 + u] = m > 0 ? (f > 0.0 ? 1 : (f < 0.0 ? -1 : 0)) : 0;
+        f_out[u] = f;
+        if (y_pred) y_pred[u] = m > 0 ? (f > 0.0 ? 1 : (f < 0.0 ? -1 : 0)) : 0;
     }
-    if (threadIdx.x == 0) atomicAdd(&A.work[0], (unsigned long long)m * (unsigned long long)cnt);
+    return m;
 }
+
+__global__ __launch_bounds__(256) void score_kernel(ScoreArgs A) {
+    __shared__ double xs[KB_SCORE_Q][KB_DMAX];
+    __shared__ double red[KB_SCORE_Q][4];
+    __shared__ double k1[KB_SCORE_Q];  // the kernel value of the only landmark (m == 1), as the K_f row would hold it
+    const ScoreBlock B = A.blk[blockIdx.x];
+    const int m = score_queries(A.D, A.K, B.dict, B.cnt, A.x + B.q0 * KB_DMAX, A.f + B.q0, A.y_pred + B.q0, xs, red, k1);
+    if (threadIdx.x == 0) atomicAdd(&A.work[0], (unsigned long long)m * (unsigned long long)B.cnt);
+}
+
+// The state of kb_fit's chip-wide rounds (kb_fit_wide.hip), in the call's staged block; rebuilt by every chunk's
+// classification.  By listed learner: mark.  By slot of the chunk's list of wide learners: everything else.
+struct FitWide {
+    int32_t* mark;       // [n] 1: taught by the rounds this chunk (fit_learner returns at once)
+    int32_t* hdr;        // [4]: wide learners of the chunk, how many of them have consumed their samples, -, -
+    int32_t* list;       // [n] slot -> listed learner
+    long long* cur;      // [n] the next row to decide; with pend: the mistaken row, whose kernel column is in the K_f row
+    long long* end;      // [n] one past the learner's last row of the chunk
+    int32_t* pend;       // [n] 1: a mistake waits for its mat-vec and finish
+    int32_t* grew;       // [n] 1: the round's update inserted: Kinv still needs its rank-1 update
+    int32_t* gm;         // [n] dictionary size before that insertion
+    double* gdelta;      // [n] its delta
+    long long* mvbase;   // [n + 1] prefix sums of the mat-vec work (tiles) of the learners with a pending mistake
+    long long* r1base;   // [n + 1] prefix sums of the rank-1 work (16-row units) of the learners that inserted
+    double* wf;          // [n][window] the scores of the window scan
+    unsigned long long* info;  // [4] kb_fit_wide_info
+    int32_t min_m, window;
+};
+
+struct WideArgs {
+    FitArgs F;
+    FitWide W;
+    int32_t n, nw;  // listed learners; wide learners of the chunk (0 until the host has read it: the classification)
+};
+
+__global__ __launch_bounds__(1024) void fit_wide_classify_kernel(WideArgs A);  // kb_fit_wide.hip
 
 }  // namespace kb
 
 // what kb_fit / kb_score keep on the handle: the counters of the last calls and their kernel timing
 struct kb_fit_state {
-    unsigned long long* d_work = nullptr;  // [8]: [0..3] the last kb_fit's samples, mistakes, insertions, kernel evaluations; [4] the last kb_score's
+    unsigned long long* d_work = nullptr;  // [12]: [8..11] the last kb_fit's kb_fit_wide_info; [0..3] the last kb_fit's samples, mistakes, insertions, kernel evaluations; [4] the last kb_score's
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    int32_t* h_wide = nullptr;             // pinned [4]: where the rounds' "wide learners, done" words are copied for the host (kb_fit_wide.hip)
     EventSpans fit_spans, score_spans;     // a pair per launch of the last call, when kernel timing was on at the call
     double fit_ms = 0.0, score_ms = 0.0;   // their sums, once drained (kb_fit_time_ms)
 };
@@ -233,6 +270,7 @@ static void kb_fit_release(kb_handle* k) {
     if (p->d_work) (void)hipFree(p->d_work);
     if (p->ev_in) (void)hipEventDestroy(p->ev_in);
     if (p->ev_out) (void)hipEventDestroy(p->ev_out);
+    if (p->h_wide) (void)hipHostFree(p->h_wide);
     p->fit_spans.release();
     p->score_spans.release();
     delete p;
@@ -243,8 +281,8 @@ static int kb_fit_prepare(kb_handle* k) {
     if (k->fit) return RS_OK;
     kb_fit_state* p = new kb_fit_state();
     k->fit = p;  // (kb_destroy frees whatever was allocated)
-    HIPCHK(k, hipMalloc((void**)&p->d_work, sizeof(unsigned long long) * 8));
-    HIPCHK(k, hipMemsetAsync(p->d_work, 0, sizeof(unsigned long long) * 8, k->stream));
+    HIPCHK(k, hipMalloc((void**)&p->d_work, sizeof(unsigned long long) * 12));
+    HIPCHK(k, hipMemsetAsync(p->d_work, 0, sizeof(unsigned long long) * 12, k->stream));
     return RS_OK;
 }
 
@@ -263,6 +301,11 @@ struct FitStage {
         return p;
     }
 };
+
+// kb_fit's chip-wide rounds (kb_fit_wide.hip): the bytes their state adds to the staged block, its arrays, and the rounds of one chunk
+static size_t kb_fit_wide_bytes(kb_handle* k, int32_t n);
+static void kb_fit_wide_take(kb_handle* k, FitStage& st, int32_t n, kb::FitWide* W);
+static int kb_fit_wide_rounds(kb_handle* k, kb::WideArgs& wa, int32_t chunk);
 
 // the checks kb_fit and kb_score share: the sample ranges.  *rows = first[n] - first[0]
 static int kb_fit_ranges(kb_handle* k, const char* who, const int64_t* first, int32_t n, int64_t* rows) {
@@ -340,9 +383,12 @@ extern "C" int kb_fit(kb_handle* k, const int32_t* task, int32_t n, const int64_
     for (int32_t i = 0; i <= n; ++i) rel[(size_t)i] = (long long)(first[i] - base);
     const size_t R = (size_t)rows;
     FitStage st;
+    // kb_set_fit_wide: learners with large dictionaries are taught chunk by chunk in chip-wide rounds (kb_fit_wide.hip); Projectron++
+    // keeps the one-workgroup loop whatever the setting
+    const bool wide = k->fit_wide_min >= 2 && k->alg != KB_ALG_PROJECTRON_PLUS;
     const size_t bytes = FitStage::pad(sizeof(int32_t) * (size_t)n) + FitStage::pad(sizeof(long long) * ((size_t)n + 1)) +
                          FitStage::pad(sizeof(double) * KB_DMAX * R) + FitStage::pad(R) + 3 * FitStage::pad(sizeof(int32_t) * R) +
-                         2 * FitStage::pad(sizeof(double) * R);
+                         2 * FitStage::pad(sizeof(double) * R) + (wide ? kb_fit_wide_bytes(k, n) : 0);
     HIPCHK(k, hipMalloc((void**)&st.base, bytes));
     kb::FitArgs a;
     memset(&a, 0, sizeof a);
@@ -364,6 +410,14 @@ extern "C" int kb_fit(kb_handle* k, const int32_t* task, int32_t n, const int64_
     a.chunk = chunk;
     a.work = p->d_work;
     a.alg = k->alg;
+    kb::WideArgs wa;
+    memset(&wa, 0, sizeof wa);
+    if (wide) {
+        kb_fit_wide_take(k, st, n, &wa.W);
+        wa.W.info = p->d_work + 8;
+        wa.n = n;
+        a.wide = wa.W.mark;
+    }
     // behind whatever is queued on either of the handle's streams
     if (k->side && (rc = stream_after(k, &p->ev_in, k->side, k->stream)) != RS_OK) return rc;
     HIPCHK(k, hipMemcpyAsync(d_task, task, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, k->stream));
@@ -371,6 +425,7 @@ extern "C" int kb_fit(kb_handle* k, const int32_t* task, int32_t n, const int64_
     HIPCHK(k, hipMemcpyAsync(d_x, x + (size_t)base * KB_DMAX, sizeof(double) * KB_DMAX * R, hipMemcpyHostToDevice, k->stream));
     HIPCHK(k, hipMemcpyAsync(d_y, y + base, R, hipMemcpyHostToDevice, k->stream));
     HIPCHK(k, hipMemsetAsync(p->d_work, 0, sizeof(unsigned long long) * 4, k->stream));
+    HIPCHK(k, hipMemsetAsync(p->d_work + 8, 0, sizeof(unsigned long long) * 4, k->stream));
     p->fit_spans.on = k->spans.on;
     p->fit_spans.reset();
     p->fit_ms = 0.0;
@@ -378,11 +433,16 @@ extern "C" int kb_fit(kb_handle* k, const int32_t* task, int32_t n, const int64_
         a.from = (long long)from;
         hipEvent_t e;
         HIPCHK(k, p->fit_spans.begin(k->stream, 0, &e));
+        if (wide) {  // which of the listed learners the rounds teach this chunk: decided on the device, from K.m
+            wa.F = a;
+            hipLaunchKernelGGL(kb::fit_wide_classify_kernel, dim3(1), dim3(1024), 0, k->stream, wa);
+        }
         if (a.alg == KB_ALG_PROJECTRON_PLUS)
             hipLaunchKernelGGL(kb::fit_plus_kernel, dim3((unsigned)n), dim3(256), 0, k->stream, a);
         else
             hipLaunchKernelGGL(kb::fit_kernel, dim3((unsigned)n), dim3(256), 0, k->stream, a);
         if (e) HIPCHK(k, hipEventRecord(e, k->stream));
+        if (wide && (rc = kb_fit_wide_rounds(k, wa, chunk)) != RS_OK) return rc;
     }
     HIPCHK(k, hipGetLastError());
     if (y_pred) HIPCHK(k, hipMemcpyAsync(y_pred + base, a.y_pred, sizeof(int32_t) * R, hipMemcpyDeviceToHost, k->stream));

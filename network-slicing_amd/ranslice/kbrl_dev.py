@@ -298,6 +298,30 @@ class VecKBRL:
         self._check(self.L.kb_fit_time_ms(self.h, ms, w))
         return dict(fit_ms=ms[0], score_ms=ms[1], samples=int(w[0]), mistakes=int(w[1]), insertions=int(w[2]), kernel_evals=int(w[3]))
 
+    def set_fit_wide(self, min_landmarks, window=0):
+        """which learners fit() teaches by chip-wide rounds (kb_set_fit_wide): 0 (the default) none -- fit() is one workgroup per
+        learner; min_landmarks >= 2: every listed learner whose dictionary holds that many landmarks at the start of a chunk is
+        taught that chunk in rounds that spread each mistake's mat-vec and rank-1 update over the whole device.  Every result is
+        bit for bit the narrow path's.  window: samples per learner a round scores ahead (1 .. 256; 0: the default, 64).  A
+        property of this handle, like the algorithm: not saved, not carried over by fork_from / deploy / load_agents.  Ignored in
+        'projectron_plus' mode.  Refused (RS_ESTATE) on deployed, by-reference and shared-dictionary handles; 1 and negative
+        values are refused (RS_EINVAL)."""
+        self._check(self.L.kb_set_fit_wide(self.h, int(min_landmarks), int(window)))
+
+    @property
+    def fit_wide(self):
+        """(min_landmarks, window) of set_fit_wide (kb_get_fit_wide); (0, 0) while the wide path is off"""
+        a, b = C.c_int32(), C.c_int32()
+        self._check(self.L.kb_get_fit_wide(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def fit_wide_info(self):
+        """what the rounds of the last fit did (kb_fit_wide_info): dict(samples, matvecs, tiles = Kinv tiles of 32,768 bytes those
+        mat-vecs read, scan_evals = samples scored x landmarks of the window scans); zeros when nothing went wide"""
+        w = (C.c_uint64 * 4)()
+        self._check(self.L.kb_fit_wide_info(self.h, w))
+        return dict(samples=int(w[0]), matvecs=int(w[1]), tiles=int(w[2]), scan_evals=int(w[3]))
+
     def learner(self, e, s, with_kinv=False):
         m = C.c_int32()
         self._check(self.L.kb_get_learner(self.h, e, s, C.byref(m), None, None, None))
@@ -669,6 +693,10 @@ class SharedVecKBRL(VecKBRL):
         (kb_fit answers RS_ESTATE); score() works.  Teach a per-replica VecKBRL and to_shared() it instead."""
         raise _lib.RanSliceError(_lib.RS_ESTATE, 'fit: shared-dictionary handles are not supported: several learners map to one '
                                  'dictionary (fit a per-replica VecKBRL, then to_shared)')
+
+    def set_fit_wide(self, min_landmarks, window=0):
+        """refused, as kb_set_fit_wide refuses it: a shared-dictionary handle does not learn through fit()"""
+        raise _lib.RanSliceError(_lib.RS_ESTATE, 'set_fit_wide: a shared-dictionary handle does not learn through fit')
 
     @staticmethod
     def unique_id():
