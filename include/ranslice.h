@@ -720,19 +720,33 @@ int kb_get_algorithm(kb_handle* k, int32_t* alg);
  * value, dictionary (landmarks, coefficients, all of Kinv), tie counter, statistic and flag, and kb_fit_time_ms's work[4], are BIT
  * FOR BIT those of the narrow path, whatever min_landmarks, window and chunk; only the time differs.  window: samples per learner
  * a round scores ahead, 1 .. 256, 0 = the default (64).  The value 1 for min_landmarks is refused: the float32 regime of a single
- * landmark stays in the narrow path.  In Projectron++ mode (kb_set_algorithm) kb_fit takes the narrow path whatever the setting
- * -- nearly every sample needs its mat-vec there, and the margin rule is one piece -- and kb_fit_wide_info reports zeros.
+ * landmark stays in the narrow path.  In Projectron++ mode (kb_set_algorithm) kb_fit takes the narrow path whatever this setting
+ * says, and kb_fit_wide_info reports zeros, UNLESS kb_set_fit_wide_plus(k, 1) has been called as well (below).
  * Like the algorithm, the setting is host state of the HANDLE: not part of kb_save_state blobs or agent files, not carried over
  * by kb_fork, kb_deploy, kb_import_agents, kb_share or kb_unshare.  Off by default.
  * kb_set_fit_wide: RS_EINVAL for a negative value, for min_landmarks = 1 and for a window above 256; RS_ESTATE on an
  * inference-only, a by-reference or a shared-dictionary handle (they do not learn through kb_fit).
  * kb_fit_wide_info: of the last kb_fit on the handle -- work[0] samples taught by rounds, work[1] mat-vecs the rounds ran (the
- * mistakes taught there), work[2] tiles of Kinv those mat-vecs read (n_b (n_b + 1) / 2 each, n_b = ceil(m / 64); 32,768 bytes a
- * tile), work[3] kernel evaluations of the window scans (samples scored x landmarks; the rescans after a mistake are counted
- * here and not in kb_fit_time_ms's work[3]). */
+ * mistakes taught there; in Projectron++ mode every sample of branches 1-4 taught there, branch 4 included), work[2] tiles of Kinv
+ * those mat-vecs read (n_b (n_b + 1) / 2 each, n_b = ceil(m / 64); 32,768 bytes a tile), work[3] kernel evaluations of the window
+ * scans (samples scored x landmarks; the rescans after a mistake -- in Projectron++ mode after any sample of branches 1-4 -- are
+ * counted here and not in kb_fit_time_ms's work[3]).
+ *
+ * kb_set_fit_wide_plus(k, on): whether the rounds also teach in Projectron++ mode.  on = 0 (the default): as above, narrow.
+ * on = 1: while the handle is in Projectron++ mode and kb_set_fit_wide's min_landmarks is 2 or more, learners holding that many
+ * landmarks at the start of a chunk are taught by the same rounds; a round then stops at the first sample with not (y f >= 1),
+ * every such sample -- mistake or margin -- gets its mat-vec over the whole chip, and the margin rule (branches 3, 4) follows it
+ * as it follows the one-workgroup mat-vec.  The bits are the narrow path's, as for Projectron.  After a branch 4 (nothing
+ * written) the next round scans again; no score of a window is reused.  In Projectron mode the switch has no effect.  Host state
+ * of the handle like kb_set_fit_wide's: not saved, not carried over.  A switch of its own, so that kb_set_fit_wide means what it
+ * meant.  RS_EINVAL for any value but 0 and 1; RS_ESTATE on an inference-only, a by-reference or a shared-dictionary handle.
+ * Measured on G17's stream in Projectron++ mode and on G18's rev stream; not measured: hardware counters, more
+ * than eight large learners in one call, thresholds below 64. */
 int kb_set_fit_wide(kb_handle* k, int32_t min_landmarks, int32_t window);
 int kb_get_fit_wide(kb_handle* k, int32_t* min_landmarks, int32_t* window);
 int kb_fit_wide_info(kb_handle* k, uint64_t work[4]);   /* of the last kb_fit */
+int kb_set_fit_wide_plus(kb_handle* k, int32_t on);
+int kb_get_fit_wide_plus(kb_handle* k, int32_t* on);
 
 #ifdef __cplusplus
 }

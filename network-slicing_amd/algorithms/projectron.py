@@ -93,7 +93,8 @@ class Projectron:
         [len(X)].  The cached (f, k) of predict is invalid afterwards: call predict before the next update.
         wide: None keeps the agent's setting; min_landmarks, or (min_landmarks, window), is handed to VecKBRL.set_fit_wide first
         and stays in force: from that dictionary size on the samples are taught by chip-wide rounds -- same bits, less time once
-        the dictionary holds hundreds of landmarks (0 turns it off again)."""
+        the dictionary holds hundreds of landmarks (0 turns it off again).  A ProjectronPlus is taught by those rounds only while its
+        attribute wide_plus is true (VecKBRL.set_fit_wide_plus)."""
         X = np.asarray(X, dtype=np.float64)
         X = X.reshape(1, -1) if X.ndim == 1 else X
         if X.shape[0] == 0:
@@ -101,6 +102,8 @@ class Projectron:
         self._ensure(X[0])
         if wide is not None:
             self._agent.set_fit_wide(*(wide if isinstance(wide, (tuple, list)) else (wide,)))
+        if isinstance(self, ProjectronPlus):
+            self._agent.set_fit_wide_plus(bool(self.wide_plus))
         out = self._agent.fit([(self._e, self._s)], [X], [np.asarray(y).reshape(-1)])
         self.f = float(out['f'][0][-1])
         return out['y_pred'][0]
@@ -128,8 +131,14 @@ class ProjectronPlus(Projectron):
     0 < y f < 1 -- a scaled projection that never adds a landmark.  The private one-learner agent runs in Projectron++ mode
     (kb_set_algorithm); predict, update, fit, decision_function and Kinv work as on Projectron.  Not accepted by
     kbrl_control.KBRL_Control, whose closed loop implements Projectron's rule: fit logged control steps instead
-    (ranslice.kbrl_dev.augmented_samples + VecKBRL.fit)."""
+    (ranslice.kbrl_dev.augmented_samples + VecKBRL.fit).
+    wide_plus (a plain attribute, False by default): whether fit(..., wide=...) lets the chip-wide rounds teach this learner too;
+    fit hands it to VecKBRL.set_fit_wide_plus before every call.  Off, fit keeps the one-workgroup path whatever `wide` says."""
     ALGORITHM = 'projectron_plus'
+
+    def __init__(self, kernel, eta=0.1, capacity=4096):
+        super().__init__(kernel, eta=eta, capacity=capacity)
+        self.wide_plus = False
 
     def _bind(self, agent, e, s):
         if agent.algorithm != self.ALGORITHM:

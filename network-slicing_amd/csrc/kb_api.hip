@@ -73,6 +73,7 @@ struct kb_handle {
     bool frozen = false;           // an inference-only handle (kb_deploy): no Kinv behind its dictionaries, learning permanently off
     int32_t alg = KB_ALG_PROJECTRON;  // kb_set_algorithm: the rule of the next kb_update / kb_fit; host state of the handle, never copied or saved
     int32_t fit_wide_min = 0, fit_wide_window = 0;  // kb_set_fit_wide: host state of the handle like alg, never copied or saved (kb_fit_wide.hip)
+    int32_t fit_wide_plus = 0;                      // kb_set_fit_wide_plus: 1 = the rounds also teach in Projectron++ mode; host state as well
     // kb_fork / kb_deploy into this handle (kb_fork.hip)
     hipEvent_t ev_fork_in = nullptr, ev_fork_out = nullptr;
     int32_t* d_fork_idx = nullptr;   // [n_envs] source agent of every agent

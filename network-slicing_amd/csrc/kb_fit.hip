@@ -234,7 +234,7 @@ struct FitWide {
     int32_t* list;       // [n] slot -> listed learner
     long long* cur;      // [n] the next row to decide; with pend: the mistaken row, whose kernel column is in the K_f row
     long long* end;      // [n] one past the learner's last row of the chunk
-    int32_t* pend;       // [n] 1: a mistake waits for its mat-vec and finish
+    int32_t* pend;       // [n] 1: a mistake (Projectron++: or a sample inside the margin) waits for its mat-vec and finish
     int32_t* grew;       // [n] 1: the round's update inserted: Kinv still needs its rank-1 update
     int32_t* gm;         // [n] dictionary size before that insertion
     double* gdelta;      // [n] its delta
@@ -384,8 +384,8 @@ extern "C" int kb_fit(kb_handle* k, const int32_t* task, int32_t n, const int64_
     const size_t R = (size_t)rows;
     FitStage st;
     // kb_set_fit_wide: learners with large dictionaries are taught chunk by chunk in chip-wide rounds (kb_fit_wide.hip); Projectron++
-    // keeps the one-workgroup loop whatever the setting
-    const bool wide = k->fit_wide_min >= 2 && k->alg != KB_ALG_PROJECTRON_PLUS;
+    // keeps the one-workgroup loop whatever that setting, unless kb_set_fit_wide_plus is on as well
+    const bool wide = k->fit_wide_min >= 2 && (k->alg != KB_ALG_PROJECTRON_PLUS || k->fit_wide_plus);
     const size_t bytes = FitStage::pad(sizeof(int32_t) * (size_t)n) + FitStage::pad(sizeof(long long) * ((size_t)n + 1)) +
                          FitStage::pad(sizeof(double) * KB_DMAX * R) + FitStage::pad(R) + 3 * FitStage::pad(sizeof(int32_t) * R) +
                          2 * FitStage::pad(sizeof(double) * R) + (wide ? kb_fit_wide_bytes(k, n) : 0);

@@ -1,7 +1,7 @@
 // kb_fit_wide.hip -- kb_fit's chip-wide rounds for learners that hold large dictionaries (kb_set_fit_wide).
 // #included by rs_api.hip after kb_fit.hip.  It adds kernels of its own and shares only device functions with kb_kbrl.hip and
 // kb_fit.hip: score_queries (kb_score's body), predict_column, tie_draw, stretch_of, matvec_tri_tiles_lds, matvec_tri_combine_wide,
-// finish_update(..., defer_rank1 = true) and rank1_units.
+// finish_update(..., defer_rank1 = true), margin_update and rank1_units.
 //
 // fit_learner runs a learner's samples on ONE workgroup; every mistake then costs an O(m^2) mat-vec and, when it inserts, an O(m^2)
 // rank-1 update of Kinv that this workgroup streams alone.  Here a chunk's learners whose dictionaries hold min_landmarks or more
@@ -24,6 +24,14 @@
 // partial sums have a slot of their own) and the combine, finish_update and rank1_units are the functions apply_update's path
 // calls or is held to (tests/test_gpu_update_chain.py).  Dictionaries here hold two landmarks or more (kb_set_fit_wide refuses 1),
 // so the float32 regime of a single landmark stays with fit_learner.
+// PROJECTRON++ (kb_set_fit_wide_plus; FitArgs.alg) goes through the same seven launches.  The decide kernel stops at the first sample
+// that apply_update_plus would not answer with branch 0, not (y f >= 1) in its own expression; every such sample, mistake or
+// margin, gets its mat-vec; the finish kernel forms margin = y f from the f the decide kernel left in F.f and continues a mistake
+// with finish_update as above and a sample inside the margin with margin_update, apply_update_plus's own tail (kb_kbrl.hip):
+// branch 3 moves the coefficients and bumps the version, branch 4 writes nothing.  Neither inserts, so the rank-1 line is empty for
+// them.  After branch 4 the dictionary is what it was and the rest of the window's scores would still hold; they are NOT used
+// again -- the next round scans from its cursor like any other, so a slot needs no window origin and the scan kernel no second
+// mode (what the rescans cost is kb_fit_wide_info's work[3]; tests/fit_wide_plus_mirror.py's counters define it).
 // NO kernel waits for another: every one ends whatever the others do, and one with nothing to do returns at once.  Every round
 // moves each pending learner at least one sample on, so a chunk needs at most `chunk` rounds; the host enqueues KB_FIT_ROUNDS of
 // them, reads back how many learners are done, and gives up with RS_EHIP if the bound is ever passed.  The rounds' state lives in
@@ -123,14 +131,18 @@ __global__ __launch_bounds__(256) void fit_wide_decide_kernel(WideArgs A) {
     const int m = K.m[task];
     const int cnt = (int)(end - cur < W.window ? end - cur : W.window);
     const double* wf = W.wf + (size_t)j * W.window;
+    const bool plus = F.alg == KB_ALG_PROJECTRON_PLUS;  // (kb_set_fit_wide_plus: the margin rule's rounds)
     // the first sample of the window that fit_learner would not pass by: a mistake f y <= 0 (an exact tie is one), or an f without
-    // a sign (never met: it would draw and update nothing)
+    // a sign (never met: it would draw and update nothing).  Projectron++: the first that apply_update_plus would not answer with
+    // branch 0, in its own words -- not (y f >= 1): a mistake, a sample inside the margin, or a NaN
     if (threadIdx.x == 0) sm.ired[1] = cnt;
     __syncthreads();
     double fw = 0.0;
     if ((int)threadIdx.x < cnt) {
         fw = wf[threadIdx.x];
-        if (fw * (double)F.y[cur + threadIdx.x] <= 0.0 || !(fw > 0.0 || fw < 0.0)) atomicMin(&sm.ired[1], (int)threadIdx.x);
+        const bool stop = plus ? !((double)F.y[cur + threadIdx.x] * fw >= 1.0)
+                               : fw * (double)F.y[cur + threadIdx.x] <= 0.0 || !(fw > 0.0 || fw < 0.0);
+        if (stop) atomicMin(&sm.ired[1], (int)threadIdx.x);
     }
     __syncthreads();
     const int k = sm.ired[1];
@@ -161,8 +173,8 @@ __global__ __launch_bounds__(256) void fit_wide_decide_kernel(WideArgs A) {
             F.y_pred[r] = yp;
             F.f[r] = f;
         }
-        if (f * (double)F.y[r] <= 0.0) {
-            pend = 1;  // the cursor stays on it: the finish kernel moves it on
+        if (plus ? !((double)F.y[r] * f >= 1.0) : f * (double)F.y[r] <= 0.0) {
+            pend = 1;  // the cursor stays on it: the finish kernel moves it on (and reads its f from F.f[r])
         } else {
             if (threadIdx.x == 0) {
                 F.branch[r] = 0;
@@ -257,9 +269,18 @@ __global__ __launch_bounds__(256) void fit_wide_finish_kernel(WideArgs A) {
     const double t_last = sm.x[d - 1];
     int branch = 0;
     double delta = 0.0;
-    const int m_new = finish_update(D, K, task, env, m, d, sm.x, t_last, grid_index(t_last, D.n_prbs), y, sm, &branch, &delta, nullptr, true);
+    // Projectron++: apply_update_plus behind its mat-vec -- margin = y f of the f the decide kernel left for this sample; a mistake
+    // continues as Projectron's, a sample inside the margin with the margin rule (branches 3, 4: no insertion, no shell, and a
+    // version bump only when the coefficients move).  The rounds hold m >= 2, so neither meets the float32 regime.
+    const double margin = F.alg == KB_ALG_PROJECTRON_PLUS ? (double)y * F.f[r] : 0.0;
+    int m_new;
+    if (margin <= 0.0)
+        m_new = finish_update(D, K, task, env, m, d, sm.x, t_last, grid_index(t_last, D.n_prbs), y, sm, &branch, &delta, nullptr, true);
+    else
+        m_new = margin_update(D, K, sh, task, m, y, margin, sm, &branch, &delta);
     if (threadIdx.x == 0) {
         const unsigned long long grow = branch == 2 && m_new > m ? 1 : 0;
+        const unsigned long long mist = branch >= 1 && branch <= 3 ? 1 : 0;  // a mistake changed the dictionary: not branch 4
         F.branch[r] = branch;
         F.delta[r] = delta;
         F.m_after[r] = m_new;
@@ -272,10 +293,10 @@ __global__ __launch_bounds__(256) void fit_wide_finish_kernel(WideArgs A) {
         W.pend[j] = 0;
         W.cur[j] = r + 1;
         K.stats[(size_t)task * 4 + 0] += 1;
-        K.stats[(size_t)task * 4 + 1] += 1;
+        K.stats[(size_t)task * 4 + 1] += mist;
         K.stats[(size_t)task * 4 + 2] += grow;
         atomicAdd(&F.work[0], 1ull);
-        atomicAdd(&F.work[1], 1ull);
+        if (mist) atomicAdd(&F.work[1], 1ull);
         if (grow) atomicAdd(&F.work[2], 1ull);
         atomicAdd(&F.work[3], (unsigned long long)m);
         const unsigned long long nb = (unsigned long long)((m + 63) >> 6);
@@ -397,6 +418,31 @@ extern "C" int kb_get_fit_wide(kb_handle* k, int32_t* min_landmarks, int32_t* wi
     if (!k || !min_landmarks || !window) return RS_EINVAL;
     *min_landmarks = k->fit_wide_min;
     *window = k->fit_wide_window;
+    return RS_OK;
+}
+
+/* Whether the rounds also teach in Projectron++ mode (ranslice.h): host state of the handle, beside kb_set_fit_wide's.
+   It has an effect only while the handle is in Projectron++ mode and kb_set_fit_wide's min_landmarks is 2 or more. */
+extern "C" int kb_set_fit_wide_plus(kb_handle* k, int32_t on) {
+    if (!k) return RS_EINVAL;
+    if (on != 0 && on != 1) {
+        k->err = "kb_set_fit_wide_plus: on = " + std::to_string(on) + " (0: Projectron++ keeps the narrow path, the default; 1: the rounds teach it too)";
+        return RS_EINVAL;
+    }
+    if (k->frozen || k->ref || k->D.shared) {
+        k->err = std::string("kb_set_fit_wide_plus: ") +
+                 (k->ref ? "a by-reference handle (kb_deploy_ref)" : k->frozen ? "an inference-only handle (kb_deploy, kb_import_agents)"
+                                                                               : "a shared-dictionary handle") +
+                 " does not learn through kb_fit";
+        return RS_ESTATE;
+    }
+    k->fit_wide_plus = on;
+    return RS_OK;
+}
+
+extern "C" int kb_get_fit_wide_plus(kb_handle* k, int32_t* on) {
+    if (!k || !on) return RS_EINVAL;
+    *on = k->fit_wide_plus;
     return RS_OK;
 }
 

@@ -1304,6 +1304,40 @@ __device__ int apply_update(const KbDev& D, const KbState& K, int dict, int err_
     return finish_update(D, K, dict, err_env, m, d, x, t_last, a_last, y, sm, branch, delta_out, saturated, false);
 }
 
+// The margin rule of ProjectronPlus.update (projectron.py:74-85) that follows d* = Kinv K_f (DS row), for 0 < margin = y f < 1
+// (so f != 0 and m >= 1): delta, the slack, and the scaled projection (branch 3) or nothing (branch 4).  Returns m: it never
+// inserts.  apply_update_plus's tail, and what fit_wide_finish_kernel (kb_fit_wide.hip) runs behind the chip-wide mat-vec -- ONE
+// statement of the rule for the one-workgroup path and the rounds.  Inlined, so that apply_update_plus compiles to what it was.
+__device__ __forceinline__ int margin_update(const KbDev& D, const KbState& K, const uint64_t* sh, int dict, int m, int y, double margin,
+                                             Lds& sm, int* branch, double* delta_out) {
+    const double delta = residual_delta(K, sh, m, sm);
+    *delta_out = delta;
+    double norm = 1.0 - delta;  // Kii - delta
+    norm = norm > 0.0 ? norm : 0.0;
+    const double loss = m == 1 ? (double)(1.0f - (float)margin) : 1.0 - margin;
+    const double slack = loss - delta / D.eta;
+    if (!(slack > 0.0)) {
+        *branch = 4;
+        return m;
+    }
+    *branch = 3;
+    if (threadIdx.x == 0) atomicAdd(&K.ver[dict], 1);  // the coefficients change: stored scores are stale
+    double alpha = loss / norm;
+    alpha = 1.0 < alpha ? 1.0 : alpha;
+    const double by_slack = 2.0 * slack / norm;
+    alpha = by_slack < alpha ? by_slack : alpha;
+    const double ay = alpha * (double)y;
+    for (int j = threadIdx.x; j < m; j += blockDim.x) {
+        double* P = vec_page(K, sh, j >> 6);
+        const int l = j & 63;
+        double nc = P[KB_ROW_CO * KB_CH + l] + ay * P[KB_ROW_DS * KB_CH + l];
+        if (m == 1) nc = (double)(float)nc;
+        P[KB_ROW_CO * KB_CH + l] = nc;
+    }
+    __syncthreads();
+    return m;
+}
+
 // ProjectronPlus.update (projectron.py:71-107) for the same x, whose f the caller holds (kb_predict's, or predict_column's of this
 // launch).  margin = y f decides: >= 1 nothing (branch 0); <= 0 Projectron's update, apply_update's two steps (branches 1, 2); in between
 // the margin rule (projectron.py:74-85): d* and delta as above, loss = 1 - margin, and when loss - delta / eta > 0 the scaled
@@ -1339,33 +1373,7 @@ __device__ int apply_update_plus(const KbDev& D, const KbState& K, int dict, int
             matvec_colsum<2>(K, sh, m);
     }
     if (margin <= 0.0) return finish_update(D, K, dict, err_env, m, d, x, t_last, a_last, y, sm, branch, delta_out, nullptr, false);
-    // (0 < margin: f != 0, so m >= 1)
-    const double delta = residual_delta(K, sh, m, sm);
-    *delta_out = delta;
-    double norm = 1.0 - delta;  // Kii - delta
-    norm = norm > 0.0 ? norm : 0.0;
-    const double loss = m == 1 ? (double)(1.0f - (float)margin) : 1.0 - margin;
-    const double slack = loss - delta / D.eta;
-    if (!(slack > 0.0)) {
-        *branch = 4;
-        return m;
-    }
-    *branch = 3;
-    if (threadIdx.x == 0) atomicAdd(&K.ver[dict], 1);  // the coefficients change: stored scores are stale
-    double alpha = loss / norm;
-    alpha = 1.0 < alpha ? 1.0 : alpha;
-    const double by_slack = 2.0 * slack / norm;
-    alpha = by_slack < alpha ? by_slack : alpha;
-    const double ay = alpha * (double)y;
-    for (int j = threadIdx.x; j < m; j += blockDim.x) {
-        double* P = vec_page(K, sh, j >> 6);
-        const int l = j & 63;
-        double nc = P[KB_ROW_CO * KB_CH + l] + ay * P[KB_ROW_DS * KB_CH + l];
-        if (m == 1) nc = (double)(float)nc;
-        P[KB_ROW_CO * KB_CH + l] = nc;
-    }
-    __syncthreads();
-    return m;
+    return margin_update(D, K, sh, dict, m, y, margin, sm, branch, delta_out);
 }
 
 struct CtlArgs {

@@ -27,6 +27,7 @@ KB_EXPORTS = (
     'kb_fit', 'kb_score', 'kb_fit_time_ms',
     'kb_set_algorithm', 'kb_get_algorithm',
     'kb_set_fit_wide', 'kb_get_fit_wide', 'kb_fit_wide_info',
+    'kb_set_fit_wide_plus', 'kb_get_fit_wide_plus',
 )
 
 EXPORTS = (
@@ -218,6 +219,8 @@ def load(dev=None):
     L.kb_set_fit_wide.argtypes = [vp, C.c_int32, C.c_int32]
     L.kb_get_fit_wide.argtypes = [vp, ip, ip]
     L.kb_fit_wide_info.argtypes = [vp, up]
+    L.kb_set_fit_wide_plus.argtypes = [vp, C.c_int32]
+    L.kb_get_fit_wide_plus.argtypes = [vp, ip]
     for name in EXPORTS:
         if name not in ('rs_last_error', 'rs_destroy', 'kb_last_error', 'kb_destroy'):
             getattr(L, name).restype = C.c_int

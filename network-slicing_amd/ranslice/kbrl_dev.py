@@ -304,9 +304,25 @@ class VecKBRL:
         taught that chunk in rounds that spread each mistake's mat-vec and rank-1 update over the whole device.  Every result is
         bit for bit the narrow path's.  window: samples per learner a round scores ahead (1 .. 256; 0: the default, 64).  A
         property of this handle, like the algorithm: not saved, not carried over by fork_from / deploy / load_agents.  Ignored in
-        'projectron_plus' mode.  Refused (RS_ESTATE) on deployed, by-reference and shared-dictionary handles; 1 and negative
-        values are refused (RS_EINVAL)."""
+        'projectron_plus' mode unless set_fit_wide_plus() is on too.  Refused (RS_ESTATE) on deployed, by-reference and
+        shared-dictionary handles; 1 and negative values are refused (RS_EINVAL)."""
         self._check(self.L.kb_set_fit_wide(self.h, int(min_landmarks), int(window)))
+
+    def set_fit_wide_plus(self, on=True):
+        """whether the chip-wide rounds of set_fit_wide also teach in 'projectron_plus' mode (kb_set_fit_wide_plus).  Off (the
+        default): that mode keeps the one-workgroup path whatever set_fit_wide says.  On: learners that hold set_fit_wide's
+        min_landmarks at the start of a chunk are taught by rounds there too -- every mistake AND every sample inside the margin
+        has its mat-vec spread over the device, with the narrow path's bits.  No effect in 'projectron' mode or while
+        set_fit_wide is off.  A property of this handle: not saved, not carried over.  Refused (RS_ESTATE) on deployed,
+        by-reference and shared-dictionary handles."""
+        self._check(self.L.kb_set_fit_wide_plus(self.h, int(on)))
+
+    @property
+    def fit_wide_plus(self):
+        """True while set_fit_wide_plus is on (kb_get_fit_wide_plus)"""
+        a = C.c_int32()
+        self._check(self.L.kb_get_fit_wide_plus(self.h, C.byref(a)))
+        return bool(a.value)
 
     @property
     def fit_wide(self):
@@ -697,6 +713,10 @@ class SharedVecKBRL(VecKBRL):
     def set_fit_wide(self, min_landmarks, window=0):
         """refused, as kb_set_fit_wide refuses it: a shared-dictionary handle does not learn through fit()"""
         raise _lib.RanSliceError(_lib.RS_ESTATE, 'set_fit_wide: a shared-dictionary handle does not learn through fit')
+
+    def set_fit_wide_plus(self, on=True):
+        """refused, as kb_set_fit_wide_plus refuses it: a shared-dictionary handle does not learn through fit()"""
+        raise _lib.RanSliceError(_lib.RS_ESTATE, 'set_fit_wide_plus: a shared-dictionary handle does not learn through fit')
 
     @staticmethod
     def unique_id():

@@ -18,7 +18,12 @@ Legs:
   fleet     G9's d4 stream to 4,096 learners of one call on this build, the setting off and on at 320 (everything stays narrow:
             what the classification and its one look per chunk cost), three rounds alternating.
 
-  python tools/fit_wide_record.py --parent-root DIR [--only compare|sweep|eight|fleet]
+  plus      Projectron++ mode (kb_set_algorithm; kb_set_fit_wide_plus): G17's sample stream with min_landmarks = 320 and G18's rev
+            stream (2,500 samples to 318 landmarks) with min_landmarks = 64, default window; the parent build (narrow: it has no
+            switch) against this build with both settings on, three rounds alternating; per row the branch counts 0-4, the
+            rounds' mat-vecs and tiles, and the dictionaries' digests, which must be equal between the two builds.
+
+  python tools/fit_wide_record.py --parent-root DIR [--only compare|sweep|eight|fleet|plus]
 """
 import argparse
 import hashlib
@@ -34,6 +39,7 @@ GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 KB_BIG_M = 320
 MINS = (64, 128, 256, 320, 512, 1024)
 WINDOWS = (8, 64, 256)
+PLUS_STREAMS = (('g17_projectron_3000', KB_BIG_M), ('g18_projectron_plus:rev', 64))   # (recording, min_landmarks) of the Projectron++ leg
 
 
 def _paths(root):
@@ -44,6 +50,10 @@ def _paths(root):
 
 def _stream(name):
     import numpy as np
+    if ':' in name:   # a tagged recording, e.g. g18_projectron_plus:rev
+        name, tag = name.split(':')
+        g = np.load(os.path.join(GOLDEN, name + '.npz'))
+        return g[tag + '_x'], g[tag + '_y']
     g = np.load(os.path.join(GOLDEN, name + '.npz'))
     if 'x' in g.files:
         return g['x'], g['y']
@@ -52,8 +62,9 @@ def _stream(name):
     return np.concatenate([g['state'].astype(np.float64), (g['a'].astype(np.float64) / 200)[:, None]], axis=1), g['y']
 
 
-def child(root, name, copies, min_landmarks, window):
-    """one measured kb_fit of `copies` learners, each taught the recording -> one JSON line"""
+def child(root, name, copies, min_landmarks, window, plus=False):
+    """one measured kb_fit of `copies` learners, each taught the recording -> one JSON line.  plus: in Projectron++ mode, and with
+    kb_set_fit_wide_plus on wherever the wide path is (min_landmarks != 0: a build that has the switch)"""
     import numpy as np
     _paths(root)
     from ranslice.kbrl_dev import VecKBRL
@@ -61,11 +72,13 @@ def child(root, name, copies, min_landmarks, window):
     d = xs.shape[1] - 1
 
     def handle(n):
-        ag = VecKBRL(n, [d], 200, capacity=4096, pool_bytes=2 << 30)
+        ag = VecKBRL(n, [d], 200, capacity=4096, pool_bytes=2 << 30, **(dict(algorithm='projectron_plus') if plus else {}))
         ag.reset(np.full((n, 1), 10), np.full((n, 1), 3))
         ag.set_kernel_timing(True)
         if min_landmarks:
             ag.set_fit_wide(min_landmarks, window)
+            if plus:
+                ag.set_fit_wide_plus(True)
         return ag
     warm = handle(1)   # first launches load code objects: both paths, when the setting is on
     if min_landmarks:
@@ -76,7 +89,7 @@ def child(root, name, copies, min_landmarks, window):
     learners = [(e, 0) for e in range(copies)]
     X, Y = [xs] * copies, [ys] * copies
     t0 = time.perf_counter()
-    ag.fit(learners, X, Y)
+    res = ag.fit(learners, X, Y)
     wall = time.perf_counter() - t0
     w = ag.fit_time_ms()
     h = hashlib.sha256()
@@ -88,13 +101,15 @@ def child(root, name, copies, min_landmarks, window):
                landmarks=int(ag.dictionary_sizes().max()), digest=h.hexdigest())
     if min_landmarks:
         out['wide'] = ag.fit_wide_info()
+    if plus:
+        out['branches'] = np.bincount(res['branch'][0], minlength=5).tolist()
     ag.close()
     print(json.dumps(out))
 
 
-def run(root, name, copies=1, min_landmarks=0, window=0, timeout=300):
+def run(root, name, copies=1, min_landmarks=0, window=0, timeout=300, plus=False):
     cmd = ['timeout', '-k', '10', str(timeout), sys.executable, os.path.abspath(__file__), '--child', name, '--root', root,
-           '--copies', str(copies), '--min', str(min_landmarks), '--window', str(window)]
+           '--copies', str(copies), '--min', str(min_landmarks), '--window', str(window)] + (['--plus'] if plus else [])
     p = subprocess.run(cmd, capture_output=True, text=True)
     if p.returncode != 0:
         raise SystemExit('%s failed with status %d\n%s' % (' '.join(cmd), p.returncode, p.stderr[-2000:]))
@@ -107,18 +122,18 @@ def _summary(runs):
         v = [r[k] for r in runs]
         out[k] = dict(median=statistics.median(v), min=min(v), max=max(v))
     out['digests'] = sorted({r['digest'] for r in runs})
-    for k in ('samples', 'mistakes', 'landmarks', 'wide'):
+    for k in ('samples', 'mistakes', 'landmarks', 'wide', 'branches'):
         if k in runs[-1]:
             out[k] = runs[-1][k]
     return out
 
 
-def pair(parent_root, name, copies, min_landmarks, rounds=3, timeout=300):
+def pair(parent_root, name, copies, min_landmarks, rounds=3, timeout=300, plus=False):
     """`rounds` alternating runs of the parent build (narrow) and this build (wide)"""
     a, b = [], []
     for _ in range(rounds):
-        a.append(run(parent_root, name, copies, 0, 0, timeout))
-        b.append(run(ROOT, name, copies, min_landmarks, 0, timeout))
+        a.append(run(parent_root, name, copies, 0, 0, timeout, plus))
+        b.append(run(ROOT, name, copies, min_landmarks, 0, timeout, plus))
     pa, th = _summary(a), _summary(b)
     spread = (pa['wall_ms']['max'] - pa['wall_ms']['min']) + (th['wall_ms']['max'] - th['wall_ms']['min'])
     return dict(parent_narrow=pa, this_wide=th, min_landmarks=min_landmarks, rounds=rounds,
@@ -134,12 +149,13 @@ def main():
     ap.add_argument('--copies', type=int, default=1)
     ap.add_argument('--min', type=int, default=0)
     ap.add_argument('--window', type=int, default=0)
+    ap.add_argument('--plus', action='store_true')
     ap.add_argument('--parent-root')
-    ap.add_argument('--only', choices=['compare', 'sweep', 'eight', 'fleet'])
+    ap.add_argument('--only', choices=['compare', 'sweep', 'eight', 'fleet', 'plus'])
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'fit_wide_record.json'))
     a = ap.parse_args()
     if a.child:
-        return child(a.root, a.child, a.copies, a.min, a.window)
+        return child(a.root, a.child, a.copies, a.min, a.window, a.plus)
     if not a.parent_root:
         raise SystemExit('--parent-root: a checkout of the parent commit with its library built')
     rec = dict(statistic='median and range of three alternating runs (compare, eight, fleet); one run per sweep point',
@@ -186,6 +202,10 @@ def main():
             on.append(run(ROOT, 'g9_projectron', 4096, KB_BIG_M, 0))
         rec['fleet_d4_x_4096'] = dict(setting_off=_summary(off), setting_on_at_320=_summary(on))
         print(json.dumps(rec['fleet_d4_x_4096']), flush=True)
+        save()
+    if a.only in (None, 'plus'):
+        rec['projectron_plus'] = {n: pair(a.parent_root, n, 1, m, timeout=600, plus=True) for n, m in PLUS_STREAMS}
+        print(json.dumps(rec['projectron_plus']), flush=True)
         save()
 
 
