@@ -748,6 +748,38 @@ int kb_fit_wide_info(kb_handle* k, uint64_t work[4]);   /* of the last kb_fit */
 int kb_set_fit_wide_plus(kb_handle* k, int32_t on);
 int kb_get_fit_wide_plus(kb_handle* k, int32_t* on);
 
+/* ---- kb_fit for logs of control steps (csrc/kb_fit_steps.hip): the sample augmentation of kbrl_control.py:103-112
+ * on the device.  agent[i] (all distinct, 0 .. n_envs - 1) owns log rows first[i] .. first[i + 1] - 1, in order (first[0] = 0);
+ * rows may come from anywhere -- one replica's history, several replicas' histories one after the other.  A row is what a
+ * control step logged: state [nv] float32 observations, action [n_slices] PRBs each slice held, labels [n_slices] +1 fulfilled,
+ * -1 not, 0 "this learner skips the row".  Learner s of a listed agent is taught every row in row order, independently of the
+ * others, and for each row exactly the samples ranslice.kbrl_dev.augmented_samples makes of it: x = ((double)state[its
+ * variables], (double)a / (double)n_prbs) with the row's label, for a = action .. n_prbs on +1 and a = 0 .. action on -1, in
+ * that order, each through kb_fit's per-sample sequence in the handle's algorithm (kb_set_algorithm) with every rule kb_fit
+ * carries.  For each listed agent the call leaves BIT FOR BIT what kb_fit leaves when given augmented_samples of the same rows --
+ * landmarks, coefficients, all of Kinv, sizes, statistics, flags, the tie stream's position -- with kb_fit's one exception
+ * (which learner meets an exhausted pool, and the pool offsets).  The kernel forms the part of each kernel distance that the
+ * state coordinates contribute once per landmark and row, not once per landmark and sample; kb_fit's summation order makes
+ * that the same double.
+ * Outputs, [first[n]][n_slices] each, any may be NULL -- per (row, learner), not per sample: f_at, the learner's f at the logged
+ * allocation (state, action / n_prbs) BEFORE the row's first sample (what update_control's hit test looks at; read-only, no tie
+ * draw; on +1 it is the f of the row's first sample); y_at its sign, 0 on an exact tie or an empty dictionary (kb_score's
+ * convention); changed, the row's samples that changed the dictionary (kb_fit's "mistakes": branches 1-2, in Projectron++ mode
+ * 1-3); grown, its insertions; m_after, the size after the row.  A skipped entry reports 0, 0, 0, 0 and the current size.
+ * chunk: most log rows of one agent per launch; 0: the default, max(1, 256 / (n_prbs + 1)), about kb_fit's default in samples.
+ * No result depends on it.  The log is staged once: rows x (4 nv + 8 n_slices) bytes in, the summaries out.
+ * Afterwards, as after kb_fit: the cached kb_predict of every learner that received a sample is invalid and versions have
+ * moved; agents not listed, agents without rows and learners whose entries are all 0 are not touched at all.  kb_fit_time_ms
+ * reports the call as it reports a kb_fit (ms[0]; work[0..3] samples, mistakes, insertions, kernel evaluations; the f_at columns
+ * are not counted).  The chip-wide rounds are not used: one workgroup per learner always, kb_set_fit_wide and
+ * kb_set_fit_wide_plus have no effect on this call, and kb_fit_wide_info keeps describing the last kb_fit.
+ * RS_EINVAL, before anything is changed: an agent out of range or listed twice, first[0] != 0 or first decreasing, a label
+ * outside {-1, 0, 1}, an action outside 0 .. n_prbs where the label is not 0, n or chunk negative.  RS_ESTATE: kb_reset missing;
+ * an inference-only, a by-reference or a shared-dictionary handle (kb_fit's reasons). */
+int kb_fit_steps(kb_handle* k, const int32_t* agent, int32_t n, const int64_t* first /* [n + 1] */,
+                 const float* state /* [rows][nv] */, const int32_t* action /* [rows][S] */, const int32_t* labels /* [rows][S] */,
+                 int32_t chunk, double* f_at, int32_t* y_at, int32_t* changed, int32_t* grown, int32_t* m_after);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3326,7 +3326,7 @@ struct OneArgs {
 // GaussianKernel.predict's sum (kernel.py:13-28) by a 256-thread block: the kernel column of x into the K_f row, f = K_f . coeff as
 // per-thread sums over j = t, t + 256, ... in increasing j and block_sum over them; float32 while one landmark is held.  Every
 // thread returns f.  kb_predict's kernel and kb_fit's (kb_fit.hip) both call it; kb_score's kernel forms the same sums, Q queries
-// at a time, and stores nothing (a change here is made there too).
+// at a time, and stores nothing; predict_column_steps below forms them from a cached partial sum (a change here is made there too).
 __device__ __forceinline__ double predict_column(const KbDev& D, const KbState& K, const uint64_t* sh, int d, int m, const double* x,
                                                  Lds& sm) {
     double p = 0.0;
@@ -3345,6 +3345,59 @@ __device__ __forceinline__ double predict_column(const KbDev& D, const KbState& 
     }
     double f = block_sum(p, sm);
     if (m == 1) f = (double)(float)((float)*vec_at(K, sh, KB_ROW_KF, 0) * (float)*vec_at(K, sh, KB_ROW_CO, 0));
+    return f;
+}
+
+// predict_column for points that share their first d - 1 coordinates -- the candidates of one logged control step
+// (kb_fit_steps.hip).  predict_column sums dist over the coordinates in order, the last one last, so the sum over the first d - 1
+// is the same double for every such point: steps_prefix forms it by predict_column's chain (0.0, then += t * t for q = 0 .. d - 2),
+// and predict_column_steps continues that chain with the last coordinate's term -- dist = prefix + t t, rs_exp, the float32
+// rounding while one landmark is held, the K_f row, k coeff, the strided per-thread sums, block_sum: predict_column's operations
+// on predict_column's operands (no contraction, no reassociation: csrc/Makefile), hence its bits.  `pre` holds the prefixes of the
+// landmarks below KB_STEPS_PRE (the caller's LDS; thread t reads the entries j = t, t + 256, ...); a landmark beyond takes the
+// whole chain again.  STORE = false leaves the K_f row alone -- the read-only column of a step's logged allocation, kb_score's
+// reading of m == 1 (the kernel value never passes through memory).  A change to predict_column is made here too.
+#define KB_STEPS_PRE 256  // prefixes held in LDS: 2 KB beside the Lds block, one entry per thread -- the first trip of the strided loop;
+                          // every dictionary of the fleet workloads lies below it (G10: 67 at most), and G15 crosses it
+__device__ __forceinline__ double steps_prefix(const KbState& K, const uint64_t* sh, int d, int j, const double* x) {
+    const double* P = vec_page(K, sh, j >> 6);
+    const int l = j & 63;
+    double dist = 0.0;
+    for (int q = 0; q < d - 1; ++q) {
+        double t = P[q * KB_CH + l] - x[q];
+        dist += t * t;
+    }
+    return dist;
+}
+
+template <bool STORE>
+__device__ __forceinline__ double predict_column_steps(const KbDev& D, const KbState& K, const uint64_t* sh, int d, int m, const double* x,
+                                                       const double* pre, Lds& sm) {
+    const double x_last = x[d - 1];
+    double p = 0.0, k0 = 0.0;
+    for (int j = threadIdx.x; j < m; j += blockDim.x) {
+        double* P = vec_page(K, sh, j >> 6);
+        const int l = j & 63;
+        double dist = j < KB_STEPS_PRE ? pre[j] : steps_prefix(K, sh, d, j, x);
+        double t = P[(d - 1) * KB_CH + l] - x_last;
+        dist += t * t;
+        double k = rs_exp(-D.gamma * dist);
+        if (m == 1) k = (double)(float)k;
+        if (STORE) P[KB_ROW_KF * KB_CH + l] = k;
+        else k0 = k;  // (m == 1: thread 0 alone is here)
+        p += k * P[KB_ROW_CO * KB_CH + l];
+    }
+    double f = block_sum(p, sm);
+    if (m == 1) {
+        if (STORE) {
+            f = (double)(float)((float)*vec_at(K, sh, KB_ROW_KF, 0) * (float)*vec_at(K, sh, KB_ROW_CO, 0));
+        } else {
+            if (threadIdx.x == 0) sm.red[8] = k0;  // (block_sum uses red[0 .. blockDim / 64 - 1] and ended with a barrier)
+            __syncthreads();
+            f = (double)(float)((float)sm.red[8] * (float)*vec_at(K, sh, KB_ROW_CO, 0));
+            __syncthreads();
+        }
+    }
     return f;
 }
 

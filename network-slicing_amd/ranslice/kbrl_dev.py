@@ -60,7 +60,8 @@ def augmented_samples(state, action, labels, dims, n_prbs):
     label.  The lists feed VecKBRL.fit, whatever produced the log -- the reference, a deployed fleet, the clairvoyant baseline.
     Limits: fit forms f in predict's summation order, update_control through the binned / MFMA scoring chain, so the two take
     the same decisions except where f is within rounding of zero -- bit-equality with update_control is not claimed; and the
-    stop of the augmentation at a full dictionary (build-defined in the oracle) is not reproduced."""
+    stop of the augmentation at a full dictionary (build-defined in the oracle) is not reproduced.
+    VecKBRL.fit_steps generates exactly these samples on the device from the log itself; this is their statement on the host."""
     state = np.asarray(state, dtype=np.float64)
     state = state.reshape(-1, int(sum(dims)))
     steps = state.shape[0]
@@ -276,6 +277,62 @@ class VecKBRL:
                                   f.ctypes.data_as(_dp), br.ctypes.data_as(_ip), dl.ctypes.data_as(_dp), ma.ctypes.data_as(_ip)))
         cut = lambda a: [a[first[i]:first[i + 1]] for i in range(task.size)]
         return dict(y_pred=cut(yp), f=cut(f), branch=cut(br), delta=cut(dl), m=cut(ma))
+
+    def _pack_steps(self, agents, state, action, labels):
+        """(agent [n] int32, first [n + 1] int64, state [rows, nv] float32, action, labels [rows, S] int32) of per-agent logs;
+        every shape, label and action is checked here (ValueError), before the library is touched"""
+        agents = [int(e) for e in agents]
+        for name, v in (('state', state), ('action', action), ('labels', labels)):
+            if len(v) != len(agents):
+                raise ValueError('fit_steps: %d agents but %d %s logs' % (len(agents), len(v), name))
+        for e in agents:
+            if not 0 <= e < self.n_envs:
+                raise ValueError('fit_steps: %d names no agent (0 .. %d)' % (e, self.n_envs - 1))
+        first = np.zeros(len(agents) + 1, dtype=np.int64)
+        st, ac, lb = [], [], []
+        for i, (x, a, l) in enumerate(zip(state, action, labels)):
+            x, a, l = np.asarray(x, dtype=np.float32), np.asarray(a), np.asarray(l)
+            if x.ndim != 2 or x.shape[1] != self.nv:
+                raise ValueError('fit_steps: state of agent %d has shape %s, not [T, %d]' % (agents[i], x.shape, self.nv))
+            for name, v in (('action', a), ('labels', l)):
+                if v.shape != (x.shape[0], self.S):
+                    raise ValueError('fit_steps: %s of agent %d has shape %s, not %s' % (name, agents[i], v.shape, (x.shape[0], self.S)))
+            if (a != np.rint(a)).any() or (l != np.rint(l)).any():
+                raise ValueError('fit_steps: actions and labels are integers')
+            a, l = a.astype(np.int64), l.astype(np.int64)
+            if ((l != 1) & (l != -1) & (l != 0)).any():
+                raise ValueError('fit_steps: labels must be +1, -1 or 0 (the learner skips the row)')
+            if (((a < 0) | (a > self.n_prbs)) & (l != 0)).any():
+                raise ValueError('fit_steps: actions must lie in 0 .. n_prbs')
+            st.append(x)
+            ac.append(a.astype(np.int32))
+            lb.append(l.astype(np.int32))
+            first[i + 1] = first[i] + x.shape[0]
+        cat = lambda v, w, t: np.ascontiguousarray(np.concatenate(v), dtype=t) if v else np.zeros((0, w), dtype=t)
+        return (np.array(agents, dtype=np.int32).reshape(-1), first, cat(st, self.nv, np.float32), cat(ac, self.S, np.int32),
+                cat(lb, self.S, np.int32))
+
+    def fit_steps(self, agents, state, action, labels, chunk=0):
+        """teach agents from logs of control steps, augmented on the device (kb_fit_steps; build-defined): agents = [e, ...] all
+        distinct; state / action / labels either lists over the agents of arrays [T_i, nv] float32 / [T_i, S] / [T_i, S], or
+        arrays [n, T, ...].  labels: +1 fulfilled, -1 not, 0 = this learner skips the row.  Learner s of agent i is taught, row by
+        row, exactly the samples augmented_samples makes of the rows -- bit for bit what fit(..., *augmented_samples(...)) leaves,
+        in the handle's algorithm -- while only the log itself is staged (about 250 bytes per agent and step, not 16 doubles per
+        sample).  chunk: most log rows of one agent per launch (0: the default); no result depends on it.  -> dict of per-agent
+        lists of arrays [T_i, S]: f_at (f at the logged allocation before the row's first sample), y_at (its sign; 0 on a tie or
+        an empty dictionary), changed (samples of the row that changed the dictionary), grown (insertions) and m (the size after
+        the row).  One workgroup per learner always: set_fit_wide has no effect here.  The cached predict of the learners that
+        received samples is invalid afterwards; fit_time_ms() reports the call like a fit."""
+        agent, first, st, ac, lb = self._pack_steps(agents, state, action, labels)
+        R = int(first[-1])
+        f_at = np.zeros((R, self.S))
+        y_at, ch, gr, ma = (np.zeros((R, self.S), dtype=np.int32) for _ in range(4))
+        self._check(self.L.kb_fit_steps(self.h, agent.ctypes.data_as(_ip), int(agent.size), first.ctypes.data_as(C.POINTER(C.c_int64)),
+                                        st.ctypes.data_as(_fp), ac.ctypes.data_as(_ip), lb.ctypes.data_as(_ip), int(chunk),
+                                        f_at.ctypes.data_as(_dp), y_at.ctypes.data_as(_ip), ch.ctypes.data_as(_ip),
+                                        gr.ctypes.data_as(_ip), ma.ctypes.data_as(_ip)))
+        cut = lambda a: [a[first[i]:first[i + 1]] for i in range(agent.size)]
+        return dict(f_at=cut(f_at), y_at=cut(y_at), changed=cut(ch), grown=cut(gr), m=cut(ma))
 
     def score(self, learners, X):
         """read-only scoring of query sets (kb_score; build-defined): learners = [(e, s), ...] (repeats allowed), X[i] =
@@ -709,6 +766,12 @@ class SharedVecKBRL(VecKBRL):
         (kb_fit answers RS_ESTATE); score() works.  Teach a per-replica VecKBRL and to_shared() it instead."""
         raise _lib.RanSliceError(_lib.RS_ESTATE, 'fit: shared-dictionary handles are not supported: several learners map to one '
                                  'dictionary (fit a per-replica VecKBRL, then to_shared)')
+
+    def fit_steps(self, agents, state, action, labels, chunk=0):
+        """refused, as fit() is and for its reason (kb_fit_steps answers RS_ESTATE): teach a per-replica VecKBRL from the log and
+        to_shared() it instead"""
+        raise _lib.RanSliceError(_lib.RS_ESTATE, 'fit_steps: shared-dictionary handles are not supported: several learners map to '
+                                 'one dictionary (teach a per-replica VecKBRL, then to_shared)')
 
     def set_fit_wide(self, min_landmarks, window=0):
         """refused, as kb_set_fit_wide refuses it: a shared-dictionary handle does not learn through fit()"""
