@@ -12,6 +12,8 @@
 // (A dictionary of thousands of landmarks is taught at the pace of one workgroup here; kb_set_fit_wide hands such learners to
 // chip-wide rounds, the heavy_* shape of update_control, with the same bits: kb_fit_wide.hip)  In Projectron++ mode (kb_set_algorithm) the same loop runs as its second
 // instance, fit_plus_kernel: apply_update_plus in place of the mistake test and apply_update, as update_one_kernel does.
+// The sample step is also stated as device functions, for kb_fit_steps.hip and kb_fit_wide.hip: fit_decide, fit_rule<ALG>,
+// fit_epilogue.  The host framing of a fitting call stands once: kb_fit_can_learn, kb_fit_list, kb_fit_open / kb_fit_close, FitStage.
 //
 // kb_score.  f of kb_predict for many points, and nothing else: no K_f row, no cache, no counter, no tie draw.  score_kernel's
 // workgroup takes one dictionary and KB_SCORE_Q of its queries, staged in LDS; thread t walks the landmarks j = t, t + 256, ...
@@ -45,6 +47,75 @@ struct FitArgs {
     int alg;                   // KB_ALG_* of the handle at the call: the instance kb_fit launches
     const int32_t* wide;       // [n] 1: the learner is taught this chunk by the rounds of kb_fit_wide.hip; NULL: the wide path is off
 };
+
+// ONE LEARNER'S SAMPLE STEP, shared by fit_steps_learner (kb_fit_steps.hip) and the chip-wide rounds (kb_fit_wide.hip): fit_decide,
+// fit_rule and, when a learner is done with a launch, fit_epilogue.  All run on the whole 256-thread block.  They restate
+// fit_learner's own step below statement for statement (a change there is made here too): built from these functions, fit_learner
+// compiled to the same instructions under another register allocation, and fit_plus_kernel measured 0.4-0.6 % slower on a fleet of
+// 20,480 learners, outside the parent's range (profiles/HISTORY.md) -- so fit_kernel and fit_plus_kernel keep the loop they had.
+
+// Projectron.predict's decision (projectron.py:32-37) on the f just formed: its sign; an exact 0 against a populated dictionary
+// draws from the learner's stream; an empty dictionary answers f = 0, y_pred = 0.  Every thread returns the same y_pred.
+__device__ __forceinline__ int fit_decide(const KbState& K, int task, int env, int s, int m, double* f, Lds& sm) {
+    int yp = 0;
+    if (m > 0) {
+        yp = *f > 0.0 ? 1 : (*f < 0.0 ? -1 : 0);
+        if (yp == 0) {  // (block-uniform: every thread holds the same f)
+            if (threadIdx.x == 0) sm.ired[0] = tie_draw(K, task, env, s);
+            __syncthreads();
+            yp = sm.ired[0];
+            __syncthreads();
+        }
+    } else {
+        *f = 0.0;
+    }
+    return yp;
+}
+
+// The update rule on the (f, K_f) just formed for the sample x (LDS) with label y.  Projectron.update (projectron.py:39-60): the
+// mistake test f y <= 0, then apply_update.  ProjectronPlus.update (projectron.py:71-107): apply_update_plus on every sample; a
+// mistake is a sample that changed the dictionary (branches 1-3).  Returns the new m; *branch and *delta as the rule leaves them
+// (0, 0.0: no update); *mistakes and *insertions, the caller's counters, are advanced in place where the sample counts as one
+// (returned as flags for the caller to add, they cost fit_steps_kernel two more moves per mistake).  ALG is a compile-time constant.
+template <int ALG>
+__device__ __forceinline__ int fit_rule(const KbDev& D, const KbState& K, int dict, int env, int m, int d, const double* x, int y, double f,
+                                        Lds& sm, int* branch, double* delta, int* mistakes, int* insertions) {
+    int m_new = m;
+    *branch = 0;
+    *delta = 0.0;
+    if (ALG == KB_ALG_PROJECTRON_PLUS) {
+        const double t_last = x[d - 1];
+        m_new = apply_update_plus(D, K, dict, env, m, d, x, t_last, grid_index(t_last, D.n_prbs), y, f, sm, branch, delta);
+        if (*branch >= 1 && *branch <= 3) *mistakes += 1;
+        if (*branch == 2 && m_new > m) *insertions += 1;
+    } else if (f * (double)y <= 0.0) {
+        const double t_last = x[d - 1];
+        m_new = apply_update(D, K, dict, env, m, d, x, t_last, grid_index(t_last, D.n_prbs), y, sm, branch, delta);
+        *mistakes += 1;
+        if (*branch == 2 && m_new > m) *insertions += 1;
+    }
+    return m_new;
+}
+
+struct FitCounts {  // what a launch counted for one learner
+    unsigned long long samples, mistakes, insertions, evals;
+};
+
+// A learner is done with its samples of the launch (thread 0; per-replica dictionaries: task names the dictionary too).  `c` is NULL
+// for the chip-wide rounds, which add their counters as they go.
+__device__ __forceinline__ void fit_epilogue(const KbState& K, int task, double f, unsigned long long* work, const FitCounts* c) {
+    K.f_last[task] = f;
+    K.m_last[task] = -1;  // the cache of the last kb_predict is gone: kb_update answers RS_ESTATE until a new kb_predict
+    K.kf_owner[task] = -1;
+    if (!c) return;
+    K.stats[(size_t)task * 4 + 0] += c->samples;
+    K.stats[(size_t)task * 4 + 1] += c->mistakes;
+    K.stats[(size_t)task * 4 + 2] += c->insertions;
+    atomicAdd(&work[0], c->samples);
+    atomicAdd(&work[1], c->mistakes);
+    atomicAdd(&work[2], c->insertions);
+    atomicAdd(&work[3], c->evals);
+}
 
 // The persistent loop of one learner, once per update rule: fit_kernel is the Projectron instance (ALG is a compile-time constant,
 // so it holds none of the margin rule's code and its arithmetic is what it was before the rule existed), fit_plus_kernel the
@@ -286,7 +357,8 @@ static int kb_fit_prepare(kb_handle* k) {
     return RS_OK;
 }
 
-// one device block for a call's staged arrays, released when the call returns
+// One device block for a call's staged arrays, released when the call returns.  The call states its arrays ONCE, as a function of
+// take() calls (256-byte boundaries, in their order): alloc runs it without a block, to count the bytes, and again on the block.
 struct FitStage {
     char* base = nullptr;
     size_t used = 0;
@@ -296,16 +368,94 @@ struct FitStage {
     static size_t pad(size_t b) { return (b + 255) & ~(size_t)255; }
     template <class Tp>
     Tp* take(size_t n) {
-        Tp* p = (Tp*)(base + used);
+        Tp* p = base ? (Tp*)(base + used) : nullptr;
         used += pad(sizeof(Tp) * (n ? n : 1));
         return p;
     }
+    template <class Layout>
+    hipError_t alloc(Layout layout) {
+        layout(*this);
+        const hipError_t e = hipMalloc((void**)&base, used);
+        if (e != hipSuccess) return e;
+        used = 0;
+        layout(*this);
+        return hipSuccess;
+    }
 };
 
-// kb_fit's chip-wide rounds (kb_fit_wide.hip): the bytes their state adds to the staged block, its arrays, and the rounds of one chunk
-static size_t kb_fit_wide_bytes(kb_handle* k, int32_t n);
+// kb_fit's chip-wide rounds (kb_fit_wide.hip): their state's arrays in the staged block, and the rounds of one chunk
 static void kb_fit_wide_take(kb_handle* k, FitStage& st, int32_t n, kb::FitWide* W);
 static int kb_fit_wide_rounds(kb_handle* k, kb::WideArgs& wa, int32_t chunk);
+
+// the handles that cannot be taught, for kb_fit and kb_fit_steps (`who`)
+static int kb_fit_can_learn(kb_handle* k, const char* who) {
+    if (k->ref) {
+        k->err = std::string(who) + ": a by-reference handle (kb_deploy_ref) shares read-only dictionaries: it cannot learn";
+        return RS_ESTATE;
+    }
+    if (k->frozen) {
+        k->err = std::string(who) + ": an inference-only handle (kb_deploy, kb_import_agents) cannot learn: it holds no Kinv";
+        return RS_ESTATE;
+    }
+    if (k->D.shared) {
+        k->err = std::string(who) + ": shared-dictionary handles are not supported: several learners map to one dictionary";
+        return RS_ESTATE;
+    }
+    return RS_OK;
+}
+
+// and for the settings of the chip-wide rounds (kb_set_fit_wide, kb_set_fit_wide_plus)
+static int kb_fit_wide_can_set(kb_handle* k, const char* who) {
+    if (k->frozen || k->ref || k->D.shared) {
+        k->err = std::string(who) + ": " +
+                 (k->ref ? "a by-reference handle (kb_deploy_ref)" : k->frozen ? "an inference-only handle (kb_deploy, kb_import_agents)"
+                                                                               : "a shared-dictionary handle") +
+                 " does not learn through kb_fit";
+        return RS_ESTATE;
+    }
+    return RS_OK;
+}
+
+// the list of a fitting call: every entry of `array` names one of `limit` learners / agents (`noun`), none twice (`seq`: its samples / rows)
+static int kb_fit_list(kb_handle* k, const char* who, const char* array, const char* noun, const char* seq, const int32_t* list,
+                       int32_t n, int32_t limit) {
+    std::vector<char> seen((size_t)limit, 0);
+    for (int32_t i = 0; i < n; ++i) {
+        if (list[i] < 0 || list[i] >= limit) {
+            k->err = std::string(who) + ": " + array + "[" + std::to_string(i) + "] = " + std::to_string(list[i]) + " names no " + noun +
+                     " (0 .. " + std::to_string(limit - 1) + ")";
+            return RS_EINVAL;
+        }
+        if (seen[(size_t)list[i]]) {
+            k->err = std::string(who) + ": " + noun + " " + std::to_string(list[i]) + " is listed twice: " +
+                     (strchr("aeiou", noun[0]) ? "an " : "a ") + noun + "'s " + seq + " form ONE sequence";
+            return RS_EINVAL;
+        }
+        seen[(size_t)list[i]] = 1;
+    }
+    return RS_OK;
+}
+
+// a fitting call opens behind whatever is queued on either stream, its counters and timing restarted; it closes with the side stream behind it
+static int kb_fit_open(kb_handle* k) {
+    int rc;
+    HIPCHK(k, hipSetDevice(k->device));
+    if ((rc = kb_fit_prepare(k)) != RS_OK) return rc;
+    kb_fit_state* p = k->fit;
+    k->gemm_fresh = false;
+    if (k->side && (rc = stream_after(k, &p->ev_in, k->side, k->stream)) != RS_OK) return rc;
+    HIPCHK(k, hipMemsetAsync(p->d_work, 0, sizeof(unsigned long long) * 4, k->stream));
+    p->fit_spans.on = k->spans.on;
+    p->fit_spans.reset();
+    p->fit_ms = 0.0;
+    return RS_OK;
+}
+
+static int kb_fit_close(kb_handle* k) {
+    int rc;
+    if (k->side && (rc = stream_after(k, &k->fit->ev_out, k->stream, k->side)) != RS_OK) return rc;
+    return kb_check(k);  // (waits for the stream)
+}
 
 // the checks kb_fit and kb_score share: the sample ranges.  *rows = first[n] - first[0]
 static int kb_fit_ranges(kb_handle* k, const char* who, const int64_t* first, int32_t n, int64_t* rows) {
@@ -329,38 +479,16 @@ extern "C" int kb_fit(kb_handle* k, const int32_t* task, int32_t n, const int64_
         k->err = "kb_fit: call kb_reset first";
         return RS_ESTATE;
     }
-    if (k->ref) {
-        k->err = "kb_fit: a by-reference handle (kb_deploy_ref) shares read-only dictionaries: it cannot learn";
-        return RS_ESTATE;
-    }
-    if (k->frozen) {
-        k->err = "kb_fit: an inference-only handle (kb_deploy, kb_import_agents) cannot learn: it holds no Kinv";
-        return RS_ESTATE;
-    }
-    if (k->D.shared) {
-        k->err = "kb_fit: shared-dictionary handles are not supported: several learners map to one dictionary";
-        return RS_ESTATE;
-    }
+    int rc = kb_fit_can_learn(k, "kb_fit");
+    if (rc != RS_OK) return rc;
     if (n < 0 || chunk < 0 || (n > 0 && (!task || !first))) {
         k->err = "kb_fit: n or chunk is negative, or task / first is NULL";
         return RS_EINVAL;
     }
     if (n == 0) return RS_OK;
-    std::vector<char> seen((size_t)k->T, 0);
-    for (int32_t i = 0; i < n; ++i) {
-        if (task[i] < 0 || task[i] >= k->T) {
-            k->err = "kb_fit: task[" + std::to_string(i) + "] = " + std::to_string(task[i]) + " names no learner (0 .. " + std::to_string(k->T - 1) + ")";
-            return RS_EINVAL;
-        }
-        if (seen[(size_t)task[i]]) {
-            k->err = "kb_fit: learner " + std::to_string(task[i]) + " is listed twice: a learner's samples form ONE sequence";
-            return RS_EINVAL;
-        }
-        seen[(size_t)task[i]] = 1;
-    }
+    if ((rc = kb_fit_list(k, "kb_fit", "task", "learner", "samples", task, n, k->T)) != RS_OK) return rc;
     int64_t rows = 0;
-    int rc = kb_fit_ranges(k, "kb_fit", first, n, &rows);
-    if (rc != RS_OK) return rc;
+    if ((rc = kb_fit_ranges(k, "kb_fit", first, n, &rows)) != RS_OK) return rc;
     if (rows == 0) return RS_OK;
     if (!x || !y) {
         k->err = "kb_fit: x or y is NULL";
@@ -375,60 +503,50 @@ extern "C" int kb_fit(kb_handle* k, const int32_t* task, int32_t n, const int64_
             return RS_EINVAL;
         }
     if (chunk == 0) chunk = KB_FIT_CHUNK;
-    HIPCHK(k, hipSetDevice(k->device));
-    if ((rc = kb_fit_prepare(k)) != RS_OK) return rc;
+    if ((rc = kb_fit_open(k)) != RS_OK) return rc;
     kb_fit_state* p = k->fit;
-    k->gemm_fresh = false;
+    HIPCHK(k, hipMemsetAsync(p->d_work + 8, 0, sizeof(unsigned long long) * 4, k->stream));  // (kb_fit_wide_info: of this call)
     std::vector<long long> rel((size_t)n + 1);
     for (int32_t i = 0; i <= n; ++i) rel[(size_t)i] = (long long)(first[i] - base);
     const size_t R = (size_t)rows;
-    FitStage st;
     // kb_set_fit_wide: learners with large dictionaries are taught chunk by chunk in chip-wide rounds (kb_fit_wide.hip); Projectron++
     // keeps the one-workgroup loop whatever that setting, unless kb_set_fit_wide_plus is on as well
     const bool wide = k->fit_wide_min >= 2 && (k->alg != KB_ALG_PROJECTRON_PLUS || k->fit_wide_plus);
-    const size_t bytes = FitStage::pad(sizeof(int32_t) * (size_t)n) + FitStage::pad(sizeof(long long) * ((size_t)n + 1)) +
-                         FitStage::pad(sizeof(double) * KB_DMAX * R) + FitStage::pad(R) + 3 * FitStage::pad(sizeof(int32_t) * R) +
-                         2 * FitStage::pad(sizeof(double) * R) + (wide ? kb_fit_wide_bytes(k, n) : 0);
-    HIPCHK(k, hipMalloc((void**)&st.base, bytes));
     kb::FitArgs a;
     memset(&a, 0, sizeof a);
     a.D = k->D;
     a.K = k->K;
-    int32_t* d_task = st.take<int32_t>((size_t)n);
-    long long* d_first = st.take<long long>((size_t)n + 1);
-    double* d_x = st.take<double>(KB_DMAX * R);
-    int8_t* d_y = st.take<int8_t>(R);
-    a.y_pred = st.take<int32_t>(R);
-    a.branch = st.take<int32_t>(R);
-    a.m_after = st.take<int32_t>(R);
-    a.f = st.take<double>(R);
-    a.delta = st.take<double>(R);
-    a.task = d_task;
-    a.first = d_first;
-    a.x = d_x;
-    a.y = d_y;
     a.chunk = chunk;
     a.work = p->d_work;
     a.alg = k->alg;
     kb::WideArgs wa;
     memset(&wa, 0, sizeof wa);
+    int32_t* d_task = nullptr;
+    long long* d_first = nullptr;
+    double* d_x = nullptr;
+    int8_t* d_y = nullptr;
+    FitStage st;
+    HIPCHK(k, st.alloc([&](FitStage& s) {
+        a.task = d_task = s.take<int32_t>((size_t)n);
+        a.first = d_first = s.take<long long>((size_t)n + 1);
+        a.x = d_x = s.take<double>(KB_DMAX * R);
+        a.y = d_y = s.take<int8_t>(R);
+        a.y_pred = s.take<int32_t>(R);
+        a.branch = s.take<int32_t>(R);
+        a.m_after = s.take<int32_t>(R);
+        a.f = s.take<double>(R);
+        a.delta = s.take<double>(R);
+        if (wide) kb_fit_wide_take(k, s, n, &wa.W);
+    }));
     if (wide) {
-        kb_fit_wide_take(k, st, n, &wa.W);
         wa.W.info = p->d_work + 8;
         wa.n = n;
         a.wide = wa.W.mark;
     }
-    // behind whatever is queued on either of the handle's streams
-    if (k->side && (rc = stream_after(k, &p->ev_in, k->side, k->stream)) != RS_OK) return rc;
     HIPCHK(k, hipMemcpyAsync(d_task, task, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, k->stream));
     HIPCHK(k, hipMemcpyAsync(d_first, rel.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, k->stream));
     HIPCHK(k, hipMemcpyAsync(d_x, x + (size_t)base * KB_DMAX, sizeof(double) * KB_DMAX * R, hipMemcpyHostToDevice, k->stream));
     HIPCHK(k, hipMemcpyAsync(d_y, y + base, R, hipMemcpyHostToDevice, k->stream));
-    HIPCHK(k, hipMemsetAsync(p->d_work, 0, sizeof(unsigned long long) * 4, k->stream));
-    HIPCHK(k, hipMemsetAsync(p->d_work + 8, 0, sizeof(unsigned long long) * 4, k->stream));
-    p->fit_spans.on = k->spans.on;
-    p->fit_spans.reset();
-    p->fit_ms = 0.0;
     for (int64_t from = 0; from < longest; from += chunk) {  // (no launch runs longer than `chunk` samples of one learner)
         a.from = (long long)from;
         hipEvent_t e;
@@ -450,8 +568,7 @@ extern "C" int kb_fit(kb_handle* k, const int32_t* task, int32_t n, const int64_
     if (branch) HIPCHK(k, hipMemcpyAsync(branch + base, a.branch, sizeof(int32_t) * R, hipMemcpyDeviceToHost, k->stream));
     if (delta) HIPCHK(k, hipMemcpyAsync(delta + base, a.delta, sizeof(double) * R, hipMemcpyDeviceToHost, k->stream));
     if (m_after) HIPCHK(k, hipMemcpyAsync(m_after + base, a.m_after, sizeof(int32_t) * R, hipMemcpyDeviceToHost, k->stream));
-    if (k->side && (rc = stream_after(k, &p->ev_out, k->stream, k->side)) != RS_OK) return rc;
-    return kb_check(k);  // (waits for the stream)
+    return kb_fit_close(k);
 }
 
 extern "C" int kb_score(kb_handle* k, const int32_t* task, int32_t n, const int64_t* first, const double* x, double* f,
@@ -497,21 +614,20 @@ extern "C" int kb_score(kb_handle* k, const int32_t* task, int32_t n, const int6
     if ((rc = kb_fit_prepare(k)) != RS_OK) return rc;
     kb_fit_state* p = k->fit;
     const size_t R = (size_t)rows, NB = blocks.size();
-    FitStage st;
-    const size_t bytes = FitStage::pad(sizeof(kb::ScoreBlock) * NB) + FitStage::pad(sizeof(double) * KB_DMAX * R) +
-                         FitStage::pad(sizeof(double) * R) + FitStage::pad(sizeof(int32_t) * R);
-    HIPCHK(k, hipMalloc((void**)&st.base, bytes));
     kb::ScoreArgs a;
     memset(&a, 0, sizeof a);
     a.D = own->D;
     a.K = own->K;
-    kb::ScoreBlock* d_blk = st.take<kb::ScoreBlock>(NB);
-    double* d_x = st.take<double>(KB_DMAX * R);
-    a.f = st.take<double>(R);
-    a.y_pred = st.take<int32_t>(R);
-    a.blk = d_blk;
-    a.x = d_x;
     a.work = p->d_work + 4;
+    kb::ScoreBlock* d_blk = nullptr;
+    double* d_x = nullptr;
+    FitStage st;
+    HIPCHK(k, st.alloc([&](FitStage& s) {
+        a.blk = d_blk = s.take<kb::ScoreBlock>(NB);
+        a.x = d_x = s.take<double>(KB_DMAX * R);
+        a.f = s.take<double>(R);
+        a.y_pred = s.take<int32_t>(R);
+    }));
     if (k->side && (rc = stream_after(k, &p->ev_in, k->side, k->stream)) != RS_OK) return rc;
     HIPCHK(k, hipMemcpyAsync(d_blk, blocks.data(), sizeof(kb::ScoreBlock) * NB, hipMemcpyHostToDevice, k->stream));
     HIPCHK(k, hipMemcpyAsync(d_x, x + (size_t)base * KB_DMAX, sizeof(double) * KB_DMAX * R, hipMemcpyHostToDevice, k->stream));

@@ -1,7 +1,8 @@
 // kb_fit_steps.hip -- kb_fit for logs of control steps: the log (state, action, SLA labels) is staged as it was recorded and the
 // sample augmentation of kbrl_control.py:103-112 runs on the device, next to the loop that consumes it.  #included by rs_api.hip
-// after kb_fit.hip: it uses kb_fit's staging block, counters and timing, and the Projectron routines of kb_kbrl.hip
-// (predict_column_steps beside predict_column, tie_draw, apply_update, apply_update_plus); it changes none of their kernels.
+// after kb_fit.hip: it uses kb_fit's sample step (fit_decide, fit_rule, fit_epilogue), its host framing (kb_fit_can_learn, kb_fit_list,
+// kb_fit_open / kb_fit_close, FitStage), counters and timing, and predict_column_steps of kb_kbrl.hip beside predict_column; it
+// changes none of their kernels.
 //
 // A logged step of a learner stands for up to n_prbs + 1 samples that differ only in their last coordinate: label +1 at allocation
 // a gives (state, a / n_prbs), ..., (state, n_prbs / n_prbs), label -1 gives (state, 0), ..., (state, a / n_prbs) -- what
@@ -54,7 +55,7 @@ __device__ __forceinline__ void fit_steps_learner(const StepsArgs& A, Lds& sm, d
     const uint64_t* sh = shells_of(D, K, dt);
     const int d = D.dims[s] + 1, n = D.n_prbs;
     int m = K.m[dt];
-    unsigned long long n_samp = 0, n_mist = 0, n_grow = 0, n_eval = 0;
+    FitCounts c = {0, 0, 0, 0};
     double f = 0.0;
     for (long long r = r0; r < r1; ++r) {
         const size_t o = (size_t)r * D.S + s;
@@ -86,45 +87,21 @@ __device__ __forceinline__ void fit_steps_learner(const StepsArgs& A, Lds& sm, d
             __syncthreads();  // (the previous sample's readers of sm.x are done; an inserted landmark's prefix is in place)
             if (threadIdx.x == 0) sm.x[d - 1] = (double)a / (double)n;
             __syncthreads();
-            // Projectron.predict (projectron.py:32-37)
             f = predict_column_steps<true>(D, K, sh, d, m, sm.x, pre, sm);
-            int yp = 0;
-            if (m > 0) {
-                yp = f > 0.0 ? 1 : (f < 0.0 ? -1 : 0);
-                if (yp == 0) {  // (block-uniform: every thread holds the same f)
-                    if (threadIdx.x == 0) sm.ired[0] = tie_draw(K, task, env, s);
-                    __syncthreads();
-                    yp = sm.ired[0];
-                    __syncthreads();
-                }
-            } else {
-                f = 0.0;
-            }
+            (void)fit_decide(K, task, env, s, m, &f, sm);  // (the tie draws as in kb_fit; the summaries keep f alone)
             if (y > 0 && a == a0) f_at = f;
-            n_eval += (unsigned long long)m;
-            // Projectron.update (projectron.py:39-60) on the (f, K_f) just formed
-            int branch = 0, m_new = m;
-            double delta = 0.0;
-            if (ALG == KB_ALG_PROJECTRON_PLUS) {
-                // ProjectronPlus.update (projectron.py:71-107): a mistake is a sample that changed the dictionary (branches 1-3)
-                const double t_last = sm.x[d - 1];
-                m_new = apply_update_plus(D, K, dt, env, m, d, sm.x, t_last, grid_index(t_last, n), y, f, sm, &branch, &delta);
-                if (branch >= 1 && branch <= 3) row_mist += 1;
-                if (branch == 2 && m_new > m) row_grow += 1;
-            } else if (f * (double)y <= 0.0) {
-                const double t_last = sm.x[d - 1];
-                m_new = apply_update(D, K, dt, env, m, d, sm.x, t_last, grid_index(t_last, n), y, sm, &branch, &delta);
-                row_mist += 1;
-                if (branch == 2 && m_new > m) row_grow += 1;
-            }
+            c.evals += (unsigned long long)m;
+            int branch;
+            double delta;
+            const int m_new = fit_rule<ALG>(D, K, dt, env, m, d, sm.x, y, f, sm, &branch, &delta, &row_mist, &row_grow);
             // a landmark inserted inside the row: its prefix by the same chain, from the coordinates the insertion stored, formed
             // by the thread that reads it (finish_update ended with a barrier behind its stores)
             if (m_new > m && m < KB_STEPS_PRE && (int)threadIdx.x == (m & 255)) pre[m] = steps_prefix(K, sh, d, m, sm.x);
             m = m_new;
         }
-        n_samp += (unsigned long long)(a1 - a0 + 1);
-        n_mist += (unsigned long long)row_mist;
-        n_grow += (unsigned long long)row_grow;
+        c.samples += (unsigned long long)(a1 - a0 + 1);
+        c.mistakes += (unsigned long long)row_mist;
+        c.insertions += (unsigned long long)row_grow;
         if (threadIdx.x == 0) {
             A.f_at[o] = f_at;
             A.y_at[o] = m0 > 0 ? (f_at > 0.0 ? 1 : (f_at < 0.0 ? -1 : 0)) : 0;
@@ -133,19 +110,10 @@ __device__ __forceinline__ void fit_steps_learner(const StepsArgs& A, Lds& sm, d
             A.m_after[o] = m;
         }
     }
-    if (n_samp == 0) return;  // every row of the launch skipped: the learner is not touched at all
+    if (c.samples == 0) return;  // every row of the launch skipped: the learner is not touched at all
     if (threadIdx.x == 0) {
         K.m[dt] = m;
-        K.f_last[task] = f;
-        K.m_last[task] = -1;   // the cache of the last kb_predict is gone: kb_update answers RS_ESTATE until a new kb_predict
-        K.kf_owner[dt] = -1;
-        K.stats[(size_t)task * 4 + 0] += n_samp;
-        K.stats[(size_t)task * 4 + 1] += n_mist;
-        K.stats[(size_t)task * 4 + 2] += n_grow;
-        atomicAdd(&A.work[0], n_samp);
-        atomicAdd(&A.work[1], n_mist);
-        atomicAdd(&A.work[2], n_grow);
-        atomicAdd(&A.work[3], n_eval);
+        fit_epilogue(K, task, f, A.work, &c);
     }
 }
 
@@ -171,43 +139,21 @@ extern "C" int kb_fit_steps(kb_handle* k, const int32_t* agent, int32_t n, const
         k->err = "kb_fit_steps: call kb_reset first";
         return RS_ESTATE;
     }
-    if (k->ref) {
-        k->err = "kb_fit_steps: a by-reference handle (kb_deploy_ref) shares read-only dictionaries: it cannot learn";
-        return RS_ESTATE;
-    }
-    if (k->frozen) {
-        k->err = "kb_fit_steps: an inference-only handle (kb_deploy, kb_import_agents) cannot learn: it holds no Kinv";
-        return RS_ESTATE;
-    }
-    if (k->D.shared) {
-        k->err = "kb_fit_steps: shared-dictionary handles are not supported: several learners map to one dictionary";
-        return RS_ESTATE;
-    }
+    int rc = kb_fit_can_learn(k, "kb_fit_steps");
+    if (rc != RS_OK) return rc;
     if (n < 0 || chunk < 0 || (n > 0 && (!agent || !first))) {
         k->err = "kb_fit_steps: n or chunk is negative, or agent / first is NULL";
         return RS_EINVAL;
     }
     if (n == 0) return RS_OK;
-    const int32_t N = k->D.n_envs, S = k->D.S, nv = k->D.nv, P = k->D.n_prbs;
-    std::vector<char> seen((size_t)N, 0);
-    for (int32_t i = 0; i < n; ++i) {
-        if (agent[i] < 0 || agent[i] >= N) {
-            k->err = "kb_fit_steps: agent[" + std::to_string(i) + "] = " + std::to_string(agent[i]) + " names no agent (0 .. " + std::to_string(N - 1) + ")";
-            return RS_EINVAL;
-        }
-        if (seen[(size_t)agent[i]]) {
-            k->err = "kb_fit_steps: agent " + std::to_string(agent[i]) + " is listed twice: an agent's rows form ONE sequence";
-            return RS_EINVAL;
-        }
-        seen[(size_t)agent[i]] = 1;
-    }
+    const int32_t S = k->D.S, nv = k->D.nv, P = k->D.n_prbs;
+    if ((rc = kb_fit_list(k, "kb_fit_steps", "agent", "agent", "rows", agent, n, k->D.n_envs)) != RS_OK) return rc;
     if (first[0] != 0) {
         k->err = "kb_fit_steps: first[0] must be 0";
         return RS_EINVAL;
     }
     int64_t rows = 0;
-    int rc = kb_fit_ranges(k, "kb_fit_steps", first, n, &rows);
-    if (rc != RS_OK) return rc;
+    if ((rc = kb_fit_ranges(k, "kb_fit_steps", first, n, &rows)) != RS_OK) return rc;
     if (rows == 0) return RS_OK;
     if (!state || !action || !labels) {
         k->err = "kb_fit_steps: state, action or labels is NULL";
@@ -228,50 +174,38 @@ extern "C" int kb_fit_steps(kb_handle* k, const int32_t* agent, int32_t n, const
     int64_t longest = 0;
     for (int32_t i = 0; i < n; ++i) longest = std::max<int64_t>(longest, first[i + 1] - first[i]);
     if (chunk == 0) chunk = std::max<int32_t>(1, KB_FIT_CHUNK / (P + 1));  // about kb_fit's default in samples of one learner
-    HIPCHK(k, hipSetDevice(k->device));
-    if ((rc = kb_fit_prepare(k)) != RS_OK) return rc;
+    if ((rc = kb_fit_open(k)) != RS_OK) return rc;  // (d_work[8..11], kb_fit_wide_info, stay the last kb_fit's)
     kb_fit_state* p = k->fit;
-    k->gemm_fresh = false;
     std::vector<long long> rel((size_t)n + 1);
     for (int32_t i = 0; i <= n; ++i) rel[(size_t)i] = (long long)first[i];
-    // the log as it was recorded: rows x (4 nv + 8 S) bytes in, rows x S x 24 bytes of summaries out
-    FitStage st;
-    const size_t bytes = FitStage::pad(sizeof(int32_t) * (size_t)n) + FitStage::pad(sizeof(long long) * ((size_t)n + 1)) +
-                         FitStage::pad(sizeof(float) * R * (size_t)nv) + 6 * FitStage::pad(sizeof(int32_t) * RS) +
-                         FitStage::pad(sizeof(double) * RS);
-    HIPCHK(k, hipMalloc((void**)&st.base, bytes));
     kb::StepsArgs a;
     memset(&a, 0, sizeof a);
     a.D = k->D;
     a.K = k->K;
-    int32_t* d_agent = st.take<int32_t>((size_t)n);
-    long long* d_first = st.take<long long>((size_t)n + 1);
-    float* d_state = st.take<float>(R * (size_t)nv);
-    int32_t* d_action = st.take<int32_t>(RS);
-    int32_t* d_labels = st.take<int32_t>(RS);
-    a.y_at = st.take<int32_t>(RS);
-    a.changed = st.take<int32_t>(RS);
-    a.grown = st.take<int32_t>(RS);
-    a.m_after = st.take<int32_t>(RS);
-    a.f_at = st.take<double>(RS);
-    a.agent = d_agent;
-    a.first = d_first;
-    a.state = d_state;
-    a.action = d_action;
-    a.labels = d_labels;
     a.chunk = chunk;
     a.work = p->d_work;
-    // behind whatever is queued on either of the handle's streams
-    if (k->side && (rc = stream_after(k, &p->ev_in, k->side, k->stream)) != RS_OK) return rc;
+    // the log as it was recorded: rows x (4 nv + 8 S) bytes in, rows x S x 24 bytes of summaries out
+    int32_t *d_agent = nullptr, *d_action = nullptr, *d_labels = nullptr;
+    long long* d_first = nullptr;
+    float* d_state = nullptr;
+    FitStage st;
+    HIPCHK(k, st.alloc([&](FitStage& s) {
+        a.agent = d_agent = s.take<int32_t>((size_t)n);
+        a.first = d_first = s.take<long long>((size_t)n + 1);
+        a.state = d_state = s.take<float>(R * (size_t)nv);
+        a.action = d_action = s.take<int32_t>(RS);
+        a.labels = d_labels = s.take<int32_t>(RS);
+        a.y_at = s.take<int32_t>(RS);
+        a.changed = s.take<int32_t>(RS);
+        a.grown = s.take<int32_t>(RS);
+        a.m_after = s.take<int32_t>(RS);
+        a.f_at = s.take<double>(RS);
+    }));
     HIPCHK(k, hipMemcpyAsync(d_agent, agent, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, k->stream));
     HIPCHK(k, hipMemcpyAsync(d_first, rel.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, k->stream));
     HIPCHK(k, hipMemcpyAsync(d_state, state, sizeof(float) * R * (size_t)nv, hipMemcpyHostToDevice, k->stream));
     HIPCHK(k, hipMemcpyAsync(d_action, action, sizeof(int32_t) * RS, hipMemcpyHostToDevice, k->stream));
     HIPCHK(k, hipMemcpyAsync(d_labels, labels, sizeof(int32_t) * RS, hipMemcpyHostToDevice, k->stream));
-    HIPCHK(k, hipMemsetAsync(p->d_work, 0, sizeof(unsigned long long) * 4, k->stream));  // ([8..11], kb_fit_wide_info, stay the last kb_fit's)
-    p->fit_spans.on = k->spans.on;
-    p->fit_spans.reset();
-    p->fit_ms = 0.0;
     const unsigned grid = (unsigned)n * (unsigned)S;
     for (int64_t from = 0; from < longest; from += chunk) {  // (no launch runs longer than `chunk` rows of one agent)
         a.from = (long long)from;
@@ -289,6 +223,5 @@ extern "C" int kb_fit_steps(kb_handle* k, const int32_t* agent, int32_t n, const
     if (changed) HIPCHK(k, hipMemcpyAsync(changed, a.changed, sizeof(int32_t) * RS, hipMemcpyDeviceToHost, k->stream));
     if (grown) HIPCHK(k, hipMemcpyAsync(grown, a.grown, sizeof(int32_t) * RS, hipMemcpyDeviceToHost, k->stream));
     if (m_after) HIPCHK(k, hipMemcpyAsync(m_after, a.m_after, sizeof(int32_t) * RS, hipMemcpyDeviceToHost, k->stream));
-    if (k->side && (rc = stream_after(k, &p->ev_out, k->stream, k->side)) != RS_OK) return rc;
-    return kb_check(k);  // (waits for the stream)
+    return kb_fit_close(k);
 }

@@ -1,6 +1,7 @@
 // kb_fit_wide.hip -- kb_fit's chip-wide rounds for learners that hold large dictionaries (kb_set_fit_wide).
 // #included by rs_api.hip after kb_fit.hip.  It adds kernels of its own and shares only device functions with kb_kbrl.hip and
-// kb_fit.hip: score_queries (kb_score's body), predict_column, tie_draw, stretch_of, matvec_tri_tiles_lds, matvec_tri_combine_wide,
+// kb_fit.hip: score_queries (kb_score's body), predict_column, fit_decide and fit_epilogue (fit_learner's decision and epilogue),
+// block_scan1024 and walk_stretch (the work line of the repair rounds), matvec_tri_tiles_lds, matvec_tri_combine_wide,
 // finish_update(..., defer_rank1 = true), margin_update and rank1_units.
 //
 // fit_learner runs a learner's samples on ONE workgroup; every mistake then costs an O(m^2) mat-vec and, when it inserts, an O(m^2)
@@ -12,7 +13,7 @@
 //                            mistaken one gets predict_column (its kernel column into the K_f row) and, on f == 0, its tie draw.
 //                            No mistake: the cursor moves past the window
 //   fit_wide_plan_kernel     the tiles of the learners with a pending mistake laid end to end (prefix sums)
-//   fit_wide_matvec_kernel   every wave an equal stretch of that line (stretch_of): matvec_tri_tiles_lds
+//   fit_wide_matvec_kernel   every wave an equal stretch of that line (walk_stretch): matvec_tri_tiles_lds
 //   fit_wide_finish_kernel   per learner: matvec_tri_combine_wide, finish_update with the rank-1 update deferred; the sample's
 //                            branch, delta and size; the cursor moves past the mistake
 //   fit_wide_plan_kernel     the 16-row units of the learners that inserted, end to end
@@ -43,26 +44,10 @@ namespace kb {
 #define KB_FIT_WINDOW_MAX 256
 #define KB_FIT_ROUNDS 8        // rounds enqueued between two looks at the "learners done" word
 
-// inclusive sums of v over the 1,024 threads of the block (Hillis-Steele, heavy_plan_kernel's scan); sc[1023] is the total
-__device__ __forceinline__ long long fit_wide_scan1024(long long v, long long* sc) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    sc[t] = v;
-    __syncthreads();
-    for (int dd = 1; dd < 1024; dd <<= 1) {
-        const long long a = t >= dd ? sc[t - dd] : 0;
-        __syncthreads();
-        v += a;
-        sc[t] = v;
-        __syncthreads();
-    }
-    return v;
-}
-
 // which listed learners the rounds teach this chunk: those with samples in it whose dictionary holds min_m landmarks or more now.
 // They are listed in the order of the call (slot = how many came before), with their cursors at the chunk's first row.
 __global__ __launch_bounds__(1024) void fit_wide_classify_kernel(WideArgs A) {
-    __shared__ long long sc[1024];
+    __shared__ long long sc[1][1024];
     const FitArgs& F = A.F;
     const FitWide& W = A.W;
     long long carry = 0;
@@ -76,16 +61,17 @@ __global__ __launch_bounds__(1024) void fit_wide_classify_kernel(WideArgs A) {
             w = r0 < r1 && F.K.m[F.task[i]] >= W.min_m;
             W.mark[i] = w;
         }
-        const long long incl = fit_wide_scan1024(w, sc);
+        long long incl[1] = {w};
+        block_scan1024(incl, sc);
         if (w) {
-            const long long slot = carry + incl - 1;
+            const long long slot = carry + incl[0] - 1;
             W.list[slot] = i;
             W.cur[slot] = r0;
             W.end[slot] = r1;
             W.pend[slot] = 0;
             W.grew[slot] = 0;
         }
-        carry += sc[1023];
+        carry += sc[0][1023];
     }
     if (threadIdx.x == 0) {
         W.hdr[0] = (int32_t)carry;
@@ -93,11 +79,10 @@ __global__ __launch_bounds__(1024) void fit_wide_classify_kernel(WideArgs A) {
     }
 }
 
-// the learner of a slot is done with the chunk: fit_learner's epilogue (K.m is kept current by the finish kernel; thread 0)
+// the learner of a slot is done with the chunk: fit_learner's epilogue (K.m is kept current by the finish kernel, the counters
+// were added round by round; thread 0)
 __device__ __forceinline__ void fit_wide_epilogue(const KbState& K, const FitWide& W, int task, double f) {
-    K.f_last[task] = f;
-    K.m_last[task] = -1;  // the cache of the last kb_predict is gone: kb_update answers RS_ESTATE until a new kb_predict
-    K.kf_owner[task] = -1;
+    fit_epilogue(K, task, f, nullptr, nullptr);
     atomicAdd(&W.hdr[1], 1);
 }
 
@@ -161,14 +146,8 @@ __global__ __launch_bounds__(256) void fit_wide_decide_kernel(WideArgs A) {
         const long long r = cur + k;
         if (threadIdx.x < KB_DMAX) sm.x[threadIdx.x] = F.x[r * KB_DMAX + threadIdx.x];
         __syncthreads();
-        const double f = predict_column(D, K, sh, d, m, sm.x, sm);
-        int yp = f > 0.0 ? 1 : (f < 0.0 ? -1 : 0);
-        if (yp == 0) {  // (block-uniform: every thread holds the same f)
-            if (threadIdx.x == 0) sm.ired[0] = tie_draw(K, task, env, s);
-            __syncthreads();
-            yp = sm.ired[0];
-            __syncthreads();
-        }
+        double f = predict_column(D, K, sh, d, m, sm.x, sm);
+        const int yp = fit_decide(K, task, env, s, m, &f, sm);
         if (threadIdx.x == 0) {
             F.y_pred[r] = yp;
             F.f[r] = f;
@@ -206,7 +185,7 @@ __global__ __launch_bounds__(256) void fit_wide_decide_kernel(WideArgs A) {
 // which = 0: the mat-vec line (tiles of the learners with a pending mistake) -> mvbase; 1: the rank-1 line (16-row units of the
 // learners that inserted) -> r1base.  One workgroup, as heavy_plan_kernel.
 __global__ __launch_bounds__(1024) void fit_wide_plan_kernel(WideArgs A, int which) {
-    __shared__ long long sc[1024];
+    __shared__ long long sc[1][1024];
     const FitWide& W = A.W;
     long long* base_out = which ? W.r1base : W.mvbase;
     long long carry = 0;
@@ -223,9 +202,10 @@ __global__ __launch_bounds__(1024) void fit_wide_plan_kernel(WideArgs A, int whi
                 w = nb1 * (nb1 + 1) / 2 * 4;
             }
         }
-        const long long incl = fit_wide_scan1024(w, sc);
-        if (slot < A.nw) base_out[slot] = carry + incl - w;
-        carry += sc[1023];
+        long long incl[1] = {w};
+        block_scan1024(incl, sc);
+        if (slot < A.nw) base_out[slot] = carry + incl[0] - w;
+        carry += sc[0][1023];
     }
     if (threadIdx.x == 0) base_out[A.nw] = carry;
 }
@@ -235,17 +215,10 @@ __global__ __launch_bounds__(256, KB_MV_OCC) void fit_wide_matvec_kernel(WideArg
     const KbDev& D = A.F.D;
     const KbState& K = A.F.K;
     const FitWide& W = A.W;
-    long long lo, hi;
-    int slot = stretch_of(W.mvbase, A.nw, &lo, &hi);
-    if (slot < 0) return;
-    for (; slot < A.nw && lo < hi; ++slot) {
-        const long long sb = W.mvbase[slot], se = W.mvbase[slot + 1];
-        if (se <= lo) continue;  // (no work of its own, or entirely before the stretch)
+    walk_stretch(W.mvbase, A.nw, [&](int slot, long long a, long long b) {
         const int dict = A.F.task[W.list[slot]];
-        const long long a = lo > sb ? lo - sb : 0, b = (hi < se ? hi : se) - sb;
-        if (a < b) matvec_tri_tiles_lds(K, shells_of(D, K, dict), K.m[dict], (int)a, (int)b, slabs[threadIdx.x >> 6]);
-        lo = se;
-    }
+        matvec_tri_tiles_lds(K, shells_of(D, K, dict), K.m[dict], (int)a, (int)b, slabs[threadIdx.x >> 6]);
+    });
 }
 
 __global__ __launch_bounds__(256) void fit_wide_finish_kernel(WideArgs A) {
@@ -311,29 +284,17 @@ __global__ __launch_bounds__(256) void fit_wide_rank1_kernel(WideArgs A) {
     const KbDev& D = A.F.D;
     const KbState& K = A.F.K;
     const FitWide& W = A.W;
-    long long lo, hi;
-    int slot = stretch_of(W.r1base, A.nw, &lo, &hi);
-    if (slot < 0) return;
-    for (; slot < A.nw && lo < hi; ++slot) {
-        const long long sb = W.r1base[slot], se = W.r1base[slot + 1];
-        if (se <= lo) continue;
+    walk_stretch(W.r1base, A.nw, [&](int slot, long long u0, long long u1) {
         const int dict = A.F.task[W.list[slot]];
-        const int u0 = (int)(lo > sb ? lo - sb : 0), u1 = (int)((hi < se ? hi : se) - sb);
-        if (u0 < u1) rank1_units(K, shells_of(D, K, dict), W.gm[slot], W.gdelta[slot], D.tri, u0, 1, u1);
-        lo = se;
-    }
+        rank1_units(K, shells_of(D, K, dict), W.gm[slot], W.gdelta[slot], D.tri, (int)u0, 1, (int)u1);
+    });
 }
 
 }  // namespace kb
 
 static int kb_fit_wide_window(const kb_handle* k) { return k->fit_wide_window ? k->fit_wide_window : KB_FIT_WINDOW; }
 
-static size_t kb_fit_wide_bytes(kb_handle* k, int32_t n) {
-    const size_t N = (size_t)n;
-    return 5 * FitStage::pad(sizeof(int32_t) * N) + FitStage::pad(sizeof(int32_t) * 4) + 4 * FitStage::pad(sizeof(long long) * (N + 1)) +
-           FitStage::pad(sizeof(double) * N) + FitStage::pad(sizeof(double) * N * (size_t)kb_fit_wide_window(k));
-}
-
+// the rounds' arrays, behind kb_fit's own in the call's staged block (kb_fit's layout function calls this)
 static void kb_fit_wide_take(kb_handle* k, FitStage& st, int32_t n, kb::FitWide* W) {
     const size_t N = (size_t)n;
     W->mark = st.take<int32_t>(N);
@@ -402,13 +363,8 @@ extern "C" int kb_set_fit_wide(kb_handle* k, int32_t min_landmarks, int32_t wind
         k->err = "kb_set_fit_wide: window = " + std::to_string(window) + " (0: the default, else 1 .. " + std::to_string(KB_FIT_WINDOW_MAX) + ")";
         return RS_EINVAL;
     }
-    if (k->frozen || k->ref || k->D.shared) {
-        k->err = std::string("kb_set_fit_wide: ") +
-                 (k->ref ? "a by-reference handle (kb_deploy_ref)" : k->frozen ? "an inference-only handle (kb_deploy, kb_import_agents)"
-                                                                               : "a shared-dictionary handle") +
-                 " does not learn through kb_fit";
-        return RS_ESTATE;
-    }
+    const int rc = kb_fit_wide_can_set(k, "kb_set_fit_wide");
+    if (rc != RS_OK) return rc;
     k->fit_wide_min = min_landmarks;
     k->fit_wide_window = window;
     return RS_OK;
@@ -429,13 +385,8 @@ extern "C" int kb_set_fit_wide_plus(kb_handle* k, int32_t on) {
         k->err = "kb_set_fit_wide_plus: on = " + std::to_string(on) + " (0: Projectron++ keeps the narrow path, the default; 1: the rounds teach it too)";
         return RS_EINVAL;
     }
-    if (k->frozen || k->ref || k->D.shared) {
-        k->err = std::string("kb_set_fit_wide_plus: ") +
-                 (k->ref ? "a by-reference handle (kb_deploy_ref)" : k->frozen ? "an inference-only handle (kb_deploy, kb_import_agents)"
-                                                                               : "a shared-dictionary handle") +
-                 " does not learn through kb_fit";
-        return RS_ESTATE;
-    }
+    const int rc = kb_fit_wide_can_set(k, "kb_set_fit_wide_plus");
+    if (rc != RS_OK) return rc;
     k->fit_wide_plus = on;
     return RS_OK;
 }

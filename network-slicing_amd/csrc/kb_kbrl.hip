@@ -1758,6 +1758,31 @@ __global__ __launch_bounds__(256, KB_SMALL_OCC) void update_small_kernel(CtlArgs
 // largest one.  heavy_plan_kernel (one workgroup) lays the learners' work end to end -- mat-vec: n_b^2 x 8 tile-row
 // passes (a unit = one column block and row class, n_b passes), rank-1: n_b^2 x 4 units -- and every wave of the two wide
 // kernels takes an equal stretch of that line (whole units; one binary search for where its stretch begins).
+// The building blocks of every work line (the repair rounds here, kb_prune.hip, kb_fit_wide.hip; kb_rebuild.hip's uniform line
+// takes wave_share alone): block_scan1024, wave_share / stretch_of, walk_stretch.  All integer (tests/test_gpu_work_line.py).
+// inclusive sums over the 1,024 threads of the block of N values per thread, in ONE pass (Hillis-Steele): v[q] comes back as
+// the sum of threads 0 .. t, sc[q][1023] holds the total.  Begins with a barrier, so that a previous pass's readers of sc are done.
+template <int N>
+__device__ __forceinline__ void block_scan1024(long long (&v)[N], long long (&sc)[N][1024]) {
+    const int t = threadIdx.x;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < N; ++q) sc[q][t] = v[q];
+    __syncthreads();
+    for (int dd = 1; dd < 1024; dd <<= 1) {
+        long long a[N];
+#pragma unroll
+        for (int q = 0; q < N; ++q) a[q] = t >= dd ? sc[q][t - dd] : 0;
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < N; ++q) {
+            v[q] += a[q];
+            sc[q][t] = v[q];
+        }
+        __syncthreads();
+    }
+}
+
 __global__ __launch_bounds__(1024) void heavy_plan_kernel(KbDev D, KbState K) {
     __shared__ long long sc[2][1024];
     const int count = K.heavy[0], t = threadIdx.x;
@@ -1775,23 +1800,11 @@ __global__ __launch_bounds__(1024) void heavy_plan_kernel(KbDev D, KbState K) {
                 wr1 = (D.tri ? nb1 * (nb1 + 1) / 2 : nb1 * nb1) * 4;
             }
         }
-        __syncthreads();
-        sc[0][t] = wmv;
-        sc[1][t] = wr1;
-        __syncthreads();
-        long long imv = wmv, ir1 = wr1;
-        for (int dd = 1; dd < 1024; dd <<= 1) {  // Hillis-Steele inclusive scans
-            const long long a = t >= dd ? sc[0][t - dd] : 0, b = t >= dd ? sc[1][t - dd] : 0;
-            __syncthreads();
-            imv += a;
-            ir1 += b;
-            sc[0][t] = imv;
-            sc[1][t] = ir1;
-            __syncthreads();
-        }
+        long long incl[2] = {wmv, wr1};
+        block_scan1024(incl, sc);
         if (slot < count) {
-            K.hv_mvbase[slot] = carry_mv + imv - wmv;
-            K.hv_r1base[slot] = carry_r1 + ir1 - wr1;
+            K.hv_mvbase[slot] = carry_mv + incl[0] - wmv;
+            K.hv_r1base[slot] = carry_r1 + incl[1] - wr1;
         }
         carry_mv += sc[0][1023];
         carry_r1 += sc[1][1023];
@@ -1802,12 +1815,16 @@ __global__ __launch_bounds__(1024) void heavy_plan_kernel(KbDev D, KbState K) {
     }
 }
 
-// the stretch [lo, hi) of wave w of the launch on a work line of `total`; the slot whose work contains `lo`
-__device__ __forceinline__ int stretch_of(const long long* base, int count, long long* lo, long long* hi) {
-    const long long total = base[count];
+// the share [lo, hi) of this wave of the launch on a work line of `total` units: equal shares, in the order of the waves
+__device__ __forceinline__ void wave_share(long long total, long long* lo, long long* hi) {
     const long long nwaves = (long long)gridDim.x * (blockDim.x >> 6), w = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     *lo = total * w / nwaves;
     *hi = total * (w + 1) / nwaves;
+}
+
+// this wave's stretch [lo, hi) of the work line base[0 .. count]; the slot whose work contains `lo` (-1: the stretch is empty)
+__device__ __forceinline__ int stretch_of(const long long* base, int count, long long* lo, long long* hi) {
+    wave_share(base[count], lo, hi);
     if (*lo >= *hi) return -1;
     int a = 0, b = count;  // last slot with base[slot] <= lo
     while (b - a > 1) {
@@ -1815,6 +1832,23 @@ __device__ __forceinline__ int stretch_of(const long long* base, int count, long
         if (base[mid] <= *lo) a = mid; else b = mid;
     }
     return a;
+}
+
+// A wave walks its stretch of the work line base[0 .. count]: body(slot, a, b) for the units [a, b) of the slot's own work, slot by
+// slot; slots without work are passed by.  `body` is called in place: keep it at this outer loop -- lambdas inside the triangle
+// mat-vec itself once cost update_small_kernel 608 B per lane of scratch (tools/check_resources.py).
+template <class Body>
+__device__ __forceinline__ void walk_stretch(const long long* base, int count, Body body) {
+    long long lo, hi;
+    int slot = stretch_of(base, count, &lo, &hi);
+    if (slot < 0) return;
+    for (; slot < count && lo < hi; ++slot) {
+        const long long sb = base[slot], se = base[slot + 1];
+        if (se <= lo) continue;  // (no work of its own, or entirely before the stretch)
+        const long long a = lo > sb ? lo - sb : 0, b = (hi < se ? hi : se) - sb;
+        if (a < b) body(slot, a, b);
+        lo = se;
+    }
 }
 
 #ifndef KB_MV_OCC
@@ -1831,27 +1865,18 @@ __global__ __launch_bounds__(256, KB_MV_OCC) void heavy_matvec_kernel(KbDev D, K
         K.hv_work[0] += (unsigned long long)K.hv_mvbase[count];
         K.hv_work[2] += 1;
     }
-    long long lo, hi;
-    int slot = stretch_of(K.hv_mvbase, count, &lo, &hi);
-    if (slot < 0) return;
-    for (; slot < count && lo < hi; ++slot) {
-        const long long sb = K.hv_mvbase[slot], se = K.hv_mvbase[slot + 1];
-        if (se <= lo) continue;  // (no work of its own, or entirely before the stretch)
+    walk_stretch(K.hv_mvbase, count, [&](int slot, long long a, long long b) {
         const int dict = dict_of(D, K.heavy[4 + slot]);
         const int m = K.m[dict];
-        const long long nb = (m + 63) >> 6;
-        const long long a = lo > sb ? lo - sb : 0, b = (hi < se ? hi : se) - sb;
         if (D.tri) {  // the work line counts tiles
-            if (a < b) {
-                if (KB_MV_LDS) matvec_tri_tiles_lds(K, shells_of(D, K, dict), m, (int)a, (int)b, slabs[threadIdx.x >> 6]);
-                else matvec_tri_tiles(K, shells_of(D, K, dict), m, (int)a, 1, (int)b);
-            }
+            if (KB_MV_LDS) matvec_tri_tiles_lds(K, shells_of(D, K, dict), m, (int)a, (int)b, slabs[threadIdx.x >> 6]);
+            else matvec_tri_tiles(K, shells_of(D, K, dict), m, (int)a, 1, (int)b);
         } else {      // units whose first pass lies in [lo, hi)
+            const long long nb = (m + 63) >> 6;
             const int u0 = (int)((a + nb - 1) / nb), u1 = (int)((b + nb - 1) / nb);
             if (u0 < u1) matvec_partials<1>(K, shells_of(D, K, dict), m, u0, 1, u1);
         }
-        lo = se;
-    }
+    });
 }
 
 __global__ __launch_bounds__(256) void heavy_rank1_kernel(KbDev D, KbState K) {
@@ -1861,17 +1886,10 @@ __global__ __launch_bounds__(256) void heavy_rank1_kernel(KbDev D, KbState K) {
         K.hv_work[1] += (unsigned long long)K.hv_r1base[count];
         K.hv_work[3] += 1;
     }
-    long long lo, hi;
-    int slot = stretch_of(K.hv_r1base, count, &lo, &hi);
-    if (slot < 0) return;
-    for (; slot < count && lo < hi; ++slot) {
-        const long long sb = K.hv_r1base[slot], se = K.hv_r1base[slot + 1];
-        if (se <= lo) continue;
+    walk_stretch(K.hv_r1base, count, [&](int slot, long long u0, long long u1) {
         const int dict = dict_of(D, K.heavy[4 + slot]);
-        const int u0 = (int)(lo > sb ? lo - sb : 0), u1 = (int)((hi < se ? hi : se) - sb);
-        if (u0 < u1) rank1_units(K, shells_of(D, K, dict), K.hv_m[slot], K.hv_delta[slot], D.tri, u0, 1, u1);
-        lo = se;
-    }
+        rank1_units(K, shells_of(D, K, dict), K.hv_m[slot], K.hv_delta[slot], D.tri, (int)u0, 1, (int)u1);
+    });
 }
 
 __global__ __launch_bounds__(256) void heavy_finish_kernel(CtlArgs A) {

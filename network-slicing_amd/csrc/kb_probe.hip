@@ -18,6 +18,15 @@
 //                      last mat-vec did not cover holds whatever it held before (tests/test_gpu_update_chain.py)
 // By-reference handles (kb_ref.hip) answer the first two: their scores are per task as everywhere (they keep no W: zeros), their rows are
 // those of the store's dictionary the map names for (e, s) -- which no selection may ever have changed.
+//
+// And ONE entry point that launches a kernel, on buffers of its own (no handle): kb_dev_work_line runs the work-line helpers of
+// kb_kbrl.hip on a line the test supplies (tests/test_gpu_work_line.py).
+//   op 0, the walker   in = base[0 .. count], grid workgroups of 256 threads call walk_stretch; lane 0 of every wave counts a hit
+//                      on, and writes its slot as the owner of, every unit it is handed: out0 = hits [total + 1], out1 = owner
+//                      [total + 1] (-1: nobody's), total = base[count]; the last entry lies past the line
+//   op 1, the scan     in = values [2][count]; one workgroup runs block_scan1024 in passes of 1,024 with a carry, as the plan
+//                      kernels do: out0 = the inclusive sums of row 0 by the one-value scan [count], out1 = those of both rows
+//                      by the two-value scan [2][count]
 
 extern "C" int kb_dev_get_scores(kb_handle* k, double* F, double* W, int32_t* fdirect) {
     if (!k) return RS_EINVAL;
@@ -152,4 +161,76 @@ extern "C" int kb_dev_get_update_rows(kb_handle* k, int e, int s, int32_t max_m,
                                 sizeof(double) * 128 * (size_t)(b + 1), hipMemcpyDeviceToHost));
     }
     return RS_OK;
+}
+
+namespace kb {
+
+__global__ __launch_bounds__(1024) void work_line_probe_kernel(int op, const long long* in, int count, void* out0, void* out1) {
+    if (op == 0) {
+        int32_t *hits = (int32_t*)out0, *owner = (int32_t*)out1;
+        walk_stretch(in, count, [&](int slot, long long a, long long b) {
+            if ((threadIdx.x & 63) == 0)
+                for (long long u = a; u < b; ++u) {
+                    atomicAdd(&hits[in[slot] + u], 1);
+                    owner[in[slot] + u] = slot;
+                }
+        });
+        return;
+    }
+    __shared__ long long sc1[1][1024], sc2[2][1024];
+    long long *one = (long long*)out0, *two = (long long*)out1;
+    long long carry1 = 0, carry2[2] = {0, 0};
+    for (int b0 = 0; b0 < count; b0 += 1024) {
+        const int i = b0 + (int)threadIdx.x;
+        long long v1[1] = {i < count ? in[i] : 0};
+        long long v2[2] = {v1[0], i < count ? in[count + i] : 0};
+        block_scan1024(v1, sc1);
+        block_scan1024(v2, sc2);
+        if (i < count) {
+            one[i] = carry1 + v1[0];
+            two[i] = carry2[0] + v2[0];
+            two[count + i] = carry2[1] + v2[1];
+        }
+        carry1 += sc1[0][1023];
+        carry2[0] += sc2[0][1023];
+        carry2[1] += sc2[1][1023];
+    }
+}
+
+}  // namespace kb
+
+// the line and the sizes are checked here, the kernel trusts them: base[0] = 0, no step down, at most 2^24 units; out0 / out1 hold
+// what the op writes (above).  Values of the scan: any int64 whose sums stay in range.
+extern "C" int kb_dev_work_line(int device, int op, const int64_t* in, int32_t count, int32_t grid, void* out0, void* out1) {
+    if ((op != 0 && op != 1) || !in || count < 1 || count > (1 << 20) || !out0 || !out1) return RS_EINVAL;
+    size_t in_bytes = sizeof(int64_t) * 2 * (size_t)count, out0_bytes = sizeof(int64_t) * (size_t)count, out1_bytes = 2 * out0_bytes;
+    if (op == 0) {
+        if (grid < 1 || grid > 1024 || in[0] != 0) return RS_EINVAL;
+        for (int32_t i = 0; i < count; ++i)
+            if (in[i + 1] < in[i]) return RS_EINVAL;
+        if (in[count] > ((int64_t)1 << 24)) return RS_EINVAL;
+        in_bytes = sizeof(int64_t) * ((size_t)count + 1);
+        out0_bytes = out1_bytes = sizeof(int32_t) * ((size_t)in[count] + 1);  // (and one entry past the line, which nobody may touch)
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return RS_EHIP;
+    void *d_in = nullptr, *d_0 = nullptr, *d_1 = nullptr;
+    int rc = RS_EHIP;
+    do {
+        if (hipMalloc(&d_in, in_bytes) != hipSuccess || hipMalloc(&d_0, out0_bytes) != hipSuccess || hipMalloc(&d_1, out1_bytes) != hipSuccess) break;
+        if (hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (hipMemset(d_0, 0, out0_bytes) != hipSuccess || hipMemset(d_1, op == 0 ? 0xff : 0, out1_bytes) != hipSuccess) break;
+        hipLaunchKernelGGL(kb::work_line_probe_kernel, dim3(op == 0 ? (unsigned)grid : 1u), dim3(op == 0 ? 256 : 1024), 0, 0, op,
+                           (const long long*)d_in, (int)count, d_0, d_1);
+        if (hipGetLastError() != hipSuccess) break;
+        if (hipDeviceSynchronize() != hipSuccess) break;
+        if (hipMemcpy(out0, d_0, out0_bytes, hipMemcpyDeviceToHost) != hipSuccess) break;
+        if (hipMemcpy(out1, d_1, out1_bytes, hipMemcpyDeviceToHost) != hipSuccess) break;
+        rc = RS_OK;
+    } while (0);
+    if (d_in) (void)hipFree(d_in);
+    if (d_0) (void)hipFree(d_0);
+    if (d_1) (void)hipFree(d_1);
+    if (hipDeviceSynchronize() != hipSuccess) rc = RS_EHIP;
+    return rc;
 }

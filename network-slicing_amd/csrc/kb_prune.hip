@@ -22,8 +22,8 @@
 //                          update writes it before it reads it) and the coefficients of step 3.  The downdate's waves then read
 //                          p from coalesced rows, and none of them reads the column while another rewrites it.
 //   prune_downdate_kernel  step 4, the hot path: the triangle tiles of all listed dictionaries laid end to end by
-//                          prune_plan_kernel, an equal stretch per wave (units of sixteen rows: 8 KB read, 8 KB written, 16-byte
-//                          accesses), the shape of heavy_rank1_kernel.
+//                          prune_plan_kernel (block_scan1024), an equal stretch per wave (walk_stretch; units of sixteen rows:
+//                          8 KB read, 8 KB written, 16-byte accesses), the shape of heavy_rank1_kernel and its helpers (kb_kbrl.hip).
 //   prune_move_kernel      steps 5-7.
 // and prune_finish_kernel once per touched dictionary: the chains, the off-grid count, the version, the predict cache.
 //
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256) void prune_choose_kernel(PruneArgs a) {
 // the downdate's work line: 4 units of sixteen rows per stored tile of every active dictionary, end to end.  The byte count
 // (kb_get_prune_work) takes only the units that hold rows: all four of a full block row's tiles, ceil(rows / 16) of the last one's.
 __global__ __launch_bounds__(1024) void prune_plan_kernel(PruneArgs a) {
-    __shared__ long long sc[1024];
+    __shared__ long long sc[1][1024];
     __shared__ unsigned long long filled;
     const int count = (int)a.info[0], t = threadIdx.x;
     long long carry = 0;
@@ -200,19 +200,10 @@ __global__ __launch_bounds__(1024) void prune_plan_kernel(PruneArgs a) {
             w = nb * (nb + 1) / 2 * 4;
             atomicAdd(&filled, (unsigned long long)((nb - 1) * nb / 2 * 4 + nb * ((m - 64 * (nb - 1) + 15) >> 4)));
         }
-        __syncthreads();
-        sc[t] = w;
-        __syncthreads();
-        long long inc = w;
-        for (int dd = 1; dd < 1024; dd <<= 1) {
-            const long long v = t >= dd ? sc[t - dd] : 0;
-            __syncthreads();
-            inc += v;
-            sc[t] = inc;
-            __syncthreads();
-        }
-        if (li < count) a.base[li] = carry + inc - w;
-        carry += sc[1023];
+        long long inc[1] = {w};
+        block_scan1024(inc, sc);
+        if (li < count) a.base[li] = carry + inc[0] - w;
+        carry += sc[0][1023];
     }
     if (t == 0) {
         a.base[count] = carry;
@@ -270,17 +261,10 @@ __device__ __forceinline__ void prune_units(const KbState& K, const uint64_t* sh
 __global__ __launch_bounds__(256) void prune_downdate_kernel(PruneArgs a) {
     const int count = (int)a.info[0];
     if (count == 0) return;
-    long long lo, hi;
-    int slot = stretch_of(a.base, count, &lo, &hi);
-    if (slot < 0) return;
-    for (; slot < count && lo < hi; ++slot) {
-        const long long sb = a.base[slot], se = a.base[slot + 1];
-        if (se <= lo) continue;  // (no work of its own, or entirely before the stretch)
+    walk_stretch(a.base, count, [&](int slot, long long u0, long long u1) {
         const int dict = a.list[slot];
-        const int u0 = (int)(lo > sb ? lo - sb : 0), u1 = (int)((hi < se ? hi : se) - sb);
-        if (u0 < u1) prune_units(a.K, shells_of(a.D, a.K, dict), a.K.m[dict], a.q[slot], u0, u1);
-        lo = se;
-    }
+        prune_units(a.K, shells_of(a.D, a.K, dict), a.K.m[dict], a.q[slot], (int)u0, (int)u1);
+    });
 }
 
 // Steps 5-7, a workgroup per active dictionary.  Row / column m - 1 of Kinv go to row / column r: for every k other than r and

@@ -157,18 +157,12 @@ __global__ __launch_bounds__(256) void rebuild_small_kernel(RebuildArgs a) {
     }
 }
 
-// the stretch [lo, hi) of this wave on a work line of n_act x per units
-__device__ __forceinline__ void rebuild_stretch(long long total, long long* lo, long long* hi) {
-    const long long nwaves = (long long)gridDim.x * (blockDim.x >> 6), w = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    *lo = total * w / nwaves;
-    *hi = total * (w + 1) / nwaves;
-}
-
+// (the rounds' work lines are uniform, n_act x per units: a wave's share by wave_share, kb_kbrl.hip, its slots by division)
 __global__ __launch_bounds__(256, KB_MV_OCC) void rebuild_matvec_kernel(RebuildArgs a) {
     __shared__ double slabs[4][8 * KB_SLAB_LD];
     const long long nb = (a.j + 63) >> 6, nt = nb * (nb + 1) / 2;
     long long lo, hi;
-    rebuild_stretch((long long)a.n_act * nt, &lo, &hi);
+    wave_share((long long)a.n_act * nt, &lo, &hi);
     while (lo < hi) {
         const long long slot = lo / nt, t0 = lo - slot * nt;
         const long long t1 = hi - slot * nt < nt ? hi - slot * nt : nt;
@@ -205,7 +199,7 @@ __global__ __launch_bounds__(256) void rebuild_finish_kernel(RebuildArgs a) {
 __global__ __launch_bounds__(256) void rebuild_rank1_kernel(RebuildArgs a) {
     const long long nb1 = (a.j + 1 + 63) >> 6, nu = nb1 * (nb1 + 1) / 2 * 4;
     long long lo, hi;
-    rebuild_stretch((long long)a.n_act * nu, &lo, &hi);
+    wave_share((long long)a.n_act * nu, &lo, &hi);
     while (lo < hi) {
         const long long slot = lo / nu, u0 = lo - slot * nu;
         const long long u1 = hi - slot * nu < nu ? hi - slot * nu : nu;

@@ -31,7 +31,8 @@ FORK = ['fork_count_kernel', 'fork_scan_kernel', 'fork_tables_kernel', 'fork_she
 # is its Projectron++ instance (fit_plus_kernel: the same loop around apply_update_plus)
 FIT_SCRATCH = {'fit_kernel': 0, 'fit_plus_kernel': 0, 'score_kernel': 0}
 # kb_fit's chip-wide rounds (kb_fit_wide.hip): reported, and held to no scratch at all -- the scan is score_kernel's
-# body, the two streaming kernels are heavy_matvec_kernel's and heavy_rank1_kernel's loops on a work line of their own
+# body, the two streaming kernels call the walker heavy_matvec_kernel and heavy_rank1_kernel call (walk_stretch, kb_kbrl.hip) on a
+# work line of their own
 FIT_SCRATCH.update({k: 0 for k in ('fit_wide_classify_kernel', 'fit_wide_scan_kernel', 'fit_wide_decide_kernel', 'fit_wide_plan_kernel',
                                    'fit_wide_matvec_kernel', 'fit_wide_finish_kernel', 'fit_wide_rank1_kernel')})
 # kb_fit_steps (kb_fit_steps.hip): fit_learner's loop around the cached-prefix column, in both update rules: no scratch
