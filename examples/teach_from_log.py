@@ -2,7 +2,8 @@
 """Teach agents from a log of control steps, with the sample augmentation done on the device (VecKBRL.fit_steps).
 
 1. A small fleet learns in the resident closed loop while (state, action, SLA labels) of every control step are logged --
-   some 250 bytes per agent and step.
+   some 250 bytes per agent and step.  --teacher-algorithm projectron_plus makes that loop a Projectron++ loop
+   (VecKBRL(..., control_plus=True)): a pupil taught from its log in the same algorithm ends with the teacher's sizes.
 2. A fresh handle, in either algorithm, is taught from the log alone: fit_steps stages the log as it is and the kernel
    generates each step's up to n_prbs + 1 samples next to the loop that consumes them.  (In 'projectron' mode the sizes it
    reaches are printed beside the closed loop's: the two take the same decisions except within rounding of zero.)
@@ -30,6 +31,8 @@ def main():
     ap.add_argument('--scenario', type=int, default=0)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--algorithm', choices=['projectron', 'projectron_plus'], default='projectron')
+    ap.add_argument('--teacher-algorithm', choices=['projectron', 'projectron_plus'], default='projectron',
+                    help='the rule of the closed loop that produces the log (projectron_plus turns set_control_plus on)')
     a = ap.parse_args()
     cfg = make_config(a.scenario, n_envs=a.agents)
     dims, n_prbs, n = [10] * cfg.n_embb + [3] * cfg.n_mmtc, cfg.n_prbs, a.agents
@@ -38,7 +41,8 @@ def main():
 
     # 1. the closed loop learns; the host keeps what update_control is given: the state an action was chosen in, the action, the labels
     env = VecRanSlice(n_envs=n, cfg=cfg, fading=fading, seed=a.seed)
-    teacher = VecKBRL(n, dims, n_prbs, capacity=1024, pool_bytes=256 << 20)
+    teacher = VecKBRL(n, dims, n_prbs, capacity=1024, pool_bytes=256 << 20, algorithm=a.teacher_algorithm,
+                      control_plus=a.teacher_algorithm == 'projectron_plus')
     teacher.reset(ia, sf)
     state = env.reset()
     env.enqueue_step(ia)

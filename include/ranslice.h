@@ -424,7 +424,9 @@ int kb_get_flags(kb_handle* k, int32_t* flags);
  * update), as their kernels count them: work[0] tiles of Kinv the mat-vec kernel read (32,768 bytes each), work[1] units of
  * the rank-1 kernel (8,192 bytes read + 8,192 written each), work[2] / work[3] launches of either that had work; work[4] scoring passes that
  * evaluated landmarks' exponentials one by one (outlier states, off-grid landmarks), work[5] the landmarks they evaluated --
- * both counted by developer builds only (-DKB_COUNT_DIRECT), 0 otherwise */
+ * both counted by developer builds only (-DKB_COUNT_DIRECT), 0 otherwise; work[6] the samples that ran the mat-vec in the closed
+ * loop's Projectron++ mode (kb_set_control_plus: branches 1-4 of its candidates) -- that mode queues no repair, so work[0..3] stay
+ * as they are while it runs */
 int kb_get_repair_work(kb_handle* k, uint64_t work[8]);
 int kb_kernel_time_ms(kb_handle* k, double* avg_ms, int64_t* launches);
 /* the same per phase: ms[0] / n[0] the update phase (update_control_kernel and its repair kernels; shared mode: the scan
@@ -702,7 +704,8 @@ int kb_fit_time_ms(kb_handle* k, double ms[2], uint64_t work[4]);
  * part of kb_save_state blobs or agent files, and kb_fork, kb_deploy, kb_import_agents, kb_unshare and kb_share do not carry it
  * over (the destination keeps its own).  While a handle is in Projectron++ mode the closed control loop does not learn through
  * it: kb_update_control, and kb_step_resident / kb_run_resident with learning on, answer RS_ESTATE (kb_set_learning(k, 0), or
- * kb_set_algorithm back, lifts that); everything that only reads dictionaries or moves them works as before.
+ * kb_set_algorithm back, lifts that; so does kb_set_control_plus(k, 1), below, under which the loop learns by this rule);
+ * everything that only reads dictionaries or moves them works as before.
  * kb_set_algorithm: RS_EINVAL for an unknown value; RS_ESTATE for KB_ALG_PROJECTRON_PLUS on an inference-only, a by-reference
  * or a shared-dictionary handle (they do not learn through kb_update / kb_fit). */
 #define KB_ALG_PROJECTRON 0
@@ -779,6 +782,27 @@ int kb_get_fit_wide_plus(kb_handle* k, int32_t* on);
 int kb_fit_steps(kb_handle* k, const int32_t* agent, int32_t n, const int64_t* first /* [n + 1] */,
                  const float* state /* [rows][nv] */, const int32_t* action /* [rows][S] */, const int32_t* labels /* [rows][S] */,
                  int32_t chunk, double* f_at, int32_t* y_at, int32_t* changed, int32_t* grown, int32_t* m_after);
+
+/* ---- the closed control loop in Projectron++ mode (csrc/kb_control_plus.hip).  kb_set_control_plus(k, on):
+ * on = 0 (the default): as above -- while the handle is in Projectron++ mode kb_update_control, and kb_step_resident /
+ * kb_run_resident with learning on, answer RS_ESTATE.  on = 1: while the handle is in Projectron++ mode those three calls run
+ * and learn by the margin rule: per learner the step's row (the state the action was taken in, the executed allocation, its SLA
+ * label) goes through exactly what kb_fit_steps does with that row in Projectron++ mode -- the candidates a = action .. n_prbs
+ * on +1, 0 .. action on -1, in that order, each through ProjectronPlus.update -- after update_control's bookkeeping
+ * (kbrl_control.py:88-101): y_pred from f at the executed allocation (kb_fit_steps's f_at; an exact 0 against a populated
+ * dictionary draws from the learner's stream), the hit, the accuracy table, the security factor.  Landmarks, coefficients, all
+ * of Kinv, sizes, flags and the per-learner statistics the step adds are BIT FOR BIT kb_fit_steps's for the same rows; hits ==
+ * (labels == y_at) wherever f_at != 0.  One 256-thread workgroup per learner, one launch per step, inside the update phase's
+ * timing span (kb_phase_times_ms, kb_kernel_times_ms kind 0); the repair queue and the chip-wide rounds are not used and
+ * kb_get_repair_work reports zeros for them.  The captured loop of kb_run_resident carries the same launch; setting this
+ * switch or kb_set_algorithm to another value drops a captured loop.  In Projectron mode the switch has no effect: kernels,
+ * launches and bits stay what they are.  Host state of the handle like the algorithm: not part of kb_save_state blobs or agent
+ * files, not carried over by kb_fork, kb_deploy, kb_import_agents, kb_share or kb_unshare.  RS_EINVAL for any value but 0 and 1;
+ * RS_ESTATE on an inference-only, a by-reference or a shared-dictionary handle.
+ * Cost: late in learning many times Projectron's loop -- one workgroup walks Kinv once per candidate inside the margin
+ * (batching those mat-vecs is not built). */
+int kb_set_control_plus(kb_handle* k, int32_t on);
+int kb_get_control_plus(kb_handle* k, int32_t* on);
 
 #ifdef __cplusplus
 }

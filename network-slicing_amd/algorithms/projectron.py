@@ -129,12 +129,15 @@ class Projectron:
 class ProjectronPlus(Projectron):
     """Projectron++ (projectron.py:66-107): update(x, y) also acts on a sample classified correctly inside the margin,
     0 < y f < 1 -- a scaled projection that never adds a landmark.  The private one-learner agent runs in Projectron++ mode
-    (kb_set_algorithm); predict, update, fit, decision_function and Kinv work as on Projectron.  Not accepted by
-    kbrl_control.KBRL_Control, whose closed loop implements Projectron's rule: fit logged control steps instead
-    (ranslice.kbrl_dev.augmented_samples + VecKBRL.fit).
+    (kb_set_algorithm); predict, update, fit, decision_function and Kinv work as on Projectron.  Accepted by
+    kbrl_control.KBRL_Control only when every learner of the list is a ProjectronPlus whose control_plus is true (below); otherwise
+    fit logged control steps instead (ranslice.kbrl_dev.augmented_samples + VecKBRL.fit).
+    control_plus (a plain attribute, False by default): the learner opts into the closed control loop's margin-rule update phase
+    (VecKBRL.set_control_plus); KBRL_Control reads it when it is constructed.
     wide_plus (a plain attribute, False by default): whether fit(..., wide=...) lets the chip-wide rounds teach this learner too;
     fit hands it to VecKBRL.set_fit_wide_plus before every call.  Off, fit keeps the one-workgroup path whatever `wide` says."""
     ALGORITHM = 'projectron_plus'
+    control_plus = False
 
     def __init__(self, kernel, eta=0.1, capacity=4096):
         super().__init__(kernel, eta=eta, capacity=capacity)

@@ -74,6 +74,8 @@ struct kb_handle {
     int32_t alg = KB_ALG_PROJECTRON;  // kb_set_algorithm: the rule of the next kb_update / kb_fit; host state of the handle, never copied or saved
     int32_t fit_wide_min = 0, fit_wide_window = 0;  // kb_set_fit_wide: host state of the handle like alg, never copied or saved (kb_fit_wide.hip)
     int32_t fit_wide_plus = 0;                      // kb_set_fit_wide_plus: 1 = the rounds also teach in Projectron++ mode; host state as well
+    int32_t control_plus = 0;                       // kb_set_control_plus: 1 = the closed control loop learns in Projectron++ mode; host state as well (kb_control_plus.hip)
+    unsigned long long* d_ctl_work = nullptr;       // [4] control_plus_kernel's counters (allocated when the switch is first set)
     // kb_fork / kb_deploy into this handle (kb_fork.hip)
     hipEvent_t ev_fork_in = nullptr, ev_fork_out = nullptr;
     int32_t* d_fork_idx = nullptr;   // [n_envs] source agent of every agent
@@ -101,6 +103,7 @@ static void kb_ref_release(kb_handle* k);
 static void kb_rebuild_release(kb_handle* k);  // kb_rebuild.hip
 static void kb_bridge_release(kb_handle* k);   // kb_bridge.hip
 static void kb_fit_release(kb_handle* k);      // kb_fit.hip
+static void kb_control_plus_release(kb_handle* k);  // kb_control_plus.hip
 static kb_handle* kb_ref_store(kb_handle* k);
 static int kb_ref_dict(kb_handle* k, size_t task);
 static int kb_ref_select(kb_handle* k, const float* d_state);  // the scoring of launch_select: one fused kernel
@@ -440,6 +443,18 @@ static void kb_drop_graph(kb_handle* k) {
     k->g_env = nullptr;
 }
 
+// for the setters that change what a closed-loop step launches (kb_set_algorithm, kb_set_control_plus): a captured loop may still be
+// replaying when they are called, and its executable graph is not destroyed under it -- the agent's stream stands behind the last
+// replay (kb_run_resident joins it), so the handle waits for that stream first
+static int kb_retire_graph(kb_handle* k) {
+    if (k->gexec) {
+        HIPCHK(k, hipSetDevice(k->device));
+        HIPCHK(k, hipStreamSynchronize(k->stream));
+    }
+    kb_drop_graph(k);
+    return RS_OK;
+}
+
 extern "C" void kb_destroy(kb_handle* k) {
     if (!k) return;
     if (k->stream) (void)hipStreamSynchronize(k->stream);
@@ -475,6 +490,7 @@ extern "C" void kb_destroy(kb_handle* k) {
     kb_rebuild_release(k);
     kb_bridge_release(k);
     kb_fit_release(k);
+    kb_control_plus_release(k);
     if (k->h_seen) (void)hipHostFree(k->h_seen);
     if (k->h_total) (void)hipHostFree(k->h_total);
     if (k->stream) (void)hipStreamDestroy(k->stream);
@@ -586,6 +602,8 @@ static void launch_shared_gemm(kb_handle* k, const float* d_state) {
     hipLaunchKernelGGL(kb::shared_fgemm_kernel, dim3(S, rts, chunks * (KB_GEMM_KS / 4)), dim3(256), 0, k->stream, k->D, k->K, d_state);
 }
 
+static int launch_control_plus(kb_handle* k, const kb::CtlArgs& a);  // kb_control_plus.hip: the update phase in Projectron++ mode
+
 static int launch_update_control(kb_handle* k, const float* d_state, const int32_t* d_action, const int32_t* d_labels) {
     kb::CtlArgs a;
     a.D = k->D;
@@ -600,6 +618,14 @@ static int launch_update_control(kb_handle* k, const float* d_state, const int32
     const unsigned grid1 = (unsigned)k->T;
     hipEvent_t e1;
     HIPCHK(k, k->spans.begin(k->stream, 0, &e1));
+    if (k->control_plus && k->alg == KB_ALG_PROJECTRON_PLUS) {
+        // kb_set_control_plus: one workgroup per learner runs the step's candidates through the margin rule; no queue, no rounds
+        // (kb_get_repair_work keeps its zeros)
+        const int rc = launch_control_plus(k, a);
+        if (rc != RS_OK) return rc;
+        if (e1) HIPCHK(k, hipEventRecord(e1, k->stream));
+        return RS_OK;
+    }
     if (k->D.heavy_m > 0)
         hipLaunchKernelGGL(kb::update_control_kernel<true>, dim3(grid1), dim3(64), 0, k->stream, a);
     else
@@ -694,9 +720,10 @@ static int launch_select(kb_handle* k, const float* d_state, int32_t* d_action_o
 }
 
 // Projectron++ mode (kb_set_algorithm): the closed control loop does not learn through such a handle -- its update phase is
-// built around Projectron's rule, under which nine learners in ten have nothing to do in a step
+// built around Projectron's rule, under which nine learners in ten have nothing to do in a step -- unless
+// kb_set_control_plus has switched the margin rule's own update phase on (kb_control_plus.hip)
 static int kb_refuse_plus(kb_handle* k, const char* who) {
-    if (k->alg != KB_ALG_PROJECTRON_PLUS) return RS_OK;
+    if (k->alg != KB_ALG_PROJECTRON_PLUS || k->control_plus) return RS_OK;
     k->err = std::string(who) +
              ": the handle is in Projectron++ mode (kb_set_algorithm), which learns through kb_update / kb_fit only -- the control "
              "loop's update phase implements Projectron's rule (kb_set_algorithm(k, KB_ALG_PROJECTRON) switches back; "
@@ -1779,6 +1806,10 @@ extern "C" int kb_set_algorithm(kb_handle* k, int32_t alg) {
                                                                                : "a shared-dictionary handle") +
                  " does not learn through kb_update / kb_fit: Projectron++ has nothing to act on";
         return RS_ESTATE;
+    }
+    if (k->alg != alg) {  // (a captured loop carries the update phase of the algorithm it was captured in)
+        const int rc = kb_retire_graph(k);
+        if (rc != RS_OK) return rc;
     }
     k->alg = alg;
     return RS_OK;

@@ -31,8 +31,11 @@ class KBRL_Control:
         self.adjusted = 0
         # the closed control loop implements Projectron's rule only: no silent training of a ProjectronPlus as a
         # Projectron, and no refusal deep inside update_control
+        # -- unless EVERY learner is a ProjectronPlus that opted in (control_plus): the handle then runs in Projectron++ mode with
+        # kb_set_control_plus on, and update_control applies the margin rule
         plus = [s for s, h in enumerate(learners) if getattr(h.algorithm, 'ALGORITHM', 'projectron') != 'projectron']
-        if plus:
+        control_plus = len(plus) == len(learners) > 0 and all(getattr(h.algorithm, 'control_plus', False) is True for h in learners)
+        if plus and not control_plus:
             raise ValueError('KBRL_Control: learner(s) %s are ProjectronPlus; the closed control loop (update_control, run) '
                              'implements the Projectron rule only.  Supported route: log the control steps, turn them into sample '
                              "lists with ranslice.kbrl_dev.augmented_samples, and VecKBRL.fit them on a handle created with "
@@ -47,7 +50,8 @@ class KBRL_Control:
             expect = idx.stop
         alg0 = learners[0].algorithm
         self._dev = VecKBRL(1, dims, n_prbs, alfa=alfa, accuracy_range=tuple(accuracy_range),
-                            gamma=alg0.kernel.gamma, eta=alg0.eta, capacity=capacity, device=device)
+                            gamma=alg0.kernel.gamma, eta=alg0.eta, capacity=capacity, device=device,
+                            **(dict(algorithm='projectron_plus', control_plus=True) if control_plus else {}))
         self._dev.reset([[int(h.initial_action) for h in learners]], [[int(h.security_factor) for h in learners]],
                         seeds=np.array([seed], dtype=np.uint64))
         for s, h in enumerate(learners):

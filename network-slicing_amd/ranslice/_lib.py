@@ -29,6 +29,7 @@ KB_EXPORTS = (
     'kb_set_fit_wide', 'kb_get_fit_wide', 'kb_fit_wide_info',
     'kb_set_fit_wide_plus', 'kb_get_fit_wide_plus',
     'kb_fit_steps',
+    'kb_set_control_plus', 'kb_get_control_plus',
 )
 
 EXPORTS = (
@@ -223,6 +224,8 @@ def load(dev=None):
     L.kb_set_fit_wide_plus.argtypes = [vp, C.c_int32]
     L.kb_get_fit_wide_plus.argtypes = [vp, ip]
     L.kb_fit_steps.argtypes = [vp, ip, C.c_int32, i64p, fp, ip, ip, C.c_int32, dp, ip, ip, ip, ip]
+    L.kb_set_control_plus.argtypes = [vp, C.c_int32]
+    L.kb_get_control_plus.argtypes = [vp, ip]
     for name in EXPORTS:
         if name not in ('rs_last_error', 'rs_destroy', 'kb_last_error', 'kb_destroy'):
             getattr(L, name).restype = C.c_int

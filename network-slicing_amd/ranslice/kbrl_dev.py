@@ -93,7 +93,8 @@ class VecKBRL:
     by_reference = False   # True on those deploy(index, by_reference=True) returns: dictionaries stored once per distinct agent
 
     def __init__(self, n_envs, dims, n_prbs, alfa=KBRL_ALFA, accuracy_range=(0.99, 0.999), gamma=KBRL_GAMMA,
-                 eta=KBRL_ETA, capacity=4096, device=0, shared=False, first_env=0, pool_bytes=0, algorithm='projectron'):
+                 eta=KBRL_ETA, capacity=4096, device=0, shared=False, first_env=0, pool_bytes=0, algorithm='projectron',
+                 control_plus=False):
         if algorithm not in ALGORITHMS:
             raise ValueError('algorithm must be one of %s, not %r' % (sorted(ALGORITHMS), algorithm))
         self.L = _lib.load()
@@ -114,13 +115,15 @@ class VecKBRL:
         self._check(self.L.kb_create(C.byref(cfg), int(device), C.byref(self.h)))
         if algorithm != 'projectron':
             self.set_algorithm(algorithm)
+        if control_plus:
+            self.set_control_plus(True)
 
     def set_algorithm(self, algorithm):
         """the update rule of the next update() / fit() (kb_set_algorithm): 'projectron' (the default; projectron.py:39-60) or
         'projectron_plus' (Projectron++, projectron.py:71-107: a sample classified correctly inside the margin 0 < y f < 1 gives
         a scaled projection, never a landmark).  A property of this handle, not of its dictionaries: checkpoints and agent files do
         not hold it, fork_from / deploy / load_agents / unshare_from do not carry it over.  While in 'projectron_plus',
-        update_control and the learning resident loop are refused (RS_ESTATE); select_action, score, prune, deploy, export work.
+        update_control and the learning resident loop are refused (RS_ESTATE) unless set_control_plus() is on; select_action, score, prune, deploy, export work.
         Refused (RS_ESTATE) on deployed, by-reference and shared-dictionary handles."""
         if algorithm not in ALGORITHMS:
             raise ValueError('algorithm must be one of %s, not %r' % (sorted(ALGORITHMS), algorithm))
@@ -379,6 +382,23 @@ class VecKBRL:
         """True while set_fit_wide_plus is on (kb_get_fit_wide_plus)"""
         a = C.c_int32()
         self._check(self.L.kb_get_fit_wide_plus(self.h, C.byref(a)))
+        return bool(a.value)
+
+    def set_control_plus(self, on=True):
+        """whether the closed control loop learns in 'projectron_plus' mode (kb_set_control_plus).  Off (the default):
+        update_control, step_resident and run_resident with learning on are refused in that mode.  On: they run, and every learner
+        takes its step's candidates through the margin rule -- per step exactly what fit_steps does with that step's log row in
+        'projectron_plus' mode, bit for bit, behind update_control's bookkeeping (hit, accuracy table, security factor).  One
+        workgroup per learner: late in learning many times the cost of Projectron's loop.  No effect in 'projectron' mode.  A
+        property of this handle: not saved, not carried over by fork_from / deploy / load_agents.  Refused (RS_ESTATE) on
+        deployed, by-reference and shared-dictionary handles."""
+        self._check(self.L.kb_set_control_plus(self.h, int(bool(on))))
+
+    @property
+    def control_plus(self):
+        """True while set_control_plus is on (kb_get_control_plus)"""
+        a = C.c_int32()
+        self._check(self.L.kb_get_control_plus(self.h, C.byref(a)))
         return bool(a.value)
 
     @property
@@ -776,6 +796,10 @@ class SharedVecKBRL(VecKBRL):
     def set_fit_wide(self, min_landmarks, window=0):
         """refused, as kb_set_fit_wide refuses it: a shared-dictionary handle does not learn through fit()"""
         raise _lib.RanSliceError(_lib.RS_ESTATE, 'set_fit_wide: a shared-dictionary handle does not learn through fit')
+
+    def set_control_plus(self, on=True):
+        """refused, as kb_set_control_plus refuses it: a shared-dictionary handle does not learn through update_control"""
+        raise _lib.RanSliceError(_lib.RS_ESTATE, 'set_control_plus: a shared-dictionary handle does not learn through update_control')
 
     def set_fit_wide_plus(self, on=True):
         """refused, as kb_set_fit_wide_plus refuses it: a shared-dictionary handle does not learn through fit()"""

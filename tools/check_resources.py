@@ -37,6 +37,9 @@ FIT_SCRATCH.update({k: 0 for k in ('fit_wide_classify_kernel', 'fit_wide_scan_ke
                                    'fit_wide_matvec_kernel', 'fit_wide_finish_kernel', 'fit_wide_rank1_kernel')})
 # kb_fit_steps (kb_fit_steps.hip): fit_learner's loop around the cached-prefix column, in both update rules: no scratch
 FIT_SCRATCH.update({'fit_steps_kernel': 0, 'fit_steps_plus_kernel': 0})
+# the closed loop's update phase in Projectron++ mode (kb_control_plus.hip): fit_steps_plus_kernel's row behind
+# update_control's bookkeeping: no scratch
+FIT_SCRATCH.update({'control_plus_kernel': 0})
 PRODUCTION = ["embb_step_kernelILi16ELb0ELb0ELb1E", "embb_step_kernelILi16ELb0ELb1ELb1E"]   # <16, false, plain | BLOCK, FDIV>
 PLAIN = PRODUCTION[0]          # the instance bench.py's headline runs
 STEP_KERNEL = 'embb_step_kernelIL'

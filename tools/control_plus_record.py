@@ -1,0 +1,132 @@
+#!/usr/bin/env python3
+"""Measures the closed control loop in Projectron++ mode (kb_set_control_plus) and writes
+profiles/control_plus_record.json.  No threshold is attached to any figure; every figure is ONE run.
+
+--replicas (4096) agents of scenario 0 learn in the resident loop (kb_run_resident, plain launches).  Around each step of --at
+(50, 500, 2000) kernel timing is switched on for --window (10) steps: ms per closed-loop step by phase (kb_phase_times_ms: the
+update phase is control_plus_kernel's one launch in Projectron++ mode), dictionary sizes, samples per step, how many of them
+changed a dictionary and how many ran the mat-vec (kb_get_repair_work's work[6]).  Then the same for Projectron on the same
+build, unchanged code, for scale.  The slowest learner's share of a Projectron++ step: the update phase is one launch of one
+workgroup per learner, so with kernel timing on the agents are stepped once more on a handle of ONE replica that holds a copy of
+the replica with the largest dictionary -- its update phase is that replica's workgroups alone.
+
+  python tools/control_plus_record.py [--replicas 4096] [--at 50 500 2000] [--window 10] [--out profiles/control_plus_record.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, 'network-slicing_amd'), os.path.join(ROOT, 'tools')):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def _kernel_resources():
+    import check_resources as cr
+    if not os.path.exists(cr.LOG):
+        return None
+    res = cr.parse()
+    hit = [k for k in res if 'control_plus_kernel' in k]
+    if not hit:
+        return None
+    r = res[hit[0]]
+    return dict(vgprs=r.get('VGPRs'), sgprs_spilled=r.get('SGPRs Spill'), scratch_bytes_per_lane=r.get('ScratchSize'),
+                occupancy=r.get('Occupancy'), lds_bytes=r.get('LDS Size'))
+
+
+def _leg(mode, n, at, window, capacity, pool_bytes, seed):
+    import ctypes as C
+    import numpy as np
+    from ranslice.config import make_config
+    from ranslice.kbrl_dev import VecKBRL
+    from ranslice.vec_env import VecRanSlice, default_fading
+    cfg = make_config(0, n_envs=n)
+    dims, n_prbs = [10] * cfg.n_embb + [3] * cfg.n_mmtc, cfg.n_prbs
+    env = VecRanSlice(n_envs=n, cfg=cfg, fading=default_fading(), seed=seed)
+    ag = VecKBRL(n, dims, n_prbs, capacity=capacity, pool_bytes=pool_bytes, algorithm=mode, control_plus=mode == 'projectron_plus')
+    ia = np.full((n, len(dims)), n_prbs // (2 * len(dims)), dtype=np.int32)
+    env.reset()
+    ag.reset(ia, np.full((n, len(dims)), 3, dtype=np.int32))
+    env._check(env.L.rs_step(env.h, ia.ctypes.data_as(C.POINTER(C.c_int32)), None, None, None, None))
+    out, step = [], 0
+    for a in at:
+        first = max(step, a - window // 2)
+        t0 = time.perf_counter()
+        if first > step:
+            ag.run_resident(env, first - step, graph=False)
+        ag.synchronize()
+        between = time.perf_counter() - t0
+        step = first
+        s0, w0 = ag.stats(), ag._repair_raw()
+        ag.set_kernel_timing(True)
+        ag.phase_times_ms()
+        t0 = time.perf_counter()
+        ag.run_resident(env, window, graph=False)
+        ag.synchronize()
+        wall = time.perf_counter() - t0
+        ph = ag.phase_times_ms()
+        ag.set_kernel_timing(False)
+        step += window
+        s1, w1 = ag.stats(), ag._repair_raw()
+        sizes = ag.dictionary_sizes()
+        rec = dict(steps=[first, step], update_ms_per_step=ph['update_ms'], select_ms_per_step=ph['select_ms'],
+                   wall_ms_per_step=wall * 1e3 / window, wall_s_since_the_last_window=between,
+                   landmarks_mean=float(sizes.mean()), landmarks_max=int(sizes.max()),
+                   changed_a_dictionary_per_step=(s1[1] - s0[1]) / window, insertions_per_step=(s1[2] - s0[2]) / window)
+        if mode == 'projectron_plus':
+            # (predictions_per_step: the update phase's samples plus select_action's predictions, as the counter holds them)
+            rec['matvec_samples_per_step'] = (int(w1[6]) - int(w0[6])) / window
+            rec['predictions_per_step'] = (s1[0] - s0[0]) / window
+            worst = int(np.argmax(sizes.max(axis=1)))
+            one = VecKBRL(1, dims, n_prbs, capacity=capacity, pool_bytes=1 << 30, algorithm=mode, control_plus=True)
+            one.fork_from(ag, [worst])
+            oenv = VecRanSlice(n_envs=1, cfg=make_config(0, n_envs=1), fading=default_fading(), seed=seed)
+            oenv.reset()
+            oenv.fork_from(env, [worst])
+            one.set_kernel_timing(True)
+            one.phase_times_ms()
+            one.run_resident(oenv, window, graph=False)
+            one.synchronize()
+            rec['largest_replica_alone'] = dict(replica=worst, landmarks=sizes[worst].tolist(),
+                                                update_ms_per_step=one.phase_times_ms()['update_ms'])
+            rec['largest_replica_share_of_the_update_phase'] = (rec['largest_replica_alone']['update_ms_per_step'] / ph['update_ms']
+                                                                if ph['update_ms'] else None)
+            one.close()
+            oenv.close()
+        else:
+            rec['predictions_per_step'] = (s1[0] - s0[0]) / window
+        out.append(rec)
+        print(mode, json.dumps(rec), flush=True)
+    flags = ag.flagged_replicas()
+    env.close()
+    ag.close()
+    return dict(windows=out, flagged=sum(len(v) for v in flags.values()))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--replicas', type=int, default=4096)
+    ap.add_argument('--at', type=int, nargs='*', default=[50, 500, 2000])
+    ap.add_argument('--window', type=int, default=10)
+    ap.add_argument('--capacity', type=int, default=2048)
+    ap.add_argument('--pool-gb', type=float, default=48.0)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'control_plus_record.json'))
+    args = ap.parse_args()
+    rec = dict(what='closed control loop, scenario 0, %d replicas on one device: Projectron++ behind kb_set_control_plus, and '
+                    'Projectron on the same build for scale; one run per figure, no threshold attached' % args.replicas,
+               replicas=args.replicas, window=args.window, kernel=_kernel_resources())
+    for mode in ('projectron_plus', 'projectron'):
+        rec[mode] = _leg(mode, args.replicas, sorted(args.at), args.window, args.capacity, int(args.pool_gb * (1 << 30)), args.seed)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, 'w') as fh:
+        json.dump(rec, fh, indent=1, sort_keys=True)
+        fh.write('\n')
+    print(json.dumps(rec, indent=1, sort_keys=True))
+
+
+if __name__ == '__main__':
+    main()
