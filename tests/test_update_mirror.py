@@ -5,6 +5,10 @@ device test that compares bits with the mirror would pass whatever the kernel di
 Dictionaries come from an OracleKBRL learner on _fast_growing_samples (tests/test_gpu_kbrl.py); at every size of SIZES the next
 sample of the stream that is projected and the one that is inserted are taken through update_mirror.step from the ORACLE's state
 before the step.  Run with -s for the largest error / bound ratios (DESIGN.md §2 quotes them).
+
+Below them the same for ONE ProjectronPlus.update (update_mirror.step_plus): it replays the reference's recording G18 walking
+alone, keeps its derived bounds against exact arithmetic (exact_plus, plus_bounds) on every margin sample of those replays, and
+its contrast switches show on the inputs tests/test_gpu_plus_chain.py uses (DESIGN.md §8i quotes the ratios).
 """
 import numpy as np
 import pytest
@@ -177,3 +181,174 @@ def test_a_wrong_order_shows_in_the_partials():
     assert not same_bits(ds, ds4) and any(not same_bits(dp[t], dp4[t]) for t in dp)
     assert not same_bits(ds, dsr) and all(same_bits(dp[t], dpr[t]) for t in dp) and all(same_bits(tp[t], tpr[t]) for t in tp)
     assert um.error_ratio(ds4, K, kf)[0] <= 1.0     # (wrong order, still accurate: only the bits can tell)
+
+
+# ------------------------------------------------------------------ Projectron++: step_plus
+def _tag(golden_dir, tag):
+    import os
+    g = np.load(os.path.join(golden_dir, 'g18_projectron_plus.npz'))
+    return {k[len(tag) + 1:]: g[k] for k in g.files if k.startswith(tag + '_')}
+
+
+def _close(a, b, rtol, atol, what):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    bad = np.abs(a - b) > np.maximum(rtol * np.abs(b), atol)
+    assert not bad.any(), (what, np.nonzero(bad)[0][:5], a[bad][:5], b[bad][:5])
+
+
+@pytest.fixture(scope='module', params=['d4', 'rev'])
+def walked(request, golden_dir):
+    """step_plus from the empty dictionary through all 1,200 samples of G18's d4 stream, and through samples 0 .. 440 of its rev
+    stream (past 64 -> 65 landmarks), fed nothing but its own state -> (tag, recording, [(state before, stages)])"""
+    g = _tag(golden_dir, request.param)
+    n = 1200 if request.param == 'd4' else 441
+    state = (np.zeros((0, 0)), np.zeros(0), np.zeros((0, g['x'].shape[1])))
+    steps = []
+    for i in range(n):
+        r = um.step_plus(*state, g['x'][i], int(g['y'][i]), GAMMA, ETA)
+        r['y'] = int(g['y'][i])
+        steps.append((state, r))
+        state = (r['kinv'], r['coeff'], r['landmarks'])
+    return request.param, g, steps
+
+
+def test_step_plus_replays_the_recording_walking_alone(walked):
+    """every branch and size equals the recording; f, delta and the final coefficients within the tolerances
+    tests/test_gpu_projectron_plus.py holds the device to (f 1e-8 / 1e-9, delta 1e-7 / 1e-9; coefficients 1e-8 / 1e-9 on d4, with
+    the vector after each of its 147 margin updates and the final Kinv, and 1e-7 / 1e-8 on rev -- there against the float64
+    restatement tests/plus_mirror.py on the same prefix, which tests/test_plus_mirror.py holds to the whole recording)"""
+    import plus_mirror as pm
+    tag, g, steps = walked
+    n = len(steps)
+    br = np.array([r['branch'] for _, r in steps])
+    assert np.array_equal(br, g['branch'][:n]), np.nonzero(br != g['branch'][:n])[0][:5]
+    assert np.array_equal([r['m'] for _, r in steps], g['m'][:n])
+    _close([r['f'] for _, r in steps], g['f'][:n], 1e-8, 1e-9, tag + ' f')
+    upd = br != 0
+    _close(np.array([r['delta'] for _, r in steps])[upd], g['delta'][:n][upd], 1e-7, 1e-9, tag + ' delta')
+    assert not np.array([r['delta'] for _, r in steps])[~upd].any()
+    margin = br >= 3
+    _close(np.array([r['slack'] for _, r in steps])[margin], g['slack'][:n][margin], 1e-7 / ETA, 1e-9 / ETA, tag + ' slack')
+    last = steps[-1][1]
+    if tag == 'd4':
+        assert np.array_equal(last['landmarks'], g['landmarks'])
+        np.testing.assert_allclose(last['coeff'], g['coeff'], rtol=1e-8, atol=1e-9)
+        np.testing.assert_allclose(last['kinv'], g['kinv'], rtol=1e-8, atol=1e-8 * np.abs(g['kinv']).max())
+        after = [r['coeff'] for _, r in steps if r['branch'] == 3]
+        assert len(after) == len(g['coeff_after']) == 147
+        for c, ref in zip(after, g['coeff_after']):
+            np.testing.assert_allclose(c, ref[:len(c)], rtol=1e-8, atol=1e-9)
+        assert any(r['branch'] >= 3 and len(b[1]) == 1 for b, r in steps)       # the float32 regime meets the margin rule
+    else:
+        mir, _ = pm.replay(g['x'][:n], g['y'][:n], g['ties'], eta=ETA, gamma=GAMMA)
+        assert last['m'] == mir.m == g['m'][n - 1] > 65 and np.array_equal(last['landmarks'], mir.L)
+        np.testing.assert_allclose(last['coeff'], mir.c, rtol=1e-7, atol=1e-8)
+        assert np.bincount(br[338:438], minlength=5).tolist() == [21, 4, 13, 8, 54] and g['m'][337] < 64 < 65 < g['m'][437] == 74
+
+
+def test_step_plus_keeps_its_bounds_against_exact_arithmetic(walked):
+    """on every margin sample of the replays: f and the new coefficients within plus_bounds of exact_plus on the same doubles (d*
+    within bound_units); where the exact margin and slack are clear of their thresholds by more than the bound the branch is the
+    exact one, and where the exact terms of alpha are clear of each other the winning term is"""
+    tag, g, steps = walked
+    worst, seen = dict(f=0.0, coeff=0.0, dstar=0.0), dict(branch=0, won=0, margin=0)
+    for (Kinv, c, L), r in steps:
+        if r['branch'] < 3:
+            continue
+        m, y = len(c), r['y']
+        ex = um.exact_plus(Kinv, r['column'], c, y, ETA)
+        bd = um.plus_bounds(ex, m, ETA)
+        rt = um.plus_ratios(dict(f=r['f'], coeff=r['coeff'] if r['branch'] == 3 else None), ex, bd)
+        assert all(v <= 1.0 for v in rt.values()), (tag, m, r['branch'], rt)
+        for k, v in rt.items():
+            worst[k] = max(worst[k], v)
+        if m >= 2:
+            rd, _ = um.error_ratio(r['dstar'], Kinv, r['column'])
+            assert rd <= 1.0, (tag, m, rd)
+            worst['dstar'] = max(worst['dstar'], rd)
+        seen['margin'] += 1
+        if min(float(ex['margin']), 1.0 - float(ex['margin'])) > bd['f'] and abs(float(ex['slack'])) > bd['slack']:
+            assert r['branch'] == ex['branch'], (tag, m, r['branch'], ex['branch'], float(ex['slack']), bd['slack'])
+            seen['branch'] += 1
+            if r['branch'] == 3 and bd['won_clear']:
+                assert r['won'] == ex['won'], (tag, m, r['won'], ex['won'], ex['terms'])
+                seen['won'] += 1
+    print('%s: margin samples %d, branch decided clear of the bound %d, winning term %d; largest error / bound: f %.3g, d* %.3g, '
+          'coefficients %.3g' % (tag, seen['margin'], seen['branch'], seen['won'], worst['f'], worst['dstar'], worst['coeff']))
+    assert seen['branch'] > 0.9 * seen['margin'] and seen['won'] > 0
+
+
+@pytest.fixture(scope='module')
+def plus_inputs():
+    """the inputs of tests/test_gpu_plus_chain.py, built without a device: dictionaries of the ladder's sizes grown in Projectron
+    mode by the float64 restatement (tests/plus_mirror.py) on the two streams, one sample per case of the margin rule from
+    update_mirror.PlusInputs, and the hand-built single-landmark points -> [(name, m, case or point, state, x, y)]"""
+    import plus_mirror as pm
+    from test_gpu_update_chain import _stream3
+    out = []
+    for name, (xs, ys), sizes in (('dims 10', _fast_growing_samples(4600), um.PLUS_LADDER10), ('dims 3', _stream3(3000), um.PLUS_LADDER3)):
+        mir, i = pm.PlusMirror(gamma=GAMMA, eta=ETA, plus=False), 0
+        for m in sizes:
+            while mir.m < m:
+                mir.predict(xs[i])
+                mir.update(xs[i], int(ys[i]))
+                i += 1
+            assert mir.m == m
+            state = (mir.P.copy(), mir.c.copy(), mir.L.copy())
+            inp = um.PlusInputs(state[0], state[2], GAMMA, ETA, 200)
+            found = []
+            for case in um.CASES:      # one after the other on the same learner, as the device test takes them
+                p = inp.pick(state[1], case)
+                if p is not None:
+                    found.append(case)
+                    out.append((name, m, case, state, p[0], p[1]))
+                    state = (state[0], um.step_plus(*state, p[0], p[1], GAMMA, ETA)['coeff'], state[2])
+            assert set(um.cases_required(m)) <= set(found), (name, m, found, inp.counts(state[1]))
+    b = um.one_landmark_inputs(GAMMA, ETA)
+    x0 = b['x0']
+    for point, near, x in b['points']:
+        assert x is not None, point
+        st = um.step_plus(np.ones((1, 1)), [1.0], x0[None], near, -1, GAMMA, ETA)
+        out.append(('one landmark', 1, point, (st['kinv'], st['coeff'], st['landmarks']), x, 1))
+    out.append(('one landmark', 1, 'x0', (np.ones((1, 1)), np.ones(1), x0[None]), x0, 1))
+    return out
+
+
+def test_the_mirror_names_the_case_the_float64_preselection_chose(plus_inputs):
+    """the clearance of 1e-6 is far above the rounding of either: step_plus's branch and winning term are the wanted case; the
+    single-landmark points meet all five cases, and both exact ties"""
+    met = set()
+    for name, m, case, state, x, y in plus_inputs:
+        r = um.step_plus(*state, x, y, GAMMA, ETA)
+        got = {0: 'branch0', 4: 'branch4', 3: r['won']}.get(r['branch'])
+        if name == 'one landmark':
+            met.add(got)
+            if case == 'x0':
+                assert r['margin'] == 1.0 and r['branch'] == 0
+            if case == 'tie_alpha':
+                assert r['terms'][0] == 1.0 and r['won'] == 'loss' and r['alpha'] == 1.0
+            if case == 'tie_slack':
+                assert r['slack'] == 0.0 and r['branch'] == 4
+            if case not in ('x0', 'tie_slack'):
+                assert 0 < r['coeff'][0] and r['coeff'][0] == np.float32(r['coeff'][0]) and r['loss'] == np.float32(r['loss'])
+        else:
+            assert got == case, (name, m, case, got)
+    assert met == set(um.CASES), met
+
+
+def test_inputs_show_every_contrast_switch_of_the_margin_rule(plus_inputs):
+    """each deliberately wrong form of the rule changes at least one output (f, branch, winning term, delta or a coefficient, as
+    bits) on these inputs -- a device test that compares them with step_plus on the same inputs would see such a fault.  What
+    each can show at all: loss64 only while one landmark is held; alpha_order only the name of the winner on an exact tie of two
+    terms (the minimum itself does not depend on the order) and slack_ge only slack == 0.0 exactly -- the two hand-built ties;
+    fused_coeff and f_pairwise on the larger dictionaries."""
+    shows = {k: 0 for k in um.PLUS_SWITCHES}
+    view = lambda r: (np.float64(r['f']).tobytes(), r['branch'], r['won'], np.float64(r['delta']).tobytes(), r['coeff'].tobytes())
+    for name, m, case, state, x, y in plus_inputs:
+        base = view(um.step_plus(*state, x, y, GAMMA, ETA))
+        for k in um.PLUS_SWITCHES:
+            if (k == 'loss64') != (m == 1) and k not in ('alpha_order', 'slack_ge'):
+                continue      # (loss64 is the m == 1 statement; the sums' switches cannot show on one landmark)
+            shows[k] += view(um.step_plus(*state, x, y, GAMMA, ETA, **{k: True})) != base
+    print('inputs on which each switch shows: %s of %d' % (shows, len(plus_inputs)))
+    assert all(v > 0 for v in shows.values()), shows
