@@ -16,6 +16,14 @@
 //                      its -1) and, optionally, the 128 partial sums of every stored tile of the first ceil(min(m, max_m) / 64)
 //                      shells, tile (b_i, b_j) at 128 (b_i (b_i + 1) / 2 + b_j): dpart, then tpart (matvec_tri_tiles); a tile the
 //                      last mat-vec did not cover holds whatever it held before (tests/test_gpu_update_chain.py)
+//   kb_dev_get_shared_scores  shared handles: K.workF [S][KB_GEMM_KS][n_envs][256], the partial scores F = E Q of the eight parts
+//                      of the landmarks, and K.workE [S][KB_GEMM_KS][n_envs], the largest E_j every replica met in each part, as
+//                      the last kb_shared_scan / kb_select_action left them (shared_fgemm_kernel; a slice it did not score
+//                      holds whatever it held before) (tests/test_gpu_shared_chain.py)
+//   kb_dev_get_shared_apply  shared handles: the work areas of slice s as the last kb_shared_apply left them, laid out by
+//                      the `budget` THAT call was given: KF and DS [budget][capr] (kernel columns and d* = Kinv k_f of the list,
+//                      capr = the capacity rounded up to 64), A [budget][budget] the proposals' Gram block stored by column
+//                      (A[q * budget + p] = k_p . d*_q, tiles tj <= ti only) and F0 [budget]
 // By-reference handles (kb_ref.hip) answer the first two: their scores are per task as everywhere (they keep no W: zeros), their rows are
 // those of the store's dictionary the map names for (e, s) -- which no selection may ever have changed.
 //
@@ -160,6 +168,37 @@ extern "C" int kb_dev_get_update_rows(kb_handle* k, int e, int s, int32_t max_m,
             HIPCHK(k, hipMemcpy(parts + (size_t)128 * ((size_t)b * (b + 1) / 2), page + KB_VEC + (size_t)(b + 1) * KB_TILE,
                                 sizeof(double) * 128 * (size_t)(b + 1), hipMemcpyDeviceToHost));
     }
+    return RS_OK;
+}
+
+extern "C" int kb_dev_get_shared_scores(kb_handle* k, double* F_parts, double* E_parts) {
+    if (!k) return RS_EINVAL;
+    if (!k->D.shared) {
+        k->err = "kb_dev_get_shared_scores: shared-dictionary handles only (kb_dev_get_scores answers the others)";
+        return RS_ESTATE;
+    }
+    HIPCHK(k, hipSetDevice(k->device));
+    HIPCHK(k, hipStreamSynchronize(k->stream));
+    const size_t n = (size_t)k->cfg.n_slices * KB_GEMM_KS * (size_t)k->cfg.n_envs;
+    if (F_parts) HIPCHK(k, hipMemcpy(F_parts, k->K.workF, sizeof(double) * n * 256, hipMemcpyDeviceToHost));
+    if (E_parts) HIPCHK(k, hipMemcpy(E_parts, k->K.workE, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return RS_OK;
+}
+
+extern "C" int kb_dev_get_shared_apply(kb_handle* k, int s, int32_t budget, double* KF, double* DS, double* A, double* F0) {
+    if (!k || s < 0 || s >= k->cfg.n_slices || budget <= 0 || budget > k->budget_cap) return RS_EINVAL;
+    if (!k->D.shared) {
+        k->err = "kb_dev_get_shared_apply: shared-dictionary handles only";
+        return RS_ESTATE;
+    }
+    HIPCHK(k, hipSetDevice(k->device));
+    HIPCHK(k, hipStreamSynchronize(k->stream));
+    const size_t capr = (size_t)kb::kb_capr(k->cfg.capacity), b = (size_t)budget;
+    const double* kf = k->K.workb + (size_t)s * 2 * b * capr;  // (the offsets of shared_cols_kernel / shared_gram_kernel)
+    if (KF) HIPCHK(k, hipMemcpy(KF, kf, sizeof(double) * b * capr, hipMemcpyDeviceToHost));
+    if (DS) HIPCHK(k, hipMemcpy(DS, kf + b * capr, sizeof(double) * b * capr, hipMemcpyDeviceToHost));
+    if (A) HIPCHK(k, hipMemcpy(A, k->K.workg + (size_t)s * b * b, sizeof(double) * b * b, hipMemcpyDeviceToHost));
+    if (F0) HIPCHK(k, hipMemcpy(F0, k->K.workf + (size_t)s * b, sizeof(double) * b, hipMemcpyDeviceToHost));
     return RS_OK;
 }
 

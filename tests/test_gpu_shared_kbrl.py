@@ -1,7 +1,9 @@
-"""Shared-dictionary KBRL (build-defined extension: no counterpart in the reference, parity unpinned).
-Pinned by self-consistency, as SURVEY.md §8e asks: (1) with one replica it is the reference's sequential
-algorithm (equals the per-replica agent, which is pinned to the reference's goldens); (2) the learned
-dictionaries do not depend on how replicas are sharded over ranks."""
+"""Shared-dictionary KBRL (build-defined extension: no counterpart in the reference).  Here: its self-consistency, as
+SURVEY.md §8e asks: (1) with one replica it is the reference's sequential algorithm (equals the per-replica
+agent, which is pinned to the reference's goldens); (2) the learned dictionaries do not depend on how replicas
+are sharded over ranks.  Its arithmetic and its rounds with several replicas are held to an independent
+reference stage by stage in tests/test_gpu_shared_chain.py (tests/shared_mirror.py, exact arithmetic, the
+sequential oracle)."""
 import os
 
 import numpy as np

@@ -182,7 +182,9 @@ def dot(a, b):
 
 def step(Kinv, coeff, landmarks, x, y, gamma=1.0, eta=0.1, capacity=None, **order):
     """one Projectron.update of a sample the learner misclassified -> dict(column, dstar, dpart, tpart, dot, delta, branch,
-    m, coeff, kinv): the state after the step, every stage in the device's order (`order`: dstar_tri's contrasting switches)"""
+    m, coeff, kinv): the state after the step, every stage in the device's order (`order`: dstar_tri's contrasting switches;
+    order='col': d* by dstar_col, the column walk of the handles that store both triangles -- the shared ones)"""
+    col = order.pop('order', 'tri') == 'col'
     x = np.asarray(x, dtype=np.float64)
     m = len(coeff)
     d = len(x)
@@ -196,6 +198,9 @@ def step(Kinv, coeff, landmarks, x, y, gamma=1.0, eta=0.1, capacity=None, **orde
     elif m == 1:
         ds = np.array([float(np.float32(1.0) * np.float32(kf[0]))])
         dt = float(np.float32(ds[0]) * np.float32(kf[0]))
+    elif col:
+        ds = dstar_col(Kinv, kf)
+        dt = dot(ds, kf)
     else:
         ds, dpart, tpart = dstar_tri(Kinv, kf, **order)
         dt = dot(ds, kf)
