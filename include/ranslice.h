@@ -800,9 +800,37 @@ int kb_fit_steps(kb_handle* k, const int32_t* agent, int32_t n, const int64_t* f
  * files, not carried over by kb_fork, kb_deploy, kb_import_agents, kb_share or kb_unshare.  RS_EINVAL for any value but 0 and 1;
  * RS_ESTATE on an inference-only, a by-reference or a shared-dictionary handle.
  * Cost: late in learning many times Projectron's loop -- one workgroup walks Kinv once per candidate inside the margin
- * (batching those mat-vecs is not built). */
+ * (kb_set_control_plus_batch, below, forms the d* of several candidates in one walk). */
 int kb_set_control_plus(kb_handle* k, int32_t on);
 int kb_get_control_plus(kb_handle* k, int32_t* on);
+
+/* ---- one pass over Kinv for a group of candidates (csrc/kb_control_plus_batch.hip).
+ * kb_set_control_plus_batch(k, width, max_landmarks): width = 0 (the default): the update phase of kb_set_control_plus as above,
+ * every kernel, launch and bit.  width = 2, 4 or 8: while the handle is in Projectron++ mode AND kb_set_control_plus is on,
+ * kb_update_control, kb_step_resident and kb_run_resident (plain and captured) launch control_plus_batch_kernel instead: the same
+ * row, but the d* = Kinv K_f of the next `width` candidates are formed together from ONE read of the stored triangle -- they
+ * depend on the landmarks and Kinv alone, which only an insertion changes -- and the walk goes on in order with the coefficients
+ * as they are; a group nobody of which lies inside the margin (y f >= 1 for all) makes no pass; an insertion ends its group behind
+ * itself.  Every sum keeps the one-by-one walk's order: landmarks, coefficients, all of Kinv, the control state, the statistics
+ * and kb_get_repair_work are BIT FOR BIT those of width 0.  max_landmarks: a multiple of 64, at least 64 and at most the handle's
+ * capacity (ignored when width is 0): the largest dictionary whose candidates are grouped; a larger one, and one of fewer than two
+ * landmarks (the float32 regime), takes its candidates one by one inside the same kernel.
+ * Scratch: all of it is allocated by this call (the first launch may be inside a stream capture), freed when the width returns
+ * to 0 and at kb_destroy, and bounded whatever the fleet -- at most 1024 workgroups per launch take the learners from a ticket,
+ * each with an arena for its group's K_f and d* columns:
+ *     scratch_bytes = 128 + min(n_envs * n_slices, 1024) * 2 * width * max_landmarks * 8        (0 while the width is 0)
+ * A change of either value waits for the agent's stream and drops a captured loop, as kb_set_control_plus does.  Host state of the
+ * handle like that switch: not part of kb_save_state blobs or agent files, carried over by no transfer call.  (Blobs saved under
+ * different widths may differ in the K_f / d* rows and the tiles' partial-sum slots: scratch every reader rewrites first.)
+ * RS_EINVAL for any other width or max_landmarks (the message names the accepted values); RS_ESTATE on an inference-only, a
+ * by-reference or a shared-dictionary handle.
+ * kb_control_plus_batch_info: work[8] since the switch was last set (zeros while the width is 0): [0] groups formed, [1] groups
+ * skipped (nobody inside the margin), [2] passes over Kinv, [3] tiles those passes read (n_b (n_b + 1) / 2 per pass, n_b =
+ * ceil(m / 64)), [4] d* columns formed, [5] columns discarded behind an insertion, [6] candidates that went one by one, [7] of
+ * those, the ones that ran the mat-vec (branches 1-4). */
+int kb_set_control_plus_batch(kb_handle* k, int32_t width, int32_t max_landmarks);
+int kb_get_control_plus_batch(kb_handle* k, int32_t* width, int32_t* max_landmarks, uint64_t* scratch_bytes);
+int kb_control_plus_batch_info(kb_handle* k, uint64_t work[8]);
 
 #ifdef __cplusplus
 }

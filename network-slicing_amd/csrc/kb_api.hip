@@ -76,6 +76,9 @@ struct kb_handle {
     int32_t fit_wide_plus = 0;                      // kb_set_fit_wide_plus: 1 = the rounds also teach in Projectron++ mode; host state as well
     int32_t control_plus = 0;                       // kb_set_control_plus: 1 = the closed control loop learns in Projectron++ mode; host state as well (kb_control_plus.hip)
     unsigned long long* d_ctl_work = nullptr;       // [4] control_plus_kernel's counters (allocated when the switch is first set)
+    int32_t cpb_width = 0, cpb_max = 0;             // kb_set_control_plus_batch: candidates per pass over Kinv (0: one by one) and the largest dictionary grouped; host state as well (kb_control_plus_batch.hip)
+    char* d_cpb = nullptr;                          // its scratch: work[8], the ticket, the workgroups' arenas (allocated by the setter, freed at width 0)
+    uint64_t cpb_bytes = 0;
     // kb_fork / kb_deploy into this handle (kb_fork.hip)
     hipEvent_t ev_fork_in = nullptr, ev_fork_out = nullptr;
     int32_t* d_fork_idx = nullptr;   // [n_envs] source agent of every agent
@@ -104,6 +107,7 @@ static void kb_rebuild_release(kb_handle* k);  // kb_rebuild.hip
 static void kb_bridge_release(kb_handle* k);   // kb_bridge.hip
 static void kb_fit_release(kb_handle* k);      // kb_fit.hip
 static void kb_control_plus_release(kb_handle* k);  // kb_control_plus.hip
+static void kb_control_plus_batch_release(kb_handle* k);  // kb_control_plus_batch.hip
 static kb_handle* kb_ref_store(kb_handle* k);
 static int kb_ref_dict(kb_handle* k, size_t task);
 static int kb_ref_select(kb_handle* k, const float* d_state);  // the scoring of launch_select: one fused kernel
@@ -491,6 +495,7 @@ extern "C" void kb_destroy(kb_handle* k) {
     kb_bridge_release(k);
     kb_fit_release(k);
     kb_control_plus_release(k);
+    kb_control_plus_batch_release(k);
     if (k->h_seen) (void)hipHostFree(k->h_seen);
     if (k->h_total) (void)hipHostFree(k->h_total);
     if (k->stream) (void)hipStreamDestroy(k->stream);
@@ -603,6 +608,7 @@ static void launch_shared_gemm(kb_handle* k, const float* d_state) {
 }
 
 static int launch_control_plus(kb_handle* k, const kb::CtlArgs& a);  // kb_control_plus.hip: the update phase in Projectron++ mode
+static int launch_control_plus_batch(kb_handle* k, const kb::CtlArgs& a);  // kb_control_plus_batch.hip: the same, a group of candidates per pass over Kinv
 
 static int launch_update_control(kb_handle* k, const float* d_state, const int32_t* d_action, const int32_t* d_labels) {
     kb::CtlArgs a;
@@ -621,7 +627,8 @@ static int launch_update_control(kb_handle* k, const float* d_state, const int32
     if (k->control_plus && k->alg == KB_ALG_PROJECTRON_PLUS) {
         // kb_set_control_plus: one workgroup per learner runs the step's candidates through the margin rule; no queue, no rounds
         // (kb_get_repair_work keeps its zeros)
-        const int rc = launch_control_plus(k, a);
+        // (kb_set_control_plus_batch: the same row, `width` candidates per pass over Kinv)
+        const int rc = k->cpb_width > 0 ? launch_control_plus_batch(k, a) : launch_control_plus(k, a);
         if (rc != RS_OK) return rc;
         if (e1) HIPCHK(k, hipEventRecord(e1, k->stream));
         return RS_OK;

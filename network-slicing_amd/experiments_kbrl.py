@@ -62,13 +62,19 @@ class BatchedEvaluator(Evaluator):
     dictionary above T landmarks is pruned back to T (VecKBRL.prune); the result files then carry one extra
     key, `pruned`: the landmarks removed from the run's dictionaries in all.  The defaults leave everything as it was.
     algorithm='projectron_plus': the agents learn by ProjectronPlus's margin rule in the closed loop (VecKBRL(...,
-    algorithm='projectron_plus', control_plus=True)) -- no reference-shaped serial counterpart is run beside it."""
+    algorithm='projectron_plus', control_plus=True)) -- no reference-shaped serial counterpart is run beside it.
+    control_plus_batch = 2, 4 or 8 (with 'projectron_plus' only): that many candidates of a step share one pass over Kinv
+    (VecKBRL.set_control_plus_batch); the results are those of 0, bit for bit."""
 
-    def __init__(self, scenario, a_range, steps=STEPS, out_dir='./results', prune_to=None, prune_every=None, algorithm='projectron'):
+    def __init__(self, scenario, a_range, steps=STEPS, out_dir='./results', prune_to=None, prune_every=None, algorithm='projectron',
+                 control_plus_batch=0):
         super().__init__(scenario, a_range, steps=steps, out_dir=out_dir)
         if algorithm not in ('projectron', 'projectron_plus'):
             raise ValueError("algorithm must be 'projectron' or 'projectron_plus', not %r" % (algorithm,))
         self.algorithm = algorithm
+        if control_plus_batch and algorithm != 'projectron_plus':
+            raise ValueError("control_plus_batch groups the candidates of the 'projectron_plus' update phase: it needs that algorithm")
+        self.control_plus_batch = int(control_plus_batch)
         if (prune_to is None) != (not prune_every):
             raise ValueError('prune_to and prune_every go together')
         self.prune_to, self.prune_every = prune_to, prune_every
@@ -106,7 +112,8 @@ class BatchedEvaluator(Evaluator):
         dims = [len(sc.state_variables_embb)] * n_embb + [len(sc.state_variables_mmtc)] * n_mmtc
         agent = VecKBRL(n, dims, n_prbs, alfa=sc.alfa, accuracy_range=tuple(self.a_range), capacity=capacity,
                         device=device, pool_bytes=pool_bytes,
-                        **(dict(algorithm=self.algorithm, control_plus=True) if self.algorithm != 'projectron' else {}))
+                        **(dict(algorithm=self.algorithm, control_plus=True, control_plus_batch=self.control_plus_batch)
+                           if self.algorithm != 'projectron' else {}))
         env.reset(seeds=env_seeds)
         agent.reset(ia, sf, seeds=ag_seeds)
         agent.history_begin(self.steps)
@@ -253,7 +260,7 @@ class BatchedEvaluator(Evaluator):
 
 
 def evaluate_grid(cells, runs, steps=STEPS, out_dir='./results', device=0, capacity=16384, pool_bytes=16 << 30, verbose=False,
-                  graph=False, prune_to=None, prune_every=None, algorithm='projectron'):
+                  graph=False, prune_to=None, prune_every=None, algorithm='projectron', control_plus_batch=0):
     """The reference's whole experiment (experiments_kbrl.py:57-70: every scenario x accuracy range x run) as ONE job on
     one GPU: a BatchedEvaluator per cell, each with its environment and agents on streams of their own, all advanced in
     the same host loop -- a cell of 30 runs leaves most of the chip idle (a handful of waves per kernel), so the cells'
@@ -261,11 +268,12 @@ def evaluate_grid(cells, runs, steps=STEPS, out_dir='./results', device=0, capac
     handles do not overlap on this runtime -- 22.4 s per 6,000 steps of the six cells against 16.1 s with plain launches,
     profiles/r04_w_grid_graph.txt -- while a single cell gains 5 % from the graph.)  Returns {(scenario, a_lo): [files]}, file
     for file what evaluate_all writes cell by cell (tests/test_gpu_kbrl.py::test_grid_of_cells_equals_cell_by_cell).
-    prune_to / prune_every: budgeted dictionaries in every cell (BatchedEvaluator); algorithm: its update rule."""
+    prune_to / prune_every: budgeted dictionaries in every cell (BatchedEvaluator); algorithm, control_plus_batch: its update rule
+    and how many candidates share a pass over Kinv."""
     evs = []
     for scenario, a_range in cells:
         ev = BatchedEvaluator(scenario, a_range, steps=steps, out_dir=out_dir, prune_to=prune_to, prune_every=prune_every,
-                              algorithm=algorithm)
+                              algorithm=algorithm, control_plus_batch=control_plus_batch)
         ev._setup(runs, device=device, capacity=capacity, pool_bytes=pool_bytes)
         evs.append(ev)
     for i in range(0, steps, CHUNK):
@@ -288,8 +296,12 @@ if __name__ == '__main__':
     ap.add_argument('--cell-by-cell', action='store_true', help='one (scenario, accuracy range) after the other instead of all at once')
     ap.add_argument('--algorithm', choices=['projectron', 'projectron_plus'], default='projectron',
                     help='the update rule of the agents; projectron_plus turns the closed loop\'s margin-rule update phase on')
+    ap.add_argument('--control-plus-batch', type=int, choices=[0, 2, 4, 8], default=0, metavar='W',
+                    help='with --algorithm projectron_plus: W candidates of a step share one pass over Kinv (same results; 0: one by one)')
     args = ap.parse_args()
     cells = list(product(args.scenarios, accuracy_list))
+    if args.control_plus_batch and args.algorithm != 'projectron_plus':
+        ap.error('--control-plus-batch needs --algorithm projectron_plus')
     if args.serial and args.algorithm != 'projectron':
         ap.error('--serial runs the reference-shaped classes, whose agents are Projectron learners')
     if args.serial:
@@ -299,6 +311,8 @@ if __name__ == '__main__':
                 evaluator.evaluate(run)
     elif args.cell_by_cell:
         for scenario, a_range in cells:
-            BatchedEvaluator(scenario, a_range, steps=args.steps, out_dir=args.out, algorithm=args.algorithm).evaluate_all(range(args.runs))
+            BatchedEvaluator(scenario, a_range, steps=args.steps, out_dir=args.out, algorithm=args.algorithm,
+                             control_plus_batch=args.control_plus_batch).evaluate_all(range(args.runs))
     else:
-        evaluate_grid(cells, range(args.runs), steps=args.steps, out_dir=args.out, verbose=True, algorithm=args.algorithm)
+        evaluate_grid(cells, range(args.runs), steps=args.steps, out_dir=args.out, verbose=True, algorithm=args.algorithm,
+                      control_plus_batch=args.control_plus_batch)

@@ -30,6 +30,7 @@ KB_EXPORTS = (
     'kb_set_fit_wide_plus', 'kb_get_fit_wide_plus',
     'kb_fit_steps',
     'kb_set_control_plus', 'kb_get_control_plus',
+    'kb_set_control_plus_batch', 'kb_get_control_plus_batch', 'kb_control_plus_batch_info',
 )
 
 EXPORTS = (
@@ -226,6 +227,9 @@ def load(dev=None):
     L.kb_fit_steps.argtypes = [vp, ip, C.c_int32, i64p, fp, ip, ip, C.c_int32, dp, ip, ip, ip, ip]
     L.kb_set_control_plus.argtypes = [vp, C.c_int32]
     L.kb_get_control_plus.argtypes = [vp, ip]
+    L.kb_set_control_plus_batch.argtypes = [vp, C.c_int32, C.c_int32]
+    L.kb_get_control_plus_batch.argtypes = [vp, ip, ip, up]
+    L.kb_control_plus_batch_info.argtypes = [vp, up]
     for name in EXPORTS:
         if name not in ('rs_last_error', 'rs_destroy', 'kb_last_error', 'kb_destroy'):
             getattr(L, name).restype = C.c_int

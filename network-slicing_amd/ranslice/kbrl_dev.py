@@ -94,7 +94,7 @@ class VecKBRL:
 
     def __init__(self, n_envs, dims, n_prbs, alfa=KBRL_ALFA, accuracy_range=(0.99, 0.999), gamma=KBRL_GAMMA,
                  eta=KBRL_ETA, capacity=4096, device=0, shared=False, first_env=0, pool_bytes=0, algorithm='projectron',
-                 control_plus=False):
+                 control_plus=False, control_plus_batch=0, control_plus_batch_max=1024):
         if algorithm not in ALGORITHMS:
             raise ValueError('algorithm must be one of %s, not %r' % (sorted(ALGORITHMS), algorithm))
         self.L = _lib.load()
@@ -117,6 +117,8 @@ class VecKBRL:
             self.set_algorithm(algorithm)
         if control_plus:
             self.set_control_plus(True)
+        if control_plus_batch:
+            self.set_control_plus_batch(control_plus_batch, control_plus_batch_max)
 
     def set_algorithm(self, algorithm):
         """the update rule of the next update() / fit() (kb_set_algorithm): 'projectron' (the default; projectron.py:39-60) or
@@ -400,6 +402,30 @@ class VecKBRL:
         a = C.c_int32()
         self._check(self.L.kb_get_control_plus(self.h, C.byref(a)))
         return bool(a.value)
+
+    def set_control_plus_batch(self, width, max_landmarks=1024):
+        """how many candidates of a step share one pass over Kinv while the closed loop learns in 'projectron_plus' mode with
+        set_control_plus on (kb_set_control_plus_batch): 0 (the default) one by one, or 2, 4, 8.  max_landmarks (a multiple of 64,
+        64 .. capacity) is the largest dictionary that is grouped; a larger one takes its candidates one by one.  Bit for bit the
+        results of width 0.  The scratch -- min(n_envs x S, 1024) arenas of 2 x width x max_landmarks doubles -- is allocated
+        here and freed at width 0.  No effect in 'projectron' mode or while set_control_plus is off.  A property of this handle:
+        not saved, not carried over.  Refused (RS_ESTATE) on deployed, by-reference and shared-dictionary handles."""
+        self._check(self.L.kb_set_control_plus_batch(self.h, int(width), int(max_landmarks)))
+
+    @property
+    def control_plus_batch(self):
+        """(width, max_landmarks, scratch_bytes) of set_control_plus_batch (kb_get_control_plus_batch); (0, 0, 0) while it is off"""
+        a, b, n = C.c_int32(), C.c_int32(), C.c_uint64()
+        self._check(self.L.kb_get_control_plus_batch(self.h, C.byref(a), C.byref(b), C.byref(n)))
+        return a.value, b.value, n.value
+
+    def control_plus_batch_work(self):
+        """kb_control_plus_batch_info since the width was last set: groups formed, groups skipped (nobody inside the margin), passes
+        over Kinv, tiles they read, d* columns formed, columns discarded behind an insertion, candidates taken one by one, of those
+        the ones that ran the mat-vec"""
+        w = (C.c_uint64 * 8)()
+        self._check(self.L.kb_control_plus_batch_info(self.h, w))
+        return [int(v) for v in w]
 
     @property
     def fit_wide(self):
@@ -800,6 +826,10 @@ class SharedVecKBRL(VecKBRL):
     def set_control_plus(self, on=True):
         """refused, as kb_set_control_plus refuses it: a shared-dictionary handle does not learn through update_control"""
         raise _lib.RanSliceError(_lib.RS_ESTATE, 'set_control_plus: a shared-dictionary handle does not learn through update_control')
+
+    def set_control_plus_batch(self, width, max_landmarks=1024):
+        """refused, as kb_set_control_plus_batch refuses it"""
+        raise _lib.RanSliceError(_lib.RS_ESTATE, 'set_control_plus_batch: a shared-dictionary handle does not learn through update_control')
 
     def set_fit_wide_plus(self, on=True):
         """refused, as kb_set_fit_wide_plus refuses it: a shared-dictionary handle does not learn through fit()"""

@@ -40,6 +40,12 @@ FIT_SCRATCH.update({'fit_steps_kernel': 0, 'fit_steps_plus_kernel': 0})
 # the closed loop's update phase in Projectron++ mode (kb_control_plus.hip): fit_steps_plus_kernel's row behind
 # update_control's bookkeeping: no scratch
 FIT_SCRATCH.update({'control_plus_kernel': 0})
+# the same row with one pass over Kinv for a group of candidates (kb_control_plus_batch.hip), one instance per
+# width, all built for two waves per SIMD: held to the VGPRs, LDS and scratch the build shows -- (registers, LDS bytes, scratch
+# bytes per lane).  Widths 2 and 4 have no scratch.  Width 8 spills 196 B per lane at two waves per SIMD; left at one wave per SIMD
+# (306 registers, no scratch) it was slower at every point measured (DESIGN.md §8m has both sets of figures)
+CTL_BATCH = {'control_plus_batch_kernelILi2E': (209, 19968, 0), 'control_plus_batch_kernelILi4E': (249, 28240, 0),
+             'control_plus_batch_kernelILi8E': (256, 44784, 196)}
 PRODUCTION = ["embb_step_kernelILi16ELb0ELb0ELb1E", "embb_step_kernelILi16ELb0ELb1ELb1E"]   # <16, false, plain | BLOCK, FDIV>
 PLAIN = PRODUCTION[0]          # the instance bench.py's headline runs
 STEP_KERNEL = 'embb_step_kernelIL'
@@ -156,6 +162,21 @@ def check(path=LOG):
                                                                            r.get('LDS Size')))
         if r.get('ScratchSize', 0) > limit:
             bad.append('%s spills %d B/lane (> %d)' % (key, r['ScratchSize'], limit))
+    for key, (regs, lds, scratch) in CTL_BATCH.items():
+        hit = [k for k in res if re.search(r'\d' + key, k)]
+        if not hit:
+            bad.append('%s: not found in %s' % (key, path))
+            continue
+        r = res[hit[0]]
+        used = r.get('VGPRs', 0) + r.get('AGPRs', 0)
+        print('%s: VGPRs %s + AGPRs %s, scratch %s B/lane, occupancy %s, LDS %s B' % (key, r.get('VGPRs'), r.get('AGPRs'), r.get('ScratchSize'),
+                                                                                      r.get('Occupancy'), r.get('LDS Size')))
+        if used > regs:
+            bad.append('%s uses %d vector registers (> %d)' % (key, used, regs))
+        if r.get('LDS Size', 0) > lds:
+            bad.append('%s uses %d B of LDS (> %d)' % (key, r['LDS Size'], lds))
+        if r.get('ScratchSize', 0) > scratch:
+            bad.append('%s spills %d B/lane (> %d)' % (key, r['ScratchSize'], scratch))
     return bad
 
 

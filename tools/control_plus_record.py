@@ -11,6 +11,13 @@ workgroup per learner, so with kernel timing on the agents are stepped once more
 the replica with the largest dictionary -- its update phase is that replica's workgroups alone.
 
   python tools/control_plus_record.py [--replicas 4096] [--at 50 500 2000] [--window 10] [--out profiles/control_plus_record.json]
+
+--batch W (2, 4 or 8) measures kb_set_control_plus_batch instead and writes profiles/control_plus_batch_record.json:
+the same agents, the same three points; at each point the fleet is forked into a second pair of handles --rounds (3) times per
+width, widths 0 and W alternating, and the window is timed on the fork -- same dictionaries, same states, same steps for both
+widths (their results are equal bit for bit, so either may carry the run between the points: W does).  Per point: the update
+phase's ms per step as median and range over the rounds, kb_control_plus_batch_info's work[0..7] per step, and the largest
+learner's share at both widths.  --also 2 4 adds one round each at further widths, for the curve.
 """
 import argparse
 import json
@@ -106,8 +113,108 @@ def _leg(mode, n, at, window, capacity, pool_bytes, seed):
     return dict(windows=out, flagged=sum(len(v) for v in flags.values()))
 
 
+def _batch_leg(width, also, rounds, n, at, window, capacity, pool_bytes, seed, max_landmarks):
+    import ctypes as C
+    import statistics
+    import numpy as np
+    from ranslice.config import make_config
+    from ranslice.kbrl_dev import VecKBRL
+    from ranslice.vec_env import VecRanSlice, default_fading
+    cfg = make_config(0, n_envs=n)
+    dims, n_prbs = [10] * cfg.n_embb + [3] * cfg.n_mmtc, cfg.n_prbs
+    mode = 'projectron_plus'
+
+    def pair(k, pool):
+        return (VecRanSlice(n_envs=k, cfg=make_config(0, n_envs=k), fading=default_fading(), seed=seed),
+                VecKBRL(k, dims, n_prbs, capacity=capacity, pool_bytes=pool, algorithm=mode, control_plus=True))
+    env, ag = pair(n, pool_bytes)
+    fenv, fag = pair(n, pool_bytes)        # the fork the windows are timed on
+    oenv, one = pair(1, 1 << 30)           # the replica with the largest dictionary, alone
+    ag.set_control_plus_batch(width, max_landmarks)
+    ia = np.full((n, len(dims)), n_prbs // (2 * len(dims)), dtype=np.int32)
+    env.reset()
+    fenv.reset()
+    oenv.reset()
+    ag.reset(ia, np.full((n, len(dims)), 3, dtype=np.int32))
+    env._check(env.L.rs_step(env.h, ia.ctypes.data_as(C.POINTER(C.c_int32)), None, None, None, None))
+    everyone = np.arange(n, dtype=np.int32)
+
+    def timed(a, e, w):
+        a.set_control_plus_batch(w, max_landmarks)      # (also restarts the counters)
+        a.set_kernel_timing(True)
+        a.phase_times_ms()
+        r0 = a._repair_raw()
+        a.run_resident(e, window, graph=False)
+        a.synchronize()
+        ms = a.phase_times_ms()['update_ms']
+        a.set_kernel_timing(False)
+        return ms, [v / window for v in a.control_plus_batch_work()], (int(a._repair_raw()[6]) - int(r0[6])) / window
+
+    out, step = [], 0
+    for a_ in at:
+        first = max(step, a_ - window // 2)
+        t0 = time.perf_counter()
+        while step < first:      # (in stretches, with a sign of life between them)
+            k = min(250, first - step)
+            ag.run_resident(env, k, graph=False)
+            ag.synchronize()
+            step += k
+            print('step %d, %.1f s' % (step, time.perf_counter() - t0), file=sys.stderr, flush=True)
+        between = time.perf_counter() - t0
+        sizes = ag.dictionary_sizes()
+        worst = int(np.argmax(sizes.max(axis=1)))
+        plan = [(w, r) for r in range(rounds) for w in (0, width)] + [(w, 0) for w in also]
+        ms, work, matvec, alone = {}, {}, {}, {}
+        for w, _ in plan:
+            fag.fork_from(ag, everyone)
+            fenv.fork_from(env, everyone)
+            t, wk, mv = timed(fag, fenv, w)
+            ms.setdefault(w, []).append(t)
+            work[w], matvec[w] = wk, mv
+        for w in (0, width):
+            one.fork_from(ag, [worst])
+            oenv.fork_from(env, [worst])
+            alone[w] = timed(one, oenv, w)[0]
+        rec = dict(steps=[first, first + window], wall_s_since_the_last_window=between, landmarks_mean=float(sizes.mean()),
+                   landmarks_max=int(sizes.max()), largest_replica=dict(replica=worst, landmarks=sizes[worst].tolist()),
+                   matvec_samples_per_step=matvec[0],
+                   widths={str(w): dict(update_ms_per_step=dict(median=statistics.median(v), min=min(v), max=max(v), runs=v),
+                                        work_per_step=work[w],
+                                        **(dict(largest_replica_alone_update_ms_per_step=alone[w],
+                                                largest_replica_share_of_the_update_phase=alone[w] / statistics.median(v))
+                                           if w in alone else {}))
+                           for w, v in ms.items()})
+        out.append(rec)
+        print(json.dumps(rec), flush=True)
+        ag.set_control_plus_batch(width, max_landmarks)
+        ag.run_resident(env, window, graph=False)
+        step += window
+    flags = ag.flagged_replicas()
+    for h in (env, ag, fenv, fag, oenv, one):
+        h.close()
+    return dict(windows=out, flagged=sum(len(v) for v in flags.values()))
+
+
+def _batch_resources():
+    import check_resources as cr
+    if not os.path.exists(cr.LOG):
+        return None
+    res = cr.parse()
+    out = {}
+    for k, r in res.items():
+        if 'control_plus_batch_kernel' in k or 'control_plus_kernel' in k:
+            out[k] = dict(vgprs=r.get('VGPRs'), agprs=r.get('AGPRs'), sgprs_spilled=r.get('SGPRs Spill'),
+                          scratch_bytes_per_lane=r.get('ScratchSize'), occupancy=r.get('Occupancy'), lds_bytes=r.get('LDS Size'))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, choices=[2, 4, 8], default=None,
+                    help='measure kb_set_control_plus_batch at this width against width 0 (writes profiles/control_plus_batch_record.json)')
+    ap.add_argument('--also', type=int, nargs='*', default=[], help='with --batch: further widths, one round each')
+    ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--max-landmarks', type=int, default=2048)
     ap.add_argument('--replicas', type=int, default=4096)
     ap.add_argument('--at', type=int, nargs='*', default=[50, 500, 2000])
     ap.add_argument('--window', type=int, default=10)
@@ -116,6 +223,20 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'control_plus_record.json'))
     args = ap.parse_args()
+    if args.batch:
+        out = args.out if args.out != ap.get_default('out') else os.path.join(ROOT, 'profiles', 'control_plus_batch_record.json')
+        rec = dict(what='closed control loop in Projectron++ mode, scenario 0, %d replicas on one device: kb_set_control_plus_batch at '
+                        'width %d against width 0 on forks of the same fleet, %d rounds per width alternating; plain launches, kernel '
+                        'timing on for %d steps per window; no threshold attached' % (args.replicas, args.batch, args.rounds, args.window),
+                   replicas=args.replicas, window=args.window, width=args.batch, rounds=args.rounds, max_landmarks=args.max_landmarks,
+                   kernels=_batch_resources())
+        rec.update(_batch_leg(args.batch, args.also, args.rounds, args.replicas, sorted(args.at), args.window, args.capacity,
+                              int(args.pool_gb * (1 << 30)), args.seed, args.max_landmarks))
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, 'w') as fh:
+            json.dump(rec, fh, indent=1, sort_keys=True)
+            fh.write('\n')
+        return
     rec = dict(what='closed control loop, scenario 0, %d replicas on one device: Projectron++ behind kb_set_control_plus, and '
                     'Projectron on the same build for scale; one run per figure, no threshold attached' % args.replicas,
                replicas=args.replicas, window=args.window, kernel=_kernel_resources())
