@@ -10,6 +10,7 @@
 3. The taught agents are deployed on a fresh fleet and stepped.
 
   python examples/teach_from_log.py --agents 8 --steps 40 --algorithm projectron_plus
+  python examples/teach_from_log.py --agents 8 --steps 40 --algorithm projectron_plus --batch 8    # 8 candidates of a row per pass over Kinv
 """
 import argparse
 import os
@@ -33,7 +34,12 @@ def main():
     ap.add_argument('--algorithm', choices=['projectron', 'projectron_plus'], default='projectron')
     ap.add_argument('--teacher-algorithm', choices=['projectron', 'projectron_plus'], default='projectron',
                     help='the rule of the closed loop that produces the log (projectron_plus turns set_control_plus on)')
+    ap.add_argument('--batch', type=int, choices=[0, 2, 4, 8], default=0,
+                    help="with --algorithm projectron_plus: that many candidates of a log row share one pass over Kinv "
+                         '(VecKBRL.set_fit_steps_batch; same results)')
     a = ap.parse_args()
+    if a.batch and a.algorithm != 'projectron_plus':
+        ap.error('--batch groups the candidates of the projectron_plus rule: it needs --algorithm projectron_plus')
     cfg = make_config(a.scenario, n_envs=a.agents)
     dims, n_prbs, n = [10] * cfg.n_embb + [3] * cfg.n_mmtc, cfg.n_prbs, a.agents
     fading = default_fading()
@@ -61,12 +67,15 @@ def main():
     print('logged %d steps of %d agents: %d bytes' % (a.steps, n, n * a.steps * (4 * sum(dims) + 8 * len(dims))))
 
     # 2. a fresh handle, taught from the log
-    pupil = VecKBRL(n, dims, n_prbs, capacity=1024, pool_bytes=256 << 20, algorithm=a.algorithm)
+    pupil = VecKBRL(n, dims, n_prbs, capacity=1024, pool_bytes=256 << 20, algorithm=a.algorithm, fit_steps_batch=a.batch)
     pupil.reset(ia, sf)
     out = pupil.fit_steps(np.arange(n), *log)
     w = pupil.fit_time_ms()
     print('fit_steps (%s): %d samples generated on the device, %d changed a dictionary, %d insertions'
           % (a.algorithm, w['samples'], w['mistakes'], w['insertions']))
+    if a.batch:
+        b = pupil.fit_steps_batch_work()
+        print('groups of up to %d candidates: %d formed, %d skipped, %d passes over Kinv for %d columns of d*' % (a.batch, b[0], b[1], b[2], b[4]))
     print('agreement of the sign of f at the logged allocation with the label, last 10 steps: %.3f'
           % np.mean([(o[-10:] == l[-10:]).mean() for o, l in zip(out['y_at'], log[2])]))
     print('dictionary sizes of agent 0: taught from the log %s, the closed loop %s'

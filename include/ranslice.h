@@ -774,7 +774,8 @@ int kb_get_fit_wide_plus(kb_handle* k, int32_t* on);
  * Afterwards, as after kb_fit: the cached kb_predict of every learner that received a sample is invalid and versions have
  * moved; agents not listed, agents without rows and learners whose entries are all 0 are not touched at all.  kb_fit_time_ms
  * reports the call as it reports a kb_fit (ms[0]; work[0..3] samples, mistakes, insertions, kernel evaluations; the f_at columns
- * are not counted).  The chip-wide rounds are not used: one workgroup per learner always, kb_set_fit_wide and
+ * are not counted).  The chip-wide rounds are not used: a learner is taught by one workgroup (one per learner; in Projectron++
+ * mode under kb_set_fit_steps_batch, below, at most 1024 per launch, which take the learners in turn), kb_set_fit_wide and
  * kb_set_fit_wide_plus have no effect on this call, and kb_fit_wide_info keeps describing the last kb_fit.
  * RS_EINVAL, before anything is changed: an agent out of range or listed twice, first[0] != 0 or first decreasing, a label
  * outside {-1, 0, 1}, an action outside 0 .. n_prbs where the label is not 0, n or chunk negative.  RS_ESTATE: kb_reset missing;
@@ -831,6 +832,31 @@ int kb_get_control_plus(kb_handle* k, int32_t* on);
 int kb_set_control_plus_batch(kb_handle* k, int32_t width, int32_t max_landmarks);
 int kb_get_control_plus_batch(kb_handle* k, int32_t* width, int32_t* max_landmarks, uint64_t* scratch_bytes);
 int kb_control_plus_batch_info(kb_handle* k, uint64_t work[8]);
+
+/* ---- the same pass for the rows of kb_fit_steps (csrc/kb_fit_steps_batch.hip).
+ * kb_set_fit_steps_batch(k, width, max_landmarks): width = 0 (the default): kb_fit_steps as above, every kernel, launch and bit.
+ * width = 2, 4 or 8: while the handle is in Projectron++ mode kb_fit_steps launches fit_steps_batch_kernel instead: every row's
+ * candidates go through the group walk of kb_set_control_plus_batch -- the d* of the next `width` candidates of the row from ONE
+ * read of the stored triangle, a group nobody of which lies inside the margin makes no pass, an insertion ends its group behind
+ * itself, a group never spans rows.  Landmarks, coefficients, all of Kinv, sizes, statistics, flags, the tie stream's position,
+ * all five returned summaries (f_at included) and kb_fit_time_ms's work[0..3] are BIT FOR BIT those of width 0, whatever the
+ * chunk; kb_get_repair_work is not added to, as at width 0.  In Projectron mode the setting has no effect.  max_landmarks as for
+ * kb_set_control_plus_batch: a multiple of 64, at least 64 and at most the handle's capacity (ignored when width is 0); a larger
+ * dictionary, and one of fewer than two landmarks, takes its candidates one by one inside the same kernel.
+ * Scratch: the setter's own -- not kb_set_control_plus_batch's, whose report it does not change -- sized for the handle and not
+ * for a call, allocated here, freed when the width returns to 0 and at kb_destroy:
+ *     scratch_bytes = 128 + min(n_envs * n_slices, 1024) * 2 * width * max_landmarks * 8        (0 while the width is 0)
+ * A launch has min(n * n_slices, 1024) workgroups, which take the call's learners from a ticket.  A change of either value waits
+ * for the agent's stream.  Host state of the handle: not part of kb_save_state blobs or agent files, carried over by no transfer
+ * call.  RS_EINVAL for any other width or max_landmarks (the message names the accepted values); RS_ESTATE on an inference-only,
+ * a by-reference or a shared-dictionary handle.
+ * kb_fit_steps_batch_info: work[8] of the last kb_fit_steps on the handle, zeroed when a call opens (zeros while the width is 0
+ * and in Projectron mode): kb_control_plus_batch_info's eight -- [0] groups formed, [1] groups skipped, [2] passes over Kinv,
+ * [3] tiles those passes read, [4] d* columns formed, [5] columns discarded behind an insertion, [6] candidates that went one by
+ * one, [7] of those, the ones that ran the mat-vec. */
+int kb_set_fit_steps_batch(kb_handle* k, int32_t width, int32_t max_landmarks);
+int kb_get_fit_steps_batch(kb_handle* k, int32_t* width, int32_t* max_landmarks, uint64_t* scratch_bytes);
+int kb_fit_steps_batch_info(kb_handle* k, uint64_t work[8]);   /* of the last kb_fit_steps */
 
 #ifdef __cplusplus
 }

@@ -79,6 +79,9 @@ struct kb_handle {
     int32_t cpb_width = 0, cpb_max = 0;             // kb_set_control_plus_batch: candidates per pass over Kinv (0: one by one) and the largest dictionary grouped; host state as well (kb_control_plus_batch.hip)
     char* d_cpb = nullptr;                          // its scratch: work[8], the ticket, the workgroups' arenas (allocated by the setter, freed at width 0)
     uint64_t cpb_bytes = 0;
+    int32_t fsb_width = 0, fsb_max = 0;             // kb_set_fit_steps_batch: the same for the rows of kb_fit_steps in Projectron++ mode; host state as well (kb_fit_steps_batch.hip)
+    char* d_fsb = nullptr;                          // its own scratch, laid out as d_cpb (allocated by the setter, freed at width 0)
+    uint64_t fsb_bytes = 0;
     // kb_fork / kb_deploy into this handle (kb_fork.hip)
     hipEvent_t ev_fork_in = nullptr, ev_fork_out = nullptr;
     int32_t* d_fork_idx = nullptr;   // [n_envs] source agent of every agent
@@ -108,6 +111,7 @@ static void kb_bridge_release(kb_handle* k);   // kb_bridge.hip
 static void kb_fit_release(kb_handle* k);      // kb_fit.hip
 static void kb_control_plus_release(kb_handle* k);  // kb_control_plus.hip
 static void kb_control_plus_batch_release(kb_handle* k);  // kb_control_plus_batch.hip
+static void kb_fit_steps_batch_release(kb_handle* k);     // kb_fit_steps_batch.hip
 static kb_handle* kb_ref_store(kb_handle* k);
 static int kb_ref_dict(kb_handle* k, size_t task);
 static int kb_ref_select(kb_handle* k, const float* d_state);  // the scoring of launch_select: one fused kernel
@@ -496,6 +500,7 @@ extern "C" void kb_destroy(kb_handle* k) {
     kb_fit_release(k);
     kb_control_plus_release(k);
     kb_control_plus_batch_release(k);
+    kb_fit_steps_batch_release(k);
     if (k->h_seen) (void)hipHostFree(k->h_seen);
     if (k->h_total) (void)hipHostFree(k->h_total);
     if (k->stream) (void)hipStreamDestroy(k->stream);

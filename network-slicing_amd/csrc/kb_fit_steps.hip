@@ -9,7 +9,8 @@
 // ranslice.kbrl_dev.augmented_samples writes out as rows of 16 doubles for kb_fit.  fit_steps_kernel generates them in place:
 // one 256-thread workgroup per (listed agent, slice), persistent over the agent's rows of the launch, and per sample fit_learner's
 // sequence -- the kernel column and f, the tie draw on an exact f == 0 against a populated dictionary, the rule -- by the same
-// device functions.  The one difference is where the kernel column's distances come from.  predict_column sums dist over the
+// device functions (in Projectron++ mode kb_set_fit_steps_batch replaces that launch by persistent workgroups that take the learners
+// from a ticket: kb_fit_steps_batch.hip).  The one difference is where the kernel column's distances come from.  predict_column sums dist over the
 // coordinates in order, the allocation last; the sum over the state coordinates is therefore the same double for every candidate
 // of a step, and it is formed once per landmark and step (steps_prefix, kept in LDS for the first KB_STEPS_PRE landmarks and
 // formed again per sample beyond them) instead of once per landmark and sample.  The library is built without contraction or
@@ -131,6 +132,10 @@ __global__ __launch_bounds__(256) void fit_steps_plus_kernel(StepsArgs A) {
 
 }  // namespace kb
 
+// kb_set_fit_steps_batch (kb_fit_steps_batch.hip): its counters start over with a call; one chunk of the call's learners, grouped
+static int kb_fit_steps_batch_open(kb_handle* k);
+static int launch_fit_steps_batch(kb_handle* k, const kb::StepsArgs& a, int32_t learners);
+
 extern "C" int kb_fit_steps(kb_handle* k, const int32_t* agent, int32_t n, const int64_t* first, const float* state,
                             const int32_t* action, const int32_t* labels, int32_t chunk, double* f_at, int32_t* y_at,
                             int32_t* changed, int32_t* grown, int32_t* m_after) {
@@ -175,6 +180,7 @@ extern "C" int kb_fit_steps(kb_handle* k, const int32_t* agent, int32_t n, const
     for (int32_t i = 0; i < n; ++i) longest = std::max<int64_t>(longest, first[i + 1] - first[i]);
     if (chunk == 0) chunk = std::max<int32_t>(1, KB_FIT_CHUNK / (P + 1));  // about kb_fit's default in samples of one learner
     if ((rc = kb_fit_open(k)) != RS_OK) return rc;  // (d_work[8..11], kb_fit_wide_info, stay the last kb_fit's)
+    if ((rc = kb_fit_steps_batch_open(k)) != RS_OK) return rc;
     kb_fit_state* p = k->fit;
     std::vector<long long> rel((size_t)n + 1);
     for (int32_t i = 0; i <= n; ++i) rel[(size_t)i] = (long long)first[i];
@@ -211,7 +217,9 @@ extern "C" int kb_fit_steps(kb_handle* k, const int32_t* agent, int32_t n, const
         a.from = (long long)from;
         hipEvent_t e;
         HIPCHK(k, p->fit_spans.begin(k->stream, 0, &e));
-        if (k->alg == KB_ALG_PROJECTRON_PLUS)
+        if (k->alg == KB_ALG_PROJECTRON_PLUS && k->fsb_width > 0)  // (kb_set_fit_steps_batch: `width` candidates of a row per pass over Kinv)
+            (void)launch_fit_steps_batch(k, a, n * S);
+        else if (k->alg == KB_ALG_PROJECTRON_PLUS)
             hipLaunchKernelGGL(kb::fit_steps_plus_kernel, dim3(grid), dim3(256), 0, k->stream, a);
         else
             hipLaunchKernelGGL(kb::fit_steps_kernel, dim3(grid), dim3(256), 0, k->stream, a);

@@ -94,7 +94,7 @@ class VecKBRL:
 
     def __init__(self, n_envs, dims, n_prbs, alfa=KBRL_ALFA, accuracy_range=(0.99, 0.999), gamma=KBRL_GAMMA,
                  eta=KBRL_ETA, capacity=4096, device=0, shared=False, first_env=0, pool_bytes=0, algorithm='projectron',
-                 control_plus=False, control_plus_batch=0, control_plus_batch_max=1024):
+                 control_plus=False, control_plus_batch=0, control_plus_batch_max=1024, fit_steps_batch=0, fit_steps_batch_max=1024):
         if algorithm not in ALGORITHMS:
             raise ValueError('algorithm must be one of %s, not %r' % (sorted(ALGORITHMS), algorithm))
         self.L = _lib.load()
@@ -119,6 +119,8 @@ class VecKBRL:
             self.set_control_plus(True)
         if control_plus_batch:
             self.set_control_plus_batch(control_plus_batch, control_plus_batch_max)
+        if fit_steps_batch:
+            self.set_fit_steps_batch(fit_steps_batch, fit_steps_batch_max)
 
     def set_algorithm(self, algorithm):
         """the update rule of the next update() / fit() (kb_set_algorithm): 'projectron' (the default; projectron.py:39-60) or
@@ -326,7 +328,8 @@ class VecKBRL:
         sample).  chunk: most log rows of one agent per launch (0: the default); no result depends on it.  -> dict of per-agent
         lists of arrays [T_i, S]: f_at (f at the logged allocation before the row's first sample), y_at (its sign; 0 on a tie or
         an empty dictionary), changed (samples of the row that changed the dictionary), grown (insertions) and m (the size after
-        the row).  One workgroup per learner always: set_fit_wide has no effect here.  The cached predict of the learners that
+        the row).  One workgroup per learner (in 'projectron_plus' mode set_fit_steps_batch lets the candidates of a row share
+        their pass over Kinv, with the same bits); set_fit_wide has no effect here.  The cached predict of the learners that
         received samples is invalid afterwards; fit_time_ms() reports the call like a fit."""
         agent, first, st, ac, lb = self._pack_steps(agents, state, action, labels)
         R = int(first[-1])
@@ -425,6 +428,31 @@ class VecKBRL:
         the ones that ran the mat-vec"""
         w = (C.c_uint64 * 8)()
         self._check(self.L.kb_control_plus_batch_info(self.h, w))
+        return [int(v) for v in w]
+
+    def set_fit_steps_batch(self, width, max_landmarks=1024):
+        """how many candidates of a log row share one pass over Kinv while fit_steps teaches in 'projectron_plus' mode
+        (kb_set_fit_steps_batch): 0 (the default) one by one, or 2, 4, 8.  max_landmarks (a multiple of 64, 64 .. capacity) is the
+        largest dictionary that is grouped; a larger one takes its candidates one by one.  Bit for bit the results of width 0,
+        the returned summaries included.  The scratch -- min(n_envs x S, 1024) arenas of 2 x width x max_landmarks doubles, its
+        own and not set_control_plus_batch's -- is allocated here and freed at width 0.  No effect in 'projectron' mode.  A
+        property of this handle: not saved, not carried over.  Refused (RS_ESTATE) on deployed, by-reference and
+        shared-dictionary handles."""
+        self._check(self.L.kb_set_fit_steps_batch(self.h, int(width), int(max_landmarks)))
+
+    @property
+    def fit_steps_batch(self):
+        """(width, max_landmarks, scratch_bytes) of set_fit_steps_batch (kb_get_fit_steps_batch); (0, 0, 0) while it is off"""
+        a, b, n = C.c_int32(), C.c_int32(), C.c_uint64()
+        self._check(self.L.kb_get_fit_steps_batch(self.h, C.byref(a), C.byref(b), C.byref(n)))
+        return a.value, b.value, n.value
+
+    def fit_steps_batch_work(self):
+        """kb_fit_steps_batch_info of the last fit_steps (zeros while the width is 0 or the mode 'projectron'): groups formed, groups
+        skipped (nobody inside the margin), passes over Kinv, tiles they read, d* columns formed, columns discarded behind an
+        insertion, candidates taken one by one, of those the ones that ran the mat-vec"""
+        w = (C.c_uint64 * 8)()
+        self._check(self.L.kb_fit_steps_batch_info(self.h, w))
         return [int(v) for v in w]
 
     @property
@@ -830,6 +858,10 @@ class SharedVecKBRL(VecKBRL):
     def set_control_plus_batch(self, width, max_landmarks=1024):
         """refused, as kb_set_control_plus_batch refuses it"""
         raise _lib.RanSliceError(_lib.RS_ESTATE, 'set_control_plus_batch: a shared-dictionary handle does not learn through update_control')
+
+    def set_fit_steps_batch(self, width, max_landmarks=1024):
+        """refused, as kb_set_fit_steps_batch refuses it"""
+        raise _lib.RanSliceError(_lib.RS_ESTATE, 'set_fit_steps_batch: a shared-dictionary handle does not learn through fit_steps')
 
     def set_fit_wide_plus(self, on=True):
         """refused, as kb_set_fit_wide_plus refuses it: a shared-dictionary handle does not learn through fit()"""

@@ -46,6 +46,11 @@ FIT_SCRATCH.update({'control_plus_kernel': 0})
 # (306 registers, no scratch) it was slower at every point measured (DESIGN.md §8m has both sets of figures)
 CTL_BATCH = {'control_plus_batch_kernelILi2E': (209, 19968, 0), 'control_plus_batch_kernelILi4E': (249, 28240, 0),
              'control_plus_batch_kernelILi8E': (256, 44784, 196)}
+# kb_fit_steps's rows through the same walk (kb_fit_steps_batch.hip), the same three widths at two waves per SIMD:
+# what the build shows, which is the control loop's instances' but for 8 B per lane more at width 8.  (As a row loop inside a
+# learner loop the kernel showed 124 B at width 4 and 372 B at width 8; it is one loop, a row per trip, for that reason.)
+FIT_STEPS_BATCH = {'fit_steps_batch_kernelILi2E': (209, 19968, 0), 'fit_steps_batch_kernelILi4E': (249, 28240, 0),
+                   'fit_steps_batch_kernelILi8E': (256, 44784, 204)}
 PRODUCTION = ["embb_step_kernelILi16ELb0ELb0ELb1E", "embb_step_kernelILi16ELb0ELb1ELb1E"]   # <16, false, plain | BLOCK, FDIV>
 PLAIN = PRODUCTION[0]          # the instance bench.py's headline runs
 STEP_KERNEL = 'embb_step_kernelIL'
@@ -162,7 +167,7 @@ def check(path=LOG):
                                                                            r.get('LDS Size')))
         if r.get('ScratchSize', 0) > limit:
             bad.append('%s spills %d B/lane (> %d)' % (key, r['ScratchSize'], limit))
-    for key, (regs, lds, scratch) in CTL_BATCH.items():
+    for key, (regs, lds, scratch) in list(CTL_BATCH.items()) + list(FIT_STEPS_BATCH.items()):
         hit = [k for k in res if re.search(r'\d' + key, k)]
         if not hit:
             bad.append('%s: not found in %s' % (key, path))
