@@ -833,6 +833,40 @@ int kb_set_control_plus_batch(kb_handle* k, int32_t width, int32_t max_landmarks
 int kb_get_control_plus_batch(kb_handle* k, int32_t* width, int32_t* max_landmarks, uint64_t* scratch_bytes);
 int kb_control_plus_batch_info(kb_handle* k, uint64_t work[8]);
 
+/* ---- the large learners' passes spread over the chip (csrc/kb_control_plus_wide.hip).
+ * kb_set_control_plus_wide(k, min_landmarks, max_landmarks, rounds): min_landmarks = 0 (the default): the update phase as above,
+ * every kernel, launch and bit; the scratch is freed.  Otherwise 2 <= min_landmarks <= max_landmarks, max_landmarks a multiple of
+ * 64 in 64 .. capacity, 1 <= rounds <= 256: while the handle is in Projectron++ mode AND kb_set_control_plus is on AND
+ * kb_set_control_plus_batch's width is 2, 4 or 8, the learners that hold min_landmarks .. max_landmarks at the start of an update
+ * phase -- and no more than kb_set_control_plus_batch's max_landmarks, beyond which that walk takes the candidates one by one --
+ * in task order the first min(n_envs * n_slices, 1024) of them, are HEAVY: behind the head of their row (the state, f at
+ * the executed allocation, the decision, the bookkeeping) they leave the batch kernel and advance in `rounds` rounds of launches as
+ * wide as the chip -- the pass d* = Kinv K_f of a group of candidates, one wave per output block of 64 entries, whatever learner it
+ * belongs to; the walk of the group's members, one workgroup per learner, which ends the learner's round at an insertion and
+ * otherwise goes on to the next group that needs a pass; the rank-1 update of Kinv of the learners that inserted -- and one more
+ * launch finishes, a workgroup per row, whatever the rounds left open (a learner an insertion took past the smaller of the two
+ * max_landmarks among them), in the batch kernel's arenas and by its max_landmarks: grouped or one by one as it would be there.
+ * Everybody else stays on the batch kernel's row.  No kernel waits for another and nothing on the host waits, so the results do
+ * not depend on `rounds` and a captured loop (kb_run_resident, use_graph = 1) carries the whole sequence.  Groups begin and end
+ * where the batch kernel's do and every sum keeps its order: landmarks, coefficients, all of Kinv, the control state, the tie
+ * streams, kb_get_stats, kb_get_repair_work and all eight counters of kb_control_plus_batch_info are BIT FOR BIT those of the same
+ * width with this switch off.  In every other state of the three settings named above every launch is what it is without it.
+ * Scratch: all of it is allocated by this call (the first launch may be inside a stream capture), apart from the repair queue's
+ * and from kb_set_control_plus_batch's, freed at min_landmarks = 0 and at kb_destroy; with T = n_envs * n_slices and slots =
+ * min(T, 1024) -- a slot is a record of 256 bytes and an arena for a group's K_f and d* columns, always eight wide:
+ *     scratch_bytes = 128 + slots * 256 + 2 * (slots + 1) * 8 + 8 * ceil(T / 2) + slots * 2 * 8 * max_landmarks * 8    (0 while off)
+ * A change of any value waits for the agent's stream and drops a captured loop, as kb_set_control_plus_batch does.  Host state of
+ * the handle like the batch width: not part of kb_save_state blobs or agent files, carried over by no transfer call.  RS_EINVAL
+ * for any other value (the message names the accepted ones); RS_ESTATE on an inference-only, a by-reference or a shared-dictionary
+ * handle.
+ * kb_control_plus_wide_info: work[8] since the switch was last set (zeros while it is off): [0] heavy rows taken, [1] learners
+ * turned away because the slots were full, [2] learner-rounds that made a spread pass, [3] tiles read in them (n_b (n_b + 1) / 2
+ * per pass), [4] rank-1 units spread (16 rows of a tile each), [5] rows that reached the finisher unfinished, [6] candidates the
+ * finisher walked, [7] update phases launched in this mode. */
+int kb_set_control_plus_wide(kb_handle* k, int32_t min_landmarks, int32_t max_landmarks, int32_t rounds);
+int kb_get_control_plus_wide(kb_handle* k, int32_t* min_landmarks, int32_t* max_landmarks, int32_t* rounds, uint64_t* scratch_bytes);
+int kb_control_plus_wide_info(kb_handle* k, uint64_t work[8]);
+
 /* ---- the same pass for the rows of kb_fit_steps (csrc/kb_fit_steps_batch.hip).
  * kb_set_fit_steps_batch(k, width, max_landmarks): width = 0 (the default): kb_fit_steps as above, every kernel, launch and bit.
  * width = 2, 4 or 8: while the handle is in Projectron++ mode kb_fit_steps launches fit_steps_batch_kernel instead: every row's

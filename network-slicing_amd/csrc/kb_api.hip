@@ -79,6 +79,10 @@ struct kb_handle {
     int32_t cpb_width = 0, cpb_max = 0;             // kb_set_control_plus_batch: candidates per pass over Kinv (0: one by one) and the largest dictionary grouped; host state as well (kb_control_plus_batch.hip)
     char* d_cpb = nullptr;                          // its scratch: work[8], the ticket, the workgroups' arenas (allocated by the setter, freed at width 0)
     uint64_t cpb_bytes = 0;
+    int32_t cpw_min = 0, cpw_max = 0, cpw_rounds = 0;  // kb_set_control_plus_wide: which learners' passes are spread over the chip (0: none), the largest of them, the rounds enqueued; host state as well (kb_control_plus_wide.hip)
+    char* d_cpw = nullptr;                          // its scratch: work[8], the slots' records, the two work lines, the slot numbers, the arenas (allocated by the setter, freed at min_landmarks 0)
+    uint64_t cpw_bytes = 0;
+    int cpw_grid[3] = {2048, 2048, 2048};           // one co-resident round of workgroups of its pass kernel at width 2, 4, 8 (the setter)
     int32_t fsb_width = 0, fsb_max = 0;             // kb_set_fit_steps_batch: the same for the rows of kb_fit_steps in Projectron++ mode; host state as well (kb_fit_steps_batch.hip)
     char* d_fsb = nullptr;                          // its own scratch, laid out as d_cpb (allocated by the setter, freed at width 0)
     uint64_t fsb_bytes = 0;
@@ -112,6 +116,7 @@ static void kb_fit_release(kb_handle* k);      // kb_fit.hip
 static void kb_control_plus_release(kb_handle* k);  // kb_control_plus.hip
 static void kb_control_plus_batch_release(kb_handle* k);  // kb_control_plus_batch.hip
 static void kb_fit_steps_batch_release(kb_handle* k);     // kb_fit_steps_batch.hip
+static void kb_control_plus_wide_release(kb_handle* k);   // kb_control_plus_wide.hip
 static kb_handle* kb_ref_store(kb_handle* k);
 static int kb_ref_dict(kb_handle* k, size_t task);
 static int kb_ref_select(kb_handle* k, const float* d_state);  // the scoring of launch_select: one fused kernel
@@ -501,6 +506,7 @@ extern "C" void kb_destroy(kb_handle* k) {
     kb_control_plus_release(k);
     kb_control_plus_batch_release(k);
     kb_fit_steps_batch_release(k);
+    kb_control_plus_wide_release(k);
     if (k->h_seen) (void)hipHostFree(k->h_seen);
     if (k->h_total) (void)hipHostFree(k->h_total);
     if (k->stream) (void)hipStreamDestroy(k->stream);
@@ -614,6 +620,8 @@ static void launch_shared_gemm(kb_handle* k, const float* d_state) {
 
 static int launch_control_plus(kb_handle* k, const kb::CtlArgs& a);  // kb_control_plus.hip: the update phase in Projectron++ mode
 static int launch_control_plus_batch(kb_handle* k, const kb::CtlArgs& a);  // kb_control_plus_batch.hip: the same, a group of candidates per pass over Kinv
+static bool kb_control_plus_wide_on(const kb_handle* k);                   // kb_control_plus_wide.hip: the same, the large learners' passes spread over the chip
+static int launch_control_plus_wide(kb_handle* k, const kb::CtlArgs& a);
 
 static int launch_update_control(kb_handle* k, const float* d_state, const int32_t* d_action, const int32_t* d_labels) {
     kb::CtlArgs a;
@@ -633,7 +641,9 @@ static int launch_update_control(kb_handle* k, const float* d_state, const int32
         // kb_set_control_plus: one workgroup per learner runs the step's candidates through the margin rule; no queue, no rounds
         // (kb_get_repair_work keeps its zeros)
         // (kb_set_control_plus_batch: the same row, `width` candidates per pass over Kinv)
-        const int rc = k->cpb_width > 0 ? launch_control_plus_batch(k, a) : launch_control_plus(k, a);
+        // (kb_set_control_plus_wide: the rows of the batch kernel, the large learners by chip-wide rounds)
+        const int rc = k->cpb_width > 0 ? (kb_control_plus_wide_on(k) ? launch_control_plus_wide(k, a) : launch_control_plus_batch(k, a))
+                                        : launch_control_plus(k, a);
         if (rc != RS_OK) return rc;
         if (e1) HIPCHK(k, hipEventRecord(e1, k->stream));
         return RS_OK;

@@ -56,7 +56,8 @@ struct BatchLds {
 
 // d* = Kinv K_f for the g columns kf[w * ld + j] of a group, into ds[w * ld + j], j < m (2 <= m <= ld, triangle storage).  Whole
 // 256-thread block; the caller puts a barrier in front (the columns are in memory) and behind (so is d*).  Per column the sums
-// of matvec_tri_tiles + matvec_tri_combine in their order (a change there is made here too).
+// of matvec_tri_tiles + matvec_tri_combine in their order (a change there is made here too).  The body of the loop over b is
+// restated as cpw_unit (kb_control_plus_wide.hip), one output block per wave of a chip-wide launch: a change here is made there too.
 template <int W>
 __device__ __forceinline__ void batch_matvec(const KbState& K, const uint64_t* sh, int m, int g, const double* kf, double* ds, int ld,
                                              BatchLds<W>& bs) {
@@ -165,7 +166,8 @@ struct BatchWork {
 // triangle) -- or a member of a GROUP, whose K_f and d* columns are copied into the page's rows.  Both then run the rule's tail at
 // ONE place: finish_update on y f <= 0, margin_update inside the margin (a change to fit_rule or apply_update_plus is made here too;
 // behind a call of fit_rule beside the group's own tail finish_update stood twice in the kernel, as two calls with 656 B per lane
-// of scratch between them).
+// of scratch between them).  cpw_walk_kernel (kb_control_plus_wide.hip) restates the walk cut where a group waits for its pass:
+// a change here is made there too.
 template <int W>
 __device__ __forceinline__ double plus_group_walk(const KbDev& D, const KbState& K, int dt, int task, int env, int s, const uint64_t* sh, int d,
                                                   int y, int a0, int a1, int* m_io, double* pre, Lds& sm, BatchLds<W>& bs, double* kf, double* ds,
@@ -312,7 +314,8 @@ __device__ __forceinline__ double plus_group_walk(const KbDev& D, const KbState&
 }
 
 // control_plus_kernel's row (steps 1-3 and 5 of DESIGN.md §8l; a change there is made here too) around the group walk, once per
-// width.  The workgroups are persistent: each takes learners from the ticket until none is left.
+// width.  The workgroups are persistent: each takes learners from the ticket until none is left.  cpw_rows_kernel
+// (kb_control_plus_wide.hip) is this kernel with the heavy learners' exit behind the head: a change here is made there too.
 template <int W>
 __global__ __launch_bounds__(256, 2) void control_plus_batch_kernel(CtlBatchArgs A) {
     __shared__ Lds sm;

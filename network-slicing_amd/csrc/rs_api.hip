@@ -1481,6 +1481,7 @@ extern "C" int rs_load_state(rs_handle* h, const void* blob, uint64_t bytes) {
 #include "kb_fit_steps.hip"
 #include "kb_control_plus.hip"
 #include "kb_control_plus_batch.hip"
+#include "kb_control_plus_wide.hip"
 #include "kb_fit_steps_batch.hip"
 #ifdef RS_DEV
 #include "rs_probe.hip"  // rs_dev_probe: the arithmetic primitives one by one (tests/test_gpu_primitives.py)

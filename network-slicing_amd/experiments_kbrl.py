@@ -64,10 +64,13 @@ class BatchedEvaluator(Evaluator):
     algorithm='projectron_plus': the agents learn by ProjectronPlus's margin rule in the closed loop (VecKBRL(...,
     algorithm='projectron_plus', control_plus=True)) -- no reference-shaped serial counterpart is run beside it.
     control_plus_batch = 2, 4 or 8 (with 'projectron_plus' only): that many candidates of a step share one pass over Kinv
-    (VecKBRL.set_control_plus_batch); the results are those of 0, bit for bit."""
+    (VecKBRL.set_control_plus_batch); the results are those of 0, bit for bit.
+    control_plus_wide = M (with a control_plus_batch width only): the learners that hold M landmarks or more have their passes
+    over Kinv spread over the chip (VecKBRL.set_control_plus_wide; up to min(2048, capacity) landmarks, and no further than the batch setting
+    groups); the same results again."""
 
     def __init__(self, scenario, a_range, steps=STEPS, out_dir='./results', prune_to=None, prune_every=None, algorithm='projectron',
-                 control_plus_batch=0):
+                 control_plus_batch=0, control_plus_wide=0):
         super().__init__(scenario, a_range, steps=steps, out_dir=out_dir)
         if algorithm not in ('projectron', 'projectron_plus'):
             raise ValueError("algorithm must be 'projectron' or 'projectron_plus', not %r" % (algorithm,))
@@ -75,6 +78,9 @@ class BatchedEvaluator(Evaluator):
         if control_plus_batch and algorithm != 'projectron_plus':
             raise ValueError("control_plus_batch groups the candidates of the 'projectron_plus' update phase: it needs that algorithm")
         self.control_plus_batch = int(control_plus_batch)
+        if control_plus_wide and not control_plus_batch:
+            raise ValueError('control_plus_wide spreads the passes of the grouped update phase: it needs a control_plus_batch width')
+        self.control_plus_wide = int(control_plus_wide)
         if (prune_to is None) != (not prune_every):
             raise ValueError('prune_to and prune_every go together')
         self.prune_to, self.prune_every = prune_to, prune_every
@@ -112,7 +118,9 @@ class BatchedEvaluator(Evaluator):
         dims = [len(sc.state_variables_embb)] * n_embb + [len(sc.state_variables_mmtc)] * n_mmtc
         agent = VecKBRL(n, dims, n_prbs, alfa=sc.alfa, accuracy_range=tuple(self.a_range), capacity=capacity,
                         device=device, pool_bytes=pool_bytes,
-                        **(dict(algorithm=self.algorithm, control_plus=True, control_plus_batch=self.control_plus_batch)
+                        **(dict(algorithm=self.algorithm, control_plus=True, control_plus_batch=self.control_plus_batch,
+                                control_plus_wide=self.control_plus_wide,
+                                control_plus_wide_max=min(2048, capacity // 64 * 64))
                            if self.algorithm != 'projectron' else {}))
         env.reset(seeds=env_seeds)
         agent.reset(ia, sf, seeds=ag_seeds)
@@ -260,7 +268,8 @@ class BatchedEvaluator(Evaluator):
 
 
 def evaluate_grid(cells, runs, steps=STEPS, out_dir='./results', device=0, capacity=16384, pool_bytes=16 << 30, verbose=False,
-                  graph=False, prune_to=None, prune_every=None, algorithm='projectron', control_plus_batch=0):
+                  graph=False, prune_to=None, prune_every=None, algorithm='projectron', control_plus_batch=0,
+                  control_plus_wide=0):
     """The reference's whole experiment (experiments_kbrl.py:57-70: every scenario x accuracy range x run) as ONE job on
     one GPU: a BatchedEvaluator per cell, each with its environment and agents on streams of their own, all advanced in
     the same host loop -- a cell of 30 runs leaves most of the chip idle (a handful of waves per kernel), so the cells'
@@ -269,11 +278,12 @@ def evaluate_grid(cells, runs, steps=STEPS, out_dir='./results', device=0, capac
     profiles/r04_w_grid_graph.txt -- while a single cell gains 5 % from the graph.)  Returns {(scenario, a_lo): [files]}, file
     for file what evaluate_all writes cell by cell (tests/test_gpu_kbrl.py::test_grid_of_cells_equals_cell_by_cell).
     prune_to / prune_every: budgeted dictionaries in every cell (BatchedEvaluator); algorithm, control_plus_batch: its update rule
-    and how many candidates share a pass over Kinv."""
+    and how many candidates share a pass over Kinv; control_plus_wide: from how many landmarks on a learner's passes are spread
+    over the chip."""
     evs = []
     for scenario, a_range in cells:
         ev = BatchedEvaluator(scenario, a_range, steps=steps, out_dir=out_dir, prune_to=prune_to, prune_every=prune_every,
-                              algorithm=algorithm, control_plus_batch=control_plus_batch)
+                              algorithm=algorithm, control_plus_batch=control_plus_batch, control_plus_wide=control_plus_wide)
         ev._setup(runs, device=device, capacity=capacity, pool_bytes=pool_bytes)
         evs.append(ev)
     for i in range(0, steps, CHUNK):
@@ -298,10 +308,15 @@ if __name__ == '__main__':
                     help='the update rule of the agents; projectron_plus turns the closed loop\'s margin-rule update phase on')
     ap.add_argument('--control-plus-batch', type=int, choices=[0, 2, 4, 8], default=0, metavar='W',
                     help='with --algorithm projectron_plus: W candidates of a step share one pass over Kinv (same results; 0: one by one)')
+    ap.add_argument('--control-plus-wide', type=int, default=0, metavar='M',
+                    help='with --control-plus-batch: learners of M landmarks or more have their passes over Kinv spread over the chip '
+                         '(same results; 0: every row on one workgroup)')
     args = ap.parse_args()
     cells = list(product(args.scenarios, accuracy_list))
     if args.control_plus_batch and args.algorithm != 'projectron_plus':
         ap.error('--control-plus-batch needs --algorithm projectron_plus')
+    if args.control_plus_wide and not args.control_plus_batch:
+        ap.error('--control-plus-wide needs --control-plus-batch')
     if args.serial and args.algorithm != 'projectron':
         ap.error('--serial runs the reference-shaped classes, whose agents are Projectron learners')
     if args.serial:
@@ -312,7 +327,7 @@ if __name__ == '__main__':
     elif args.cell_by_cell:
         for scenario, a_range in cells:
             BatchedEvaluator(scenario, a_range, steps=args.steps, out_dir=args.out, algorithm=args.algorithm,
-                             control_plus_batch=args.control_plus_batch).evaluate_all(range(args.runs))
+                             control_plus_batch=args.control_plus_batch, control_plus_wide=args.control_plus_wide).evaluate_all(range(args.runs))
     else:
         evaluate_grid(cells, range(args.runs), steps=args.steps, out_dir=args.out, verbose=True, algorithm=args.algorithm,
-                      control_plus_batch=args.control_plus_batch)
+                      control_plus_batch=args.control_plus_batch, control_plus_wide=args.control_plus_wide)

@@ -104,12 +104,15 @@ def _write_evaluation(h, scenario, a_range, runs, R, eval_steps, out_dir):
 
 
 def _evaluate_loaded(scenario, a_range, runs, R, eval_steps, out_dir, device, graph, verbose, by_reference, directory,
-                     learning_control=False, pool_bytes=32 << 30, algorithm='projectron', control_plus_batch=0):
+                     learning_control=False, pool_bytes=32 << 30, algorithm='projectron', control_plus_batch=0,
+                     control_plus_wide=0):
     """steps 2-4 of a cell whose agents come from their file: agent k of the file is trained run runs[k].  learning_control: the
     same agents loaded once more with learning left on (their Kinv rebuilt on the device), against the same fleet"""
     from ranslice import agent_file
     from ranslice.kbrl_dev import VecKBRL, fork_pool_bytes
     n = len(runs)
+    if control_plus_wide and not (control_plus_batch and algorithm == 'projectron_plus'):
+        raise ValueError('control_plus_wide needs a control_plus_batch width and the projectron_plus algorithm')
     t1 = time.perf_counter()
     with open(agents_path(directory, scenario, a_range), 'rb') as f:
         blob = f.read()
@@ -131,6 +134,8 @@ def _evaluate_loaded(scenario, a_range, runs, R, eval_steps, out_dir, device, gr
             control.set_algorithm(algorithm)
             control.set_control_plus(True)
             control.set_control_plus_batch(control_plus_batch)
+            if control_plus_wide:
+                control.set_control_plus_wide(control_plus_wide, min(2048, control.capacity // 64 * 64))
         rebuilt = control.rebuild_stats()
         hc = _fleet_run(control, scenario, n * R, eval_steps, device, graph)
         shape = (n, R, eval_steps)
@@ -159,7 +164,7 @@ def _evaluate_loaded(scenario, a_range, runs, R, eval_steps, out_dir, device, gr
 def train_and_deploy(scenario, a_range, runs=range(RUNS), train_steps=TRAIN_STEPS, eval_replicas=EVAL_REPLICAS, eval_steps=EVAL_STEPS,
                      out_dir='./results', device=0, capacity=16384, pool_bytes=32 << 30, graph=GRAPH, verbose=True,
                      learning_control=False, by_reference=False, save_agents=None, load_agents=None, algorithm='projectron',
-                     control_plus_batch=0):
+                     control_plus_batch=0, control_plus_wide=0):
     """one (scenario, accuracy range): writes the evaluation files and returns a summary with both pairs of numbers.
     learning_control: also run FULL forks of the same agents, learning left on, against the same fresh fleet -- what separates
     "the agent is frozen" from "the environment is new" in the difference between the two pairs (summary['learning_control'];
@@ -171,7 +176,9 @@ def train_and_deploy(scenario, a_range, runs=range(RUNS), train_steps=TRAIN_STEP
     would).
     algorithm='projectron_plus': the agents train, and the learning_control leg goes on learning, by ProjectronPlus's margin rule
     in the closed loop (VecKBRL.set_control_plus); the deployed leg only selects and is indifferent to it.
-    control_plus_batch = 2, 4 or 8: in that mode that many candidates of a step share one pass over Kinv (same results)."""
+    control_plus_batch = 2, 4 or 8: in that mode that many candidates of a step share one pass over Kinv (same results).
+    control_plus_wide = M (with a control_plus_batch width): learners of M landmarks or more have their passes over Kinv spread over
+    the chip (same results)."""
     from ranslice.kbrl_dev import VecKBRL, fork_pool_bytes
     runs = list(runs)
     n, R = len(runs), int(eval_replicas)
@@ -179,10 +186,13 @@ def train_and_deploy(scenario, a_range, runs=range(RUNS), train_steps=TRAIN_STEP
     if load_agents is not None:
         return _evaluate_loaded(scenario, a_range, runs, R, eval_steps, out_dir, device, graph, verbose, by_reference, load_agents,
                                 learning_control=learning_control, pool_bytes=pool_bytes, algorithm=algorithm,
-                                control_plus_batch=control_plus_batch)
+                                control_plus_batch=control_plus_batch, control_plus_wide=control_plus_wide)
+    if control_plus_wide and not (control_plus_batch and algorithm == 'projectron_plus'):
+        raise ValueError('control_plus_wide needs a control_plus_batch width and the projectron_plus algorithm')
     t0 = time.perf_counter()
     ev = BatchedEvaluator(scenario, a_range, steps=train_steps, out_dir=out_dir, algorithm=algorithm,
-                          control_plus_batch=control_plus_batch if algorithm == 'projectron_plus' else 0)
+                          control_plus_batch=control_plus_batch if algorithm == 'projectron_plus' else 0,
+                          control_plus_wide=control_plus_wide if algorithm == 'projectron_plus' else 0)
     agent, env = ev.train(runs, device=device, capacity=capacity, pool_bytes=pool_bytes, graph=graph)
     hist = agent.history_fetch()
     assert hist['recorded'] == train_steps
@@ -204,7 +214,8 @@ def train_and_deploy(scenario, a_range, runs=range(RUNS), train_steps=TRAIN_STEP
     if learning_control:
         control = VecKBRL(n * R, agent.dims, agent.n_prbs, alfa=sc.alfa, accuracy_range=tuple(a_range), capacity=capacity,
                           device=device, pool_bytes=fork_pool_bytes(sizes[index]) + pool_bytes,
-                          **(dict(algorithm=algorithm, control_plus=True, control_plus_batch=control_plus_batch)
+                          **(dict(algorithm=algorithm, control_plus=True, control_plus_batch=control_plus_batch,
+                                  control_plus_wide=control_plus_wide, control_plus_wide_max=min(2048, capacity // 64 * 64))
                              if algorithm != 'projectron' else {}))
         control.fork_from(agent, index)
         control.synchronize()
@@ -256,13 +267,19 @@ if __name__ == '__main__':
                     help='the update rule of the agents; projectron_plus turns the closed loop\'s margin-rule update phase on')
     ap.add_argument('--control-plus-batch', type=int, choices=[0, 2, 4, 8], default=0, metavar='W',
                     help='with --algorithm projectron_plus: W candidates of a step share one pass over Kinv (same results; 0: one by one)')
+    ap.add_argument('--control-plus-wide', type=int, default=0, metavar='M',
+                    help='with --control-plus-batch: learners of M landmarks or more have their passes over Kinv spread over the chip '
+                         '(same results; 0: every row on one workgroup)')
     args = ap.parse_args()
     if args.control_plus_batch and args.algorithm != 'projectron_plus':
         ap.error('--control-plus-batch needs --algorithm projectron_plus')
+    if args.control_plus_wide and not args.control_plus_batch:
+        ap.error('--control-plus-wide needs --control-plus-batch')
     if args.load_agents and args.save_agents:
         ap.error('--load-agents evaluates agents from their files: it neither trains nor saves')
     for scenario, a_range in product(args.scenarios, accuracy_list):
         train_and_deploy(scenario, a_range, range(args.runs), train_steps=args.train_steps, eval_replicas=args.eval_replicas,
                          eval_steps=args.eval_steps, out_dir=args.out, learning_control=args.learning_control,
                          by_reference=args.by_reference, save_agents=args.save_agents, load_agents=args.load_agents,
-                         algorithm=args.algorithm, control_plus_batch=args.control_plus_batch)
+                         algorithm=args.algorithm, control_plus_batch=args.control_plus_batch,
+                         control_plus_wide=args.control_plus_wide)

@@ -31,6 +31,7 @@ KB_EXPORTS = (
     'kb_fit_steps',
     'kb_set_control_plus', 'kb_get_control_plus',
     'kb_set_control_plus_batch', 'kb_get_control_plus_batch', 'kb_control_plus_batch_info',
+    'kb_set_control_plus_wide', 'kb_get_control_plus_wide', 'kb_control_plus_wide_info',
     'kb_set_fit_steps_batch', 'kb_get_fit_steps_batch', 'kb_fit_steps_batch_info',
 )
 
@@ -231,6 +232,9 @@ def load(dev=None):
     L.kb_set_control_plus_batch.argtypes = [vp, C.c_int32, C.c_int32]
     L.kb_get_control_plus_batch.argtypes = [vp, ip, ip, up]
     L.kb_control_plus_batch_info.argtypes = [vp, up]
+    L.kb_set_control_plus_wide.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+    L.kb_get_control_plus_wide.argtypes = [vp, ip, ip, ip, up]
+    L.kb_control_plus_wide_info.argtypes = [vp, up]
     L.kb_set_fit_steps_batch.argtypes = [vp, C.c_int32, C.c_int32]
     L.kb_get_fit_steps_batch.argtypes = [vp, ip, ip, up]
     L.kb_fit_steps_batch_info.argtypes = [vp, up]

@@ -94,7 +94,8 @@ class VecKBRL:
 
     def __init__(self, n_envs, dims, n_prbs, alfa=KBRL_ALFA, accuracy_range=(0.99, 0.999), gamma=KBRL_GAMMA,
                  eta=KBRL_ETA, capacity=4096, device=0, shared=False, first_env=0, pool_bytes=0, algorithm='projectron',
-                 control_plus=False, control_plus_batch=0, control_plus_batch_max=1024, fit_steps_batch=0, fit_steps_batch_max=1024):
+                 control_plus=False, control_plus_batch=0, control_plus_batch_max=1024, fit_steps_batch=0, fit_steps_batch_max=1024,
+                 control_plus_wide=0, control_plus_wide_max=2048, control_plus_wide_rounds=32):
         if algorithm not in ALGORITHMS:
             raise ValueError('algorithm must be one of %s, not %r' % (sorted(ALGORITHMS), algorithm))
         self.L = _lib.load()
@@ -121,6 +122,8 @@ class VecKBRL:
             self.set_control_plus_batch(control_plus_batch, control_plus_batch_max)
         if fit_steps_batch:
             self.set_fit_steps_batch(fit_steps_batch, fit_steps_batch_max)
+        if control_plus_wide:
+            self.set_control_plus_wide(control_plus_wide, control_plus_wide_max, control_plus_wide_rounds)
 
     def set_algorithm(self, algorithm):
         """the update rule of the next update() / fit() (kb_set_algorithm): 'projectron' (the default; projectron.py:39-60) or
@@ -428,6 +431,33 @@ class VecKBRL:
         the ones that ran the mat-vec"""
         w = (C.c_uint64 * 8)()
         self._check(self.L.kb_control_plus_batch_info(self.h, w))
+        return [int(v) for v in w]
+
+    def set_control_plus_wide(self, min_landmarks, max_landmarks=2048, rounds=32):
+        """which learners of the closed loop's 'projectron_plus' update phase have their passes over Kinv spread over the chip
+        (kb_set_control_plus_wide): 0 (the default) none -- every row on one workgroup, as set_control_plus_batch leaves it -- else
+        those that hold min_landmarks (2 or more) .. max_landmarks (a multiple of 64, 64 .. capacity) at the start of a step, in task
+        order the first 1024 of them -- and no more than set_control_plus_batch's max_landmarks, beyond which that walk goes one by one.  They advance in `rounds` (1 .. 256) rounds of chip-wide launches -- the pass of a group of
+        candidates, the walk of its members, the rank-1 update of an insertion -- and a finishing launch completes what is left,
+        so the results do not depend on `rounds`: bit for bit those of the same width with this switch off.  It has an effect only
+        in 'projectron_plus' mode with set_control_plus on and a set_control_plus_batch width of 2, 4 or 8.  The scratch (a record
+        and an arena of 2 x 8 x max_landmarks doubles per slot) is allocated here and freed at 0.  A property of this handle: not
+        saved, not carried over.  Refused (RS_ESTATE) on deployed, by-reference and shared-dictionary handles."""
+        self._check(self.L.kb_set_control_plus_wide(self.h, int(min_landmarks), int(max_landmarks), int(rounds)))
+
+    @property
+    def control_plus_wide(self):
+        """(min_landmarks, max_landmarks, rounds, scratch_bytes) of set_control_plus_wide (kb_get_control_plus_wide); zeros while off"""
+        a, b, r, n = C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint64()
+        self._check(self.L.kb_get_control_plus_wide(self.h, C.byref(a), C.byref(b), C.byref(r), C.byref(n)))
+        return a.value, b.value, r.value, n.value
+
+    def control_plus_wide_work(self):
+        """kb_control_plus_wide_info since the switch was last set: heavy rows taken, learners turned away because the slots were
+        full, learner-rounds that made a spread pass, tiles read in them, rank-1 units spread, rows that reached the finisher
+        unfinished, candidates the finisher walked, update phases launched in this mode"""
+        w = (C.c_uint64 * 8)()
+        self._check(self.L.kb_control_plus_wide_info(self.h, w))
         return [int(v) for v in w]
 
     def set_fit_steps_batch(self, width, max_landmarks=1024):
@@ -858,6 +888,10 @@ class SharedVecKBRL(VecKBRL):
     def set_control_plus_batch(self, width, max_landmarks=1024):
         """refused, as kb_set_control_plus_batch refuses it"""
         raise _lib.RanSliceError(_lib.RS_ESTATE, 'set_control_plus_batch: a shared-dictionary handle does not learn through update_control')
+
+    def set_control_plus_wide(self, min_landmarks, max_landmarks=2048, rounds=32):
+        """refused, as kb_set_control_plus_wide refuses it"""
+        raise _lib.RanSliceError(_lib.RS_ESTATE, 'set_control_plus_wide: a shared-dictionary handle does not learn through update_control')
 
     def set_fit_steps_batch(self, width, max_landmarks=1024):
         """refused, as kb_set_fit_steps_batch refuses it"""

@@ -51,6 +51,15 @@ CTL_BATCH = {'control_plus_batch_kernelILi2E': (209, 19968, 0), 'control_plus_ba
 # learner loop the kernel showed 124 B at width 4 and 372 B at width 8; it is one loop, a row per trip, for that reason.)
 FIT_STEPS_BATCH = {'fit_steps_batch_kernelILi2E': (209, 19968, 0), 'fit_steps_batch_kernelILi4E': (249, 28240, 0),
                    'fit_steps_batch_kernelILi8E': (256, 44784, 204)}
+# the same update phase with the large learners' passes spread over the chip (kb_control_plus_wide.hip): scratch
+# bytes per lane.  The two kernels that stream Kinv (the pass, per width, and the rank-1 update), the list and the plan hold none;
+# the walk holds none either; the rows kernel (the batch kernel's row, with the heavy learners' early exit) and the finisher (its
+# walk from a cursor) are held to what the build shows at two waves per SIMD, below the 240 B line
+CTL_WIDE = {'cpw_list_kernel': 0, 'cpw_plan_kernel': 0, 'cpw_rank1_kernel': 0,
+            'cpw_pass_kernelILi2E': 0, 'cpw_pass_kernelILi4E': 0, 'cpw_pass_kernelILi8E': 0,
+            'cpw_walk_kernelILi2E': 0, 'cpw_walk_kernelILi4E': 0, 'cpw_walk_kernelILi8E': 0,
+            'cpw_rows_kernelILi2E': 0, 'cpw_rows_kernelILi4E': 0, 'cpw_rows_kernelILi8E': 220,
+            'cpw_finish_kernelILi2E': 0, 'cpw_finish_kernelILi4E': 0, 'cpw_finish_kernelILi8E': 116}
 PRODUCTION = ["embb_step_kernelILi16ELb0ELb0ELb1E", "embb_step_kernelILi16ELb0ELb1ELb1E"]   # <16, false, plain | BLOCK, FDIV>
 PLAIN = PRODUCTION[0]          # the instance bench.py's headline runs
 STEP_KERNEL = 'embb_step_kernelIL'
@@ -181,6 +190,16 @@ def check(path=LOG):
         if r.get('LDS Size', 0) > lds:
             bad.append('%s uses %d B of LDS (> %d)' % (key, r['LDS Size'], lds))
         if r.get('ScratchSize', 0) > scratch:
+            bad.append('%s spills %d B/lane (> %d)' % (key, r['ScratchSize'], scratch))
+    for key, scratch in CTL_WIDE.items():
+        hit = [k for k in res if re.search(r'\d' + key, k)]
+        if not hit:
+            bad.append('%s: not found in %s' % (key, path))
+            continue
+        r = res[hit[0]]
+        print('%s: VGPRs %s + AGPRs %s, scratch %s B/lane, occupancy %s, LDS %s B' % (key, r.get('VGPRs'), r.get('AGPRs'), r.get('ScratchSize'),
+                                                                                      r.get('Occupancy'), r.get('LDS Size')))
+        if r.get('ScratchSize', 0) > min(scratch, LIMIT):
             bad.append('%s spills %d B/lane (> %d)' % (key, r['ScratchSize'], scratch))
     return bad
 

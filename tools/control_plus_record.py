@@ -18,6 +18,13 @@ width, widths 0 and W alternating, and the window is timed on the fork -- same d
 widths (their results are equal bit for bit, so either may carry the run between the points: W does).  Per point: the update
 phase's ms per step as median and range over the rounds, kb_control_plus_batch_info's work[0..7] per step, and the largest
 learner's share at both widths.  --also 2 4 adds one round each at further widths, for the curve.
+
+--batch W --wide M measures kb_set_control_plus_wide instead and writes profiles/control_plus_wide_record.json: the
+fleet runs at width W; at each point it is forked and the window is timed on the fork with the switch off and on (min_landmarks
+M, --wide-rounds rounds), alternating, --rounds times each -- the update phase's ms per step as median (min - max) -- and so is
+the replica with the largest dictionary alone on a one-replica handle.  --wide-also 512 1024 adds further M at the last point
+(--wide-also-rounds rounds each, 1 by default); --cell 30 repeats the last point on a fleet of that many replicas (the reference's cell: 30 runs x 5 learners).
+Where no learner reaches M the on-figure is the price of the empty rounds.
 """
 import argparse
 import json
@@ -195,6 +202,94 @@ def _batch_leg(width, also, rounds, n, at, window, capacity, pool_bytes, seed, m
     return dict(windows=out, flagged=sum(len(v) for v in flags.values()))
 
 
+def _wide_leg(width, wide, wide_also, also_rounds, wide_rounds, rounds, n, at, window, capacity, pool_bytes, seed, max_landmarks):
+    """the fleet at width `width`; per point the fork's window with the wide switch off (0) and on (`wide`), alternating"""
+    import ctypes as C
+    import statistics
+    import numpy as np
+    from ranslice.config import make_config
+    from ranslice.kbrl_dev import VecKBRL
+    from ranslice.vec_env import VecRanSlice, default_fading
+    cfg = make_config(0, n_envs=n)
+    dims, n_prbs = [10] * cfg.n_embb + [3] * cfg.n_mmtc, cfg.n_prbs
+
+    def pair(k, pool):
+        return (VecRanSlice(n_envs=k, cfg=make_config(0, n_envs=k), fading=default_fading(), seed=seed),
+                VecKBRL(k, dims, n_prbs, capacity=capacity, pool_bytes=pool, algorithm='projectron_plus', control_plus=True,
+                        control_plus_batch=width, control_plus_batch_max=max_landmarks))
+    env, ag = pair(n, pool_bytes)
+    fenv, fag = pair(n, pool_bytes)        # the fork the windows are timed on
+    oenv, one = pair(1, 1 << 30)           # the replica with the largest dictionary, alone
+    ia = np.full((n, len(dims)), n_prbs // (2 * len(dims)), dtype=np.int32)
+    for e in (env, fenv, oenv):
+        e.reset()
+    ag.reset(ia, np.full((n, len(dims)), 3, dtype=np.int32))
+    env._check(env.L.rs_step(env.h, ia.ctypes.data_as(C.POINTER(C.c_int32)), None, None, None, None))
+    everyone = np.arange(n, dtype=np.int32)
+
+    def timed(a, e, m):
+        a.set_control_plus_batch(width, max_landmarks)      # (restarts the counters)
+        a.set_control_plus_wide(m, max_landmarks, wide_rounds)
+        a.set_kernel_timing(True)
+        a.phase_times_ms()
+        a.run_resident(e, window, graph=False)
+        a.synchronize()
+        ms = a.phase_times_ms()['update_ms']
+        a.set_kernel_timing(False)
+        return ms, [v / window for v in a.control_plus_wide_work()], [v / window for v in a.control_plus_batch_work()]
+
+    def summary(v):
+        return dict(median=statistics.median(v), min=min(v), max=max(v), runs=v)
+
+    out, step = [], 0
+    for i, a_ in enumerate(at):
+        first = max(step, a_ - window // 2)
+        t0 = time.perf_counter()
+        while step < first:      # (in stretches, with a sign of life between them)
+            k = min(250, first - step)
+            ag.run_resident(env, k, graph=False)
+            ag.synchronize()
+            step += k
+            print('%d replicas: step %d, %.1f s' % (n, step, time.perf_counter() - t0), file=sys.stderr, flush=True)
+        sizes = ag.dictionary_sizes()
+        worst = int(np.argmax(sizes.max(axis=1)))
+        plan = [(m, r) for r in range(rounds) for m in (0, wide)] + ([(m, r) for r in range(also_rounds) for m in wide_also] if i == len(at) - 1 else [])
+        ms, wwork, bwork, alone = {}, {}, {}, {}
+        for m, _ in plan:
+            fag.fork_from(ag, everyone)
+            fenv.fork_from(env, everyone)
+            t, ww, bw = timed(fag, fenv, m)
+            ms.setdefault(m, []).append(t)
+            wwork[m], bwork[m] = ww, bw
+        for m, _ in plan:
+            one.fork_from(ag, [worst])
+            oenv.fork_from(env, [worst])
+            alone.setdefault(m, []).append(timed(one, oenv, m)[0])
+        rec = dict(steps=[first, first + window], landmarks_mean=float(sizes.mean()), landmarks_max=int(sizes.max()),
+                   learners_at_or_above={str(m): int((sizes >= m).sum()) for m in [wide] + list(wide_also)},
+                   largest_replica=dict(replica=worst, landmarks=sizes[worst].tolist()),
+                   min_landmarks={str(m): dict(update_ms_per_step=summary(v), wide_work_per_step=wwork[m], batch_work_per_step=bwork[m],
+                                               largest_replica_alone_update_ms_per_step=summary(alone[m]))
+                                  for m, v in ms.items()})
+        out.append(rec)
+        print(json.dumps(rec), flush=True)
+        ag.run_resident(env, window, graph=False)
+        step += window
+    flags = ag.flagged_replicas()
+    for h in (env, ag, fenv, fag, oenv, one):
+        h.close()
+    return dict(windows=out, flagged=sum(len(v) for v in flags.values()))
+
+
+def _wide_resources():
+    import check_resources as cr
+    if not os.path.exists(cr.LOG):
+        return None
+    return {k: dict(vgprs=r.get('VGPRs'), agprs=r.get('AGPRs'), scratch_bytes_per_lane=r.get('ScratchSize'), occupancy=r.get('Occupancy'),
+                    lds_bytes=r.get('LDS Size'))
+            for k, r in cr.parse().items() if 'cpw_' in k or 'control_plus_batch_kernel' in k}
+
+
 def _batch_resources():
     import check_resources as cr
     if not os.path.exists(cr.LOG):
@@ -214,6 +309,13 @@ def main():
                     help='measure kb_set_control_plus_batch at this width against width 0 (writes profiles/control_plus_batch_record.json)')
     ap.add_argument('--also', type=int, nargs='*', default=[], help='with --batch: further widths, one round each')
     ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--wide', type=int, default=0, metavar='M',
+                    help='with --batch: measure kb_set_control_plus_wide at min_landmarks M against the switch off (writes '
+                         'profiles/control_plus_wide_record.json)')
+    ap.add_argument('--wide-also', type=int, nargs='*', default=[], help='with --wide: further M at the last point')
+    ap.add_argument('--wide-also-rounds', type=int, default=1, help='with --wide-also: rounds of each further M')
+    ap.add_argument('--wide-rounds', type=int, default=32, help='with --wide: the rounds enqueued per update phase')
+    ap.add_argument('--cell', type=int, default=0, help='with --wide: repeat the last point on a fleet of this many replicas')
     ap.add_argument('--max-landmarks', type=int, default=2048)
     ap.add_argument('--replicas', type=int, default=4096)
     ap.add_argument('--at', type=int, nargs='*', default=[50, 500, 2000])
@@ -223,6 +325,30 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'control_plus_record.json'))
     args = ap.parse_args()
+    if args.wide and not args.batch:
+        ap.error('--wide needs --batch')
+    if args.wide:
+        out = args.out if args.out != ap.get_default('out') else os.path.join(ROOT, 'profiles', 'control_plus_wide_record.json')
+        rec = dict(what='closed control loop in Projectron++ mode at batch width %d, scenario 0, %d replicas on one device: '
+                        'kb_set_control_plus_wide at min_landmarks %d (%d rounds) against the switch off on forks of the same fleet, %d '
+                        'rounds each alternating; plain launches, kernel timing on for %d steps per window; no threshold attached'
+                        % (args.batch, args.replicas, args.wide, args.wide_rounds, args.rounds, args.window),
+                   replicas=args.replicas, window=args.window, width=args.batch, rounds=args.rounds, max_landmarks=args.max_landmarks,
+                   min_landmarks=args.wide, wide_rounds=args.wide_rounds, wide_also=args.wide_also, wide_also_rounds=args.wide_also_rounds,
+                   kernels=_wide_resources())
+        pool = int(args.pool_gb * (1 << 30))
+        at = sorted(args.at)
+        rec['fleet'] = _wide_leg(args.batch, args.wide, args.wide_also, args.wide_also_rounds, args.wide_rounds, args.rounds, args.replicas, at, args.window,
+                                 args.capacity, pool, args.seed, args.max_landmarks)
+        if args.cell:
+            rec['cell'] = dict(replicas=args.cell, **_wide_leg(args.batch, args.wide, args.wide_also, args.wide_also_rounds, args.wide_rounds, args.rounds, args.cell,
+                                                               at[-1:], args.window, args.capacity, min(pool, 8 << 30), args.seed,
+                                                               args.max_landmarks))
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, 'w') as fh:
+            json.dump(rec, fh, indent=1, sort_keys=True)
+            fh.write('\n')
+        return
     if args.batch:
         out = args.out if args.out != ap.get_default('out') else os.path.join(ROOT, 'profiles', 'control_plus_batch_record.json')
         rec = dict(what='closed control loop in Projectron++ mode, scenario 0, %d replicas on one device: kb_set_control_plus_batch at '
