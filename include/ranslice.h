@@ -639,7 +639,7 @@ int kb_set_learning(kb_handle* k, int on);
  * RS_ESTATE until a new kb_predict); the float32 mark, the control state, the tie-break stream and the flag word stay (bit
  * 16 is sticky).  Shells are kept: growing back to the old size allocates nothing, and kb_get_pool reports the same bytes in
  * use.  Ordered on the agent's stream, between kb_run_resident calls (never captured); the host waits for it.
- * RS_EINVAL: target < 64 or target > capacity.  RS_ESTATE: a shared-dictionary handle, an inference-only handle, kb_reset
+ * RS_EINVAL: target < 64 or target > capacity.  RS_ESTATE: a shared-dictionary handle (kb_shared_prune), an inference-only handle, kb_reset
  * missing, or dictionaries with a diagonal entry of Kinv that is not finite and positive -- those are left as they are (the
  * others are pruned; kb_last_error counts them).
  * kb_get_pruned: landmarks removed per dictionary [n_envs][S] since kb_reset / kb_load_state / kb_fork into the handle (the
@@ -653,6 +653,24 @@ int kb_prune(kb_handle* k, int32_t target, uint64_t* removed_total);
 int kb_get_pruned(kb_handle* k, int64_t* removed /* [n_dictionaries] since kb_reset */);
 int kb_prune_time_ms(kb_handle* k, double ms[3], int64_t n[3]);   /* choose, downdate, move: HIP events, when kernel timing is on */
 int kb_get_prune_work(kb_handle* k, uint64_t work[2]);
+/* Budgeted SHARED dictionaries.  kb_shared_prune is kb_prune on a shared-dictionary handle
+ * (kb_config.shared_dictionary = 1): each of its S dictionaries that holds more than `target` landmarks is left with exactly
+ * `target`, by kb_prune's rule to the letter -- the same victim, the same expressions in the same operation order, nothing
+ * summed -- on the storage the handle has: both block triangles of Kinv are downdated in place, the upper one staying the
+ * exact transpose of the lower.  One dictionary comes out, bit for bit, as kb_prune leaves its unshared copy (kb_unshare):
+ * landmarks, slots, coefficients and the lower triangle.  Per touched dictionary afterwards: heads and chain links rebuilt, the
+ * off-grid count recounted (a dictionary whose last off-grid landmark left is scored on the wide path again), the version
+ * bumped, and the cache of the last kb_predict invalidated for EVERY replica of the slice.  Everything the shared mode
+ * derives from a dictionary (the scoring operands and products, the proposal cursors) is rebuilt by the next step, as after
+ * kb_share.  Control state, tie-break streams, flag words and shells stay (kb_get_pool reports the same bytes before, after,
+ * and after growing back); the communicator is not touched.  Nothing in the call depends on the rank: ranks that call it with
+ * the same target at the same step keep bit-identical dictionaries with no collective.  Ordered on the agent's stream, never
+ * captured; the host waits twice, as kb_prune does.  kb_get_pruned ([S] entries), kb_prune_time_ms and kb_get_prune_work
+ * report it as they report kb_prune (here a dictionary's work line is its whole block square: twice the triangle's units).
+ * RS_EINVAL: target < 64 or target > capacity.  RS_ESTATE: a handle that is not shared-dictionary (kb_prune is the call
+ * there), kb_reset missing, a round open between kb_shared_scan and kb_shared_commit, or dictionaries with a diagonal entry of
+ * Kinv that is not finite and positive -- those are left as they are, the others are pruned.  The handle stays usable. */
+int kb_shared_prune(kb_handle* k, int32_t target, uint64_t* removed_total);
 /* ---- the learner's own surface, batched (csrc/kb_fit.hip): sample sequences in, trained learners out; query
  * sets in, scores out.  Build-defined: the reference has Projectron.predict(x) / update(x, y), one sample per call.
  *

@@ -1,5 +1,6 @@
 // kb_prune.hip -- budgeted dictionaries: kb_prune removes landmarks with an exact downdate of Kinv.
 // #included by rs_api.hip after kb_fork.hip: it uses the agent handle and changes none of its kernels.
+// Shared handles: kb_shared_prune (kb_shared_prune.hip), the same rule on the storage that keeps both triangles of Kinv.
 //
 // The rule.  Write P = Kinv of the live landmarks, c their coefficients.  While a dictionary holds more than `target`
 // landmarks, one landmark leaves:

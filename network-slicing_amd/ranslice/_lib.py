@@ -20,6 +20,7 @@ KB_EXPORTS = (
     'kb_comm_info', 'kb_get_stats', 'kb_get_sizes', 'kb_get_pool', 'kb_state_bytes', 'kb_save_state', 'kb_load_state', 'kb_get_flags', 'kb_get_repair_work', 'kb_get_kernel_row', 'kb_shared_scan', 'kb_shared_apply', 'kb_shared_commit', 'kb_comm_unique_id', 'kb_comm_init', 'kb_shared_step', 'kb_shared_step_resident', 'kb_shared_merge', 'kb_history_begin', 'kb_history_fetch', 'kb_kernel_time_ms', 'kb_phase_times_ms', 'kb_repair_times_ms', 'kb_kernel_times_ms', 'kb_set_kernel_timing', 'kb_synchronize',
     'kb_fork', 'kb_deploy', 'kb_set_learning',
     'kb_prune', 'kb_get_pruned', 'kb_prune_time_ms', 'kb_get_prune_work',
+    'kb_shared_prune',
     'kb_deploy_ref',
     'kb_export_bytes', 'kb_export_agents', 'kb_agents_info', 'kb_import_agents', 'kb_agents_kernel_times',
     'kb_fork_rebuild', 'kb_get_rebuild', 'kb_rebuild_time_ms',
@@ -213,6 +214,7 @@ def load(dev=None):
     L.kb_share.argtypes = [vp, vp, C.c_int32, ip]
     L.kb_bridge_time_ms.argtypes = [vp, dp, up]
     L.kb_prune.argtypes = [vp, C.c_int32, up]
+    L.kb_shared_prune.argtypes = [vp, C.c_int32, up]
     L.kb_get_pruned.argtypes = [vp, i64p]
     L.kb_prune_time_ms.argtypes = [vp, dp, i64p]
     L.kb_get_prune_work.argtypes = [vp, up]

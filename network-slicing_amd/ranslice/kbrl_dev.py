@@ -958,6 +958,16 @@ class SharedVecKBRL(VecKBRL):
             raise
         return ag
 
+    def shrink(self, target):
+        """every shared dictionary above `target` landmarks is brought down to exactly `target` (kb_shared_prune): VecKBRL.prune's
+        rule on this handle's own storage, in place -- one dictionary comes out bit for bit as prune() leaves its to_agents() copy.
+        Control state, shells (pool()['used_bytes']) and the communicator stay; ranks that call it with the same target at the
+        same step keep identical dictionaries.  Call it between steps, never inside a host-driven round.  pruned() and
+        prune_times_ms() report it.  (prune() itself keeps refusing a shared handle.)  -> landmarks removed by the call"""
+        n = C.c_uint64()
+        self._check(self.L.kb_shared_prune(self.h, int(target), C.byref(n)))
+        return int(n.value)
+
     def step_resident(self, env, count_rounds=False):
         """one closed-loop agent step on the device: the shared learning step on the simulator's buffers, then
         select_action into them (kb_shared_step_resident).  count_rounds: wait for the number of exchange rounds

@@ -14,6 +14,9 @@ KB_SCRATCH = {'update_small_kernel': 64, 'update_heavy_kernel': 16, 'update_cont
               'heavy_matvec_kernel': 0, 'heavy_rank1_kernel': 0, 'select_bin_kernel': 16, 'select_bin_big_kernel': 16, 'select_gemm_kernel': 0}
 # kb_prune's kernels (kb_prune.hip): reported, and held to no scratch at all -- the downdate is a pure streaming kernel
 PRUNE = ['prune_list_kernel', 'prune_choose_kernel', 'prune_plan_kernel', 'prune_downdate_kernel', 'prune_move_kernel', 'prune_finish_kernel']
+# kb_shared_prune's kernels (kb_shared_prune.hip): the same rule on full storage, reported beside them and held to no scratch as well
+PRUNE_SHARED = ['prune_shared_choose_kernel', 'prune_shared_plan_kernel', 'prune_shared_downdate_kernel', 'prune_shared_move_kernel',
+                'prune_shared_finish_kernel']
 # kb_deploy_ref's kernels (kb_ref.hip): reported, and held to no scratch at all, as they are built and documented
 REF_SCRATCH = {'select_ref_kernel': 0, 'ref_gather_kernel': 0}
 # the agent-file kernels (kb_agents.hip): reported, and held to no scratch at all -- pack and build are pure streaming kernels
@@ -137,7 +140,7 @@ def check(path=LOG):
             bad.append('%s: not found in %s' % (key, path))
         elif res[hit[0]].get('ScratchSize', 0) > limit:
             bad.append('%s spills %d B/lane (> %d)' % (key, res[hit[0]]['ScratchSize'], limit))
-    for key in PRUNE:
+    for key in PRUNE + PRUNE_SHARED:
         hit = [k for k in res if key in k]
         if not hit:
             bad.append('%s: not found in %s' % (key, path))
