@@ -381,7 +381,9 @@ int kb_shared_commit(kb_handle* k, const int32_t* n_accept);
  * (rounds_out).  Only a 4-byte "anything left" flag per round returns to the host.  kb_comm_unique_id: 128 bytes
  * from ncclGetUniqueId, generated by ONE rank and handed to the others by the launcher; kb_comm_init joins the
  * communicator (rank = the handle's index among the `world` agents that share their dictionaries; kb_config.first_env
- * must be rank * n_envs).  Without kb_comm_init the handle is its own world (no RCCL needed). */
+ * must be rank * n_envs).  Without kb_comm_init the handle is its own world (no RCCL needed).
+ * Every rank of a group must have set the same kb_set_shared_plus value (below) before the same step: the rule the merged
+ * list is applied by is host state of each handle and nothing checks it across ranks. */
 int kb_comm_unique_id(void* id128);
 int kb_comm_init(kb_handle* k, const void* id128, int rank, int world);
 /* What the live communicator itself reports (ncclCommUserRank / ncclCommCount); (0, 1) for a handle that never joined one.
@@ -426,7 +428,7 @@ int kb_get_flags(kb_handle* k, int32_t* flags);
  * evaluated landmarks' exponentials one by one (outlier states, off-grid landmarks), work[5] the landmarks they evaluated --
  * both counted by developer builds only (-DKB_COUNT_DIRECT), 0 otherwise; work[6] the samples that ran the mat-vec in the closed
  * loop's Projectron++ mode (kb_set_control_plus: branches 1-4 of its candidates) -- that mode queues no repair, so work[0..3] stay
- * as they are while it runs */
+ * as they are while it runs; on a shared-dictionary handle under kb_set_shared_plus the proposals whose branch was 1-4 */
 int kb_get_repair_work(kb_handle* k, uint64_t work[8]);
 int kb_kernel_time_ms(kb_handle* k, double* avg_ms, int64_t* launches);
 /* the same per phase: ms[0] / n[0] the update phase (update_control_kernel and its repair kernels; shared mode: the scan
@@ -729,6 +731,7 @@ int kb_fit_time_ms(kb_handle* k, double ms[2], uint64_t work[4]);
 #define KB_ALG_PROJECTRON 0
 #define KB_ALG_PROJECTRON_PLUS 1
 int kb_set_algorithm(kb_handle* k, int32_t alg);
+/* (on a shared-dictionary handle always KB_ALG_PROJECTRON: not the rule its rounds learn by, which kb_get_shared_plus reports) */
 int kb_get_algorithm(kb_handle* k, int32_t* alg);
 
 /* ---- kb_fit for learners that hold large dictionaries: chip-wide rounds (csrc/kb_fit_wide.hip).  kb_fit teaches
@@ -909,6 +912,35 @@ int kb_control_plus_wide_info(kb_handle* k, uint64_t work[8]);
 int kb_set_fit_steps_batch(kb_handle* k, int32_t width, int32_t max_landmarks);
 int kb_get_fit_steps_batch(kb_handle* k, int32_t* width, int32_t* max_landmarks, uint64_t* scratch_bytes);
 int kb_fit_steps_batch_info(kb_handle* k, uint64_t work[8]);   /* of the last kb_fit_steps */
+
+/* ---- Projectron++ for the shared-dictionary rounds (csrc/kb_shared_plus.hip).  kb_set_shared_plus(k, on):
+ * on = 0 (the default): kb_shared_scan, kb_shared_apply, kb_shared_step and kb_shared_step_resident learn by Projectron's rule,
+ * every kernel, launch and bit as above.  on = 1: they learn by ProjectronPlus.update (projectron.py:66-107); with one replica
+ * that is the reference's sequential loop (kbrl_control.py:103-112) with a ProjectronPlus learner.
+ *   scan   round 0's bookkeeping is unchanged (the sign of f at the executed allocation); a replica proposes its first
+ *          candidate, in augmentation order from its cursor, with y f < 1 instead of y f <= 0.  The proposal word, collect,
+ *          merge and commit are unchanged: a proposer that was not taken scans again from its candidate, a taken one moves past
+ *          it whichever branch its sample took.
+ *   apply  a dictionary that can still grow predicts the remaining proposals together, as before, and the first in list order
+ *          with y f < 1 goes through the margin rule with that f (branches 1-4, float32 while one landmark is held); the rest
+ *          are predicted again.  A dictionary at its capacity forms KF, d*, F0 and the Gram block A of the whole list as before
+ *          and walks it: f_p = F0_p + g_p, margin = y_p f_p; margin >= 1 nothing; margin <= 0 the projection with w_p = y_p;
+ *          otherwise delta = max(1 - A[p][p], 0), norm = max(1 - delta, 0), loss = 1 - margin, slack = loss - delta / eta, and
+ *          when slack > 0 the weight w_p = min(min(loss / norm, 1), 2 slack / norm) y_p.  An applied p adds w_p A[q][p] to g_q
+ *          of the later q, and the coefficients take c + w_p d*_p in list order.
+ * Under KBRL_SERIAL_APPLY=1 (test build) the one-by-one path forms f_p as a fresh k . coeff, so in this mode its coefficient
+ * bits differ from the batched walk's; the decisions agree and the values agree within DESIGN.md §2's tolerances.
+ * Counters: kb_get_stats[1] counts the samples that changed a dictionary (branches 1-3), [2] the insertions; kb_get_repair_work's
+ * work[6] the samples whose branch was 1-4; the saturation flag is raised by mistakes only.
+ * Host state of the handle like kb_set_control_plus: off by default, not part of kb_save_state blobs, neither carried nor
+ * changed by kb_share, kb_unshare and kb_shared_prune.  kb_get_algorithm keeps answering KB_ALG_PROJECTRON on a shared handle:
+ * it names the rule of kb_update / kb_fit, not the fleet's -- this switch does.  Every rank of a group (kb_comm_init) must set
+ * the same value before the same step; nothing checks it across ranks.  With equal switches the merged list and the rule are
+ * deterministic, so the ranks' dictionaries stay bit-identical without a collective.
+ * RS_EINVAL for a null handle or a value other than 0 and 1; RS_ESTATE for a handle that is not shared-dictionary (there
+ * kb_set_control_plus is the call meant) and while a round is open between kb_shared_scan and kb_shared_commit. */
+int kb_set_shared_plus(kb_handle* k, int32_t on);
+int kb_get_shared_plus(kb_handle* k, int32_t* on);
 
 #ifdef __cplusplus
 }

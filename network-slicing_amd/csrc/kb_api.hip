@@ -75,6 +75,7 @@ struct kb_handle {
     int32_t fit_wide_min = 0, fit_wide_window = 0;  // kb_set_fit_wide: host state of the handle like alg, never copied or saved (kb_fit_wide.hip)
     int32_t fit_wide_plus = 0;                      // kb_set_fit_wide_plus: 1 = the rounds also teach in Projectron++ mode; host state as well
     int32_t control_plus = 0;                       // kb_set_control_plus: 1 = the closed control loop learns in Projectron++ mode; host state as well (kb_control_plus.hip)
+    int32_t shared_plus = 0;                        // kb_set_shared_plus: 1 = the shared-dictionary rounds learn by the margin rule; host state as well (kb_shared_plus.hip)
     unsigned long long* d_ctl_work = nullptr;       // [4] control_plus_kernel's counters (allocated when the switch is first set)
     int32_t cpb_width = 0, cpb_max = 0;             // kb_set_control_plus_batch: candidates per pass over Kinv (0: one by one) and the largest dictionary grouped; host state as well (kb_control_plus_batch.hip)
     char* d_cpb = nullptr;                          // its scratch: work[8], the ticket, the workgroups' arenas (allocated by the setter, freed at width 0)
@@ -428,8 +429,10 @@ static int kb_create_impl(const kb_config* cfg, int device, kb_handle** out, uns
             k->err = "kb_create: shared dictionaries hold at most ~14,000 landmarks (the batched apply keeps a column in LDS)";
             return RS_EINVAL;
         }
-        if (lds > 48 * 1024)
+        if (lds > 48 * 1024) {
             HIPCHK(k, hipFuncSetAttribute((const void*)kb::shared_apply_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HIPCHK(k, hipFuncSetAttribute((const void*)kb::shared_apply_plus_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        }
     }
     {
         // The two kernels that stream Kinv split their work line evenly over the waves of the launch: exactly one resident
@@ -607,7 +610,19 @@ static void launch_shared_apply(kb_handle* k, const double* props, const int32_t
         hipLaunchKernelGGL(kb::shared_matvec_kernel, dim3(S, KB_MATVEC_BLOCKS), dim3(256), 0, k->stream, k->D, k->K, counts, budget, 0);
     hipLaunchKernelGGL(kb::shared_gram_kernel, dim3(S, 128), dim3(256), 0, k->stream, k->D, k->K, counts, budget);
     const size_t lds = sizeof(double) * kb::kb_apply_lds_doubles(k->cfg.capacity, k->budget_cap);
-    hipLaunchKernelGGL(kb::shared_apply_kernel, dim3(S), dim3(1024), lds, k->stream, k->D, k->K, props, counts, budget, k->d_gstats);
+    // (kb_set_shared_plus: the walk and the one-by-one path decide by the margin rule; what the wide kernels form is the same)
+    if (k->shared_plus)
+        hipLaunchKernelGGL(kb::shared_apply_plus_kernel, dim3(S), dim3(1024), lds, k->stream, k->D, k->K, props, counts, budget, k->d_gstats);
+    else
+        hipLaunchKernelGGL(kb::shared_apply_kernel, dim3(S), dim3(1024), lds, k->stream, k->D, k->K, props, counts, budget, k->d_gstats);
+}
+
+// the scan of a round: the instance kb_set_shared_plus names
+static void launch_shared_scan(kb_handle* k, const kb::ScanArgs& a) {
+    if (k->shared_plus)
+        hipLaunchKernelGGL(kb::shared_scan_plus_kernel, dim3((unsigned)k->T), dim3(64), 0, k->stream, a);
+    else
+        hipLaunchKernelGGL(kb::shared_scan_kernel, dim3((unsigned)k->T), dim3(64), 0, k->stream, a);
 }
 
 // the scores of the large shared dictionaries for all replicas at once (F = E Q on MFMA); shared_scan_kernel picks them up
@@ -1295,7 +1310,7 @@ extern "C" int kb_shared_scan(kb_handle* k, const float* state, const int32_t* a
     HIPCHK(k, k->spans.begin(k->stream, 0, &e1));
     k->gemm_fresh = false;
     launch_shared_gemm(k, a.state);
-    hipLaunchKernelGGL(kb::shared_scan_kernel, dim3((unsigned)k->T), dim3(64), 0, k->stream, a);
+    launch_shared_scan(k, a);
     if (e1) HIPCHK(k, hipEventRecord(e1, k->stream));
     hipLaunchKernelGGL(kb::shared_collect_kernel, dim3((unsigned)S), dim3(KB_RANK_THREADS), 0, k->stream, k->D, k->d_state, k->d_labels,
                        k->d_cstar, (int)budget, k->d_props, k->d_counts);
@@ -1420,7 +1435,7 @@ static int shared_step_core(kb_handle* k, const float* d_state, const int32_t* d
         // (resident loop, round 0: select_action of the previous step scored this very state against these very dictionaries)
         if (!(rnd == 0 && k->gemm_fresh && d_state == k->d_prev_state)) launch_shared_gemm(k, a.state);
         k->gemm_fresh = false;
-        hipLaunchKernelGGL(kb::shared_scan_kernel, dim3((unsigned)k->T), dim3(64), 0, k->stream, a);
+        launch_shared_scan(k, a);
         if (e1) local(hipEventRecord(e1, k->stream), "hipEventRecord");
         hipLaunchKernelGGL(kb::shared_collect_block_kernel, dim3((unsigned)S), dim3(KB_RANK_THREADS), 0, k->stream, k->D, d_state,
                            d_labels, k->d_cstar, (int)budget, k->d_block);

@@ -774,7 +774,9 @@ __device__ __forceinline__ double f_of(const double (&f)[4], Win w, int c) {
 }
 
 // first candidate c in [c_from, c_to] (in order) with f(c) * y <= 0, or -1; *zeros = candidates with f == 0 among
-// [c_from, min(c_to, found)]
+// [c_from, min(c_to, found)].  MARGIN (the shared rounds under kb_set_shared_plus): with f(c) * y < 1 -- the
+// samples ProjectronPlus.update does not pass over (projectron.py:71-74: a mistake, or inside the margin).
+template <bool MARGIN = false>
 __device__ __forceinline__ int first_mistake(const double (&f)[4], Win w, int y, int c_from, int c_to, int* zeros) {
     const int lane = threadIdx.x & 63;
     int found = -1, nz = 0;
@@ -782,7 +784,7 @@ __device__ __forceinline__ int first_mistake(const double (&f)[4], Win w, int y,
     for (int g = 0; g < 4; ++g) {
         const int c = w.base + 64 * g + lane;
         const bool in = c >= c_from && c <= c_to;
-        const unsigned long long bad = __ballot(in && f[g] * (double)y <= 0.0);
+        const unsigned long long bad = __ballot(in && (MARGIN ? f[g] * (double)y < 1.0 : f[g] * (double)y <= 0.0));
         const unsigned long long zer = __ballot(in && f[g] == 0.0);
         if (found < 0) {
             if (bad) {
@@ -2701,7 +2703,10 @@ __global__ __launch_bounds__(256) void shared_fgemm_kernel(KbDev D, KbState K, c
 #ifndef KB_SCAN_OCC
 #define KB_SCAN_OCC 3
 #endif
-__global__ __launch_bounds__(64, KB_SCAN_OCC) void shared_scan_kernel(ScanArgs A) {
+// the scan of one (replica, slice).  PLUS (kb_set_shared_plus): the proposal is the first candidate with y f < 1
+// instead of y f <= 0; round 0's bookkeeping, the counters and the cursor are the same.
+template <bool PLUS>
+__device__ __forceinline__ void shared_scan_body(ScanArgs A) {
     const KbDev& D = A.D;
     const KbState& K = A.K;
     __shared__ Lds sm;
@@ -2759,7 +2764,7 @@ __global__ __launch_bounds__(64, KB_SCAN_OCC) void shared_scan_kernel(ScanArgs A
     if (c_from >= 0 && c_from <= c_to) {
         n_eval += (uint64_t)(c_to - c_from + 1) * (uint64_t)m;
         int zeros;
-        cstar = first_mistake(f, w, y, c_from, c_to, &zeros);
+        cstar = first_mistake<PLUS>(f, w, y, c_from, c_to, &zeros);
         const int last = cstar >= 0 ? cstar : c_to;
         n_pred += (uint64_t)(last - c_from + 1);
         if (m > 0 && zeros > 0 && threadIdx.x == 0) K.tie_ctr[task] += (uint32_t)zeros;  // Q11
@@ -2772,6 +2777,8 @@ __global__ __launch_bounds__(64, KB_SCAN_OCC) void shared_scan_kernel(ScanArgs A
         st[3] += n_eval;
     }
 }
+__global__ __launch_bounds__(64, KB_SCAN_OCC) void shared_scan_kernel(ScanArgs A) { shared_scan_body<false>(A); }
+__global__ __launch_bounds__(64, KB_SCAN_OCC) void shared_scan_plus_kernel(ScanArgs A) { shared_scan_body<true>(A); }
 
 // first `budget` proposers of each slice in replica order -> props[s][i][KB_PROP_W], counts[s] = all proposers
 // Rank of every local proposer of slice s (replicas with cstar >= 0) in replica order, by all threads of the block:
@@ -3123,9 +3130,13 @@ __global__ __launch_bounds__(256) void shared_gram_kernel(KbDev D, KbState K, co
     }
 }
 
-// the ordered part, by the slice's own workgroup: co = the coefficient column, wl = scratch (4 x budget doubles), in LDS
+// the ordered part, by the slice's own workgroup: co = the coefficient column, wl = scratch (4 x budget doubles), in LDS.
+// PLUS (kb_set_shared_plus): the walk decides by ProjectronPlus.update -- margin = y f >= 1 nothing, <= 0 the
+// projection as below, in between margin_update's rule on delta = max(1 - A[p][p], 0) with the weight w_p = alpha y_p; wq holds
+// w_p, the return value counts the samples that changed the coefficients and *n_work those that formed delta (branches 1-4).
+template <bool PLUS>
 __device__ uint64_t apply_full_batch(const KbDev& D, const KbState& K, int s, int m, const double* pr, int np, int budget,
-                                     double* co, double* wl) {
+                                     double* co, double* wl, uint64_t* n_work) {
     const int capr = kb_capr(D.cap);
     const uint64_t* sh = shells_of(D, K, s);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -3139,6 +3150,7 @@ __device__ uint64_t apply_full_batch(const KbDev& D, const KbState& K, int s, in
     for (int q = threadIdx.x; q < budget; q += blockDim.x) wq[q] = 0.0;
     __syncthreads();
     uint64_t n_mist = 0;
+    [[maybe_unused]] uint64_t work = 0;
     if (wave == 0) {
         bool sat = false;
         int napp = 0;
@@ -3168,7 +3180,40 @@ __device__ uint64_t apply_full_batch(const KbDev& D, const KbState& K, int s, in
             const int pk = p >> 6, pl = p & 63;
             const int y = __builtin_amdgcn_readlane(pk == 0 ? yv[0] : (pk == 1 ? yv[1] : (pk == 2 ? yv[2] : yv[3])), pl);
             const double f = readlane_f64(pk == 0 ? f0v[0] + g[0] : (pk == 1 ? f0v[1] + g[1] : (pk == 2 ? f0v[2] + g[2] : f0v[3] + g[3])), pl);
-            if (f * (double)y <= 0.0) {
+            if constexpr (PLUS) {
+                // (the applied step -- the fma over col, the wq / lst stores -- stands in the Projectron arm below as well, with
+                // w = y: a change there is made here too)
+                const double margin = (double)y * f;
+                if (margin >= 1.0) continue;  // (the prefetch of column p + 2 is issued above)
+                work += 1;
+                const double dg = readlane_f64(pk == 0 ? col[0] : (pk == 1 ? col[1] : (pk == 2 ? col[2] : col[3])), pl);
+                double delta = 1.0 - dg;
+                delta = delta > 0.0 ? delta : 0.0;
+                double w = (double)y;
+                if (margin <= 0.0) {
+                    sat = sat || delta > D.eta;  // a mistake the full dictionary would have grown for
+                } else {  // margin_update's statements on the Gram block's diagonal
+                    double norm = 1.0 - delta;
+                    norm = norm > 0.0 ? norm : 0.0;
+                    const double loss = 1.0 - margin;
+                    const double slack = loss - delta / D.eta;
+                    if (!(slack > 0.0)) continue;  // branch 4
+                    double alpha = loss / norm;
+                    alpha = 1.0 < alpha ? 1.0 : alpha;
+                    const double by_slack = 2.0 * slack / norm;
+                    alpha = by_slack < alpha ? by_slack : alpha;
+                    w = alpha * (double)y;
+                }
+                n_mist += 1;
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (lane + 64 * k > p) g[k] = __builtin_fma(w, col[k], g[k]);
+                if (lane == 0) {
+                    wq[p] = w;
+                    lst[napp] = (double)p;
+                }
+                napp += 1;
+            } else if (f * (double)y <= 0.0) {
                 n_mist += 1;
                 // delta = 1 - k_p . d*_p is the Gram block's diagonal: a full dictionary met a sample it would have grown for
                 const double dg = readlane_f64(pk == 0 ? col[0] : (pk == 1 ? col[1] : (pk == 2 ? col[2] : col[3])), pl);
@@ -3206,12 +3251,17 @@ __device__ uint64_t apply_full_batch(const KbDev& D, const KbState& K, int s, in
         }
         *vec_at(K, sh, KB_ROW_CO, j) = c;
     }
+    if constexpr (PLUS) *n_work = work;
     return n_mist;
 }
 
 // apply a merged proposal list to the dictionary of slice s = blockIdx.x, in order.  Dynamic LDS: kb_apply_lds_doubles().
-__global__ __launch_bounds__(1024) void shared_apply_kernel(KbDev D, KbState K, const double* props, const int32_t* counts,
-                                                         int budget, uint64_t* gstats) {
+// PLUS (kb_set_shared_plus): the list is learned by ProjectronPlus.update -- the proposal applied next is the first
+// with y f < 1, through apply_update_plus with the f it was predicted with; gstats[1] counts the samples that changed the
+// dictionary (branches 1-3), K.hv_work[6] those that formed d* (branches 1-4), as the per-replica loop does (§8l).
+template <bool PLUS>
+__device__ __forceinline__ void shared_apply_body(KbDev D, KbState K, const double* props, const int32_t* counts, int budget,
+                                                  uint64_t* gstats) {
     extern __shared__ double kb_dyn_lds[];
     __shared__ Lds sm;
     const int s = blockIdx.x;
@@ -3223,9 +3273,12 @@ __global__ __launch_bounds__(1024) void shared_apply_kernel(KbDev D, KbState K, 
     const unsigned long long t_in = wall_clock64();  // (developer aid: per-slice time and applied samples, gstats[8..])
     if (np > 0 && batch_applies(D, m)) {
         // kernel columns and d* of the whole list are in the work area (shared_cols_kernel, shared_matvec_kernel)
-        n_mist = apply_full_batch(D, K, s, m, props + (size_t)s * budget * KB_PROP_W, np, budget, kb_dyn_lds,
-                                  kb_dyn_lds + kb_capr(D.cap));
+        [[maybe_unused]] uint64_t n_work = 0;
+        n_mist = apply_full_batch<PLUS>(D, K, s, m, props + (size_t)s * budget * KB_PROP_W, np, budget, kb_dyn_lds,
+                                        kb_dyn_lds + kb_capr(D.cap), &n_work);
         if (threadIdx.x == 0) {
+            if constexpr (PLUS)
+                if (n_work) atomicAdd((unsigned long long*)&K.hv_work[6], (unsigned long long)n_work);
             atomicAdd((unsigned long long*)&gstats[1], (unsigned long long)n_mist);
             atomicAdd((unsigned long long*)&gstats[8 + s], wall_clock64() - t_in);
             atomicAdd((unsigned long long*)&gstats[16 + s], (unsigned long long)n_mist);
@@ -3242,8 +3295,10 @@ __global__ __launch_bounds__(1024) void shared_apply_kernel(KbDev D, KbState K, 
     const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6, lane = threadIdx.x & 63;
     double* fp = kb_dyn_lds;  // [budget] predictions of the remaining proposals
     int from = 0;
+    [[maybe_unused]] uint64_t n_work = 0;
     while (from < np) {
-        // The first remaining proposal, in order, that is still a mistake.  The remaining proposals are predicted in
+        // The first remaining proposal, in order, that is still a mistake (PLUS: a mistake or inside the margin, y f < 1).
+        // The remaining proposals are predicted in
         // chunks that double (one proposal per wave first): while a list is being learned its next mistake is usually among
         // the first few, and a pass over all of the rest for every applied sample was most of a long list's time.  The
         // predictions past the one that is applied are discarded either way (the dictionary changes under them).
@@ -3296,7 +3351,7 @@ __global__ __launch_bounds__(1024) void shared_apply_kernel(KbDev D, KbState K, 
             __syncthreads();
             for (int q = lo + (int)threadIdx.x; q < hi; q += blockDim.x) {
                 const int y = (((int)props[((size_t)s * budget + q) * KB_PROP_W + 1]) & 1) ? 1 : -1;
-                if (fp[q] * (double)y <= 0.0) atomicMin(&sm.ired[5], q);
+                if (PLUS ? fp[q] * (double)y < 1.0 : fp[q] * (double)y <= 0.0) atomicMin(&sm.ired[5], q);
             }
             __syncthreads();
             i = sm.ired[5];
@@ -3312,8 +3367,15 @@ __global__ __launch_bounds__(1024) void shared_apply_kernel(KbDev D, KbState K, 
         kernel_column_full(D, K, sh, m, d, sm.x, t);
         int branch;
         double delta;
-        const int m_new = apply_update(D, K, s, 0, m, d, sm.x, t, c, y, sm, &branch, &delta);
-        n_mist += 1;
+        int m_new;
+        if constexpr (PLUS) {
+            m_new = apply_update_plus(D, K, s, 0, m, d, sm.x, t, c, y, fp[i], sm, &branch, &delta);
+            n_work += 1;
+            n_mist += branch != 4;
+        } else {
+            m_new = apply_update(D, K, s, 0, m, d, sm.x, t, c, y, sm, &branch, &delta);
+            n_mist += 1;
+        }
         if (branch == 2 && m_new > m) n_grow += 1;
         m = m_new;
         from = i + 1;
@@ -3321,12 +3383,22 @@ __global__ __launch_bounds__(1024) void shared_apply_kernel(KbDev D, KbState K, 
     if (threadIdx.x == 0) {
         K.m[s] = m;
         if (np > 0) K.kf_owner[s] = -1;
+        if constexpr (PLUS)
+            if (n_work) atomicAdd((unsigned long long*)&K.hv_work[6], (unsigned long long)n_work);
         atomicAdd((unsigned long long*)&gstats[1], (unsigned long long)n_mist);
         atomicAdd((unsigned long long*)&gstats[2], (unsigned long long)n_grow);
         atomicAdd((unsigned long long*)&gstats[8 + s], wall_clock64() - t_in);
         atomicAdd((unsigned long long*)&gstats[16 + s], (unsigned long long)n_mist);
         atomicAdd((unsigned long long*)&gstats[24 + s], (unsigned long long)np);
     }
+}
+__global__ __launch_bounds__(1024) void shared_apply_kernel(KbDev D, KbState K, const double* props, const int32_t* counts,
+                                                         int budget, uint64_t* gstats) {
+    shared_apply_body<false>(D, K, props, counts, budget, gstats);
+}
+__global__ __launch_bounds__(1024) void shared_apply_plus_kernel(KbDev D, KbState K, const double* props, const int32_t* counts,
+                                                              int budget, uint64_t* gstats) {
+    shared_apply_body<true>(D, K, props, counts, budget, gstats);
 }
 
 // ---- single-call entry points behind Projectron.predict / update (drop-in API, N=1 plumbing)

@@ -34,6 +34,7 @@ KB_EXPORTS = (
     'kb_set_control_plus_batch', 'kb_get_control_plus_batch', 'kb_control_plus_batch_info',
     'kb_set_control_plus_wide', 'kb_get_control_plus_wide', 'kb_control_plus_wide_info',
     'kb_set_fit_steps_batch', 'kb_get_fit_steps_batch', 'kb_fit_steps_batch_info',
+    'kb_set_shared_plus', 'kb_get_shared_plus',
 )
 
 EXPORTS = (
@@ -231,6 +232,8 @@ def load(dev=None):
     L.kb_fit_steps.argtypes = [vp, ip, C.c_int32, i64p, fp, ip, ip, C.c_int32, dp, ip, ip, ip, ip]
     L.kb_set_control_plus.argtypes = [vp, C.c_int32]
     L.kb_get_control_plus.argtypes = [vp, ip]
+    L.kb_set_shared_plus.argtypes = [vp, C.c_int32]
+    L.kb_get_shared_plus.argtypes = [vp, ip]
     L.kb_set_control_plus_batch.argtypes = [vp, C.c_int32, C.c_int32]
     L.kb_get_control_plus_batch.argtypes = [vp, ip, ip, up]
     L.kb_control_plus_batch_info.argtypes = [vp, up]

@@ -854,16 +854,38 @@ class SharedVecKBRL(VecKBRL):
 
     `exchange(counts, props)` (optional) replaces the device exchange by a host callback that must return the lists of
     all ranks stacked on a leading axis ([W][S], [W][S][budget][PROP_W]) and this rank's index: used to run several
-    handles side by side in ONE process (tests) and to pin the merge rule on CPU (merge_proposals, gloo test)."""
+    handles side by side in ONE process (tests) and to pin the merge rule on CPU (merge_proposals, gloo test).
 
-    def __init__(self, n_envs, dims, n_prbs, budget=64, max_rounds=4, exchange=None, **kw):
+    `shared_plus=True` (or set_shared_plus()): the rounds learn by ProjectronPlus.update instead of Projectron.update
+    (kb_set_shared_plus).  A replica proposes its first candidate with y f < 1 instead of y f <= 0; a merged
+    list is applied in order by the margin rule -- y f >= 1 nothing, y f <= 0 Projectron's projection or insertion, in between the
+    scaled projection coeff += alpha y d* when its slack is positive -- and a taken proposer moves past its candidate whichever
+    branch the sample took.  Every rank of a group must set the same value before the same step.  stats()[1] then counts
+    the samples that changed a dictionary (branches 1-3), kb_get_repair_work's work[6] those whose branch was 1-4."""
+
+    def __init__(self, n_envs, dims, n_prbs, budget=64, max_rounds=4, exchange=None, shared_plus=False, **kw):
         if kw.get('algorithm', 'projectron') != 'projectron':
-            raise ValueError("SharedVecKBRL learns through its proposal rounds, which implement Projectron's rule: "
-                             "algorithm=%r is not supported (fit a per-replica VecKBRL, then to_shared)" % kw['algorithm'])
+            raise ValueError("SharedVecKBRL learns through its proposal rounds: algorithm=%r is not supported (the rounds learn by "
+                             "the margin rule of 'projectron_plus' with shared_plus=True; or fit a per-replica VecKBRL, then "
+                             "to_shared)" % kw['algorithm'])
         super().__init__(n_envs, dims, n_prbs, shared=True, **kw)
         self.budget, self.max_rounds = budget, max_rounds
         self.exchange = exchange
         self.rounds_last = 0
+        if shared_plus:
+            self.set_shared_plus(True)
+
+    def set_shared_plus(self, on=True):
+        """whether the proposal rounds learn by the margin rule of Projectron++ (kb_set_shared_plus); off is the default.  Between
+        steps only: refused while a host-driven round is open."""
+        self._check(self.L.kb_set_shared_plus(self.h, int(bool(on))))
+
+    @property
+    def shared_plus(self):
+        """True while set_shared_plus is on (kb_get_shared_plus)"""
+        a = C.c_int32()
+        self._check(self.L.kb_get_shared_plus(self.h, C.byref(a)))
+        return bool(a.value)
 
     def fit(self, learners, X, y, chunk=0):
         """refused: the replicas' learners map to ONE dictionary per slice, so their sample lists are not independent sequences

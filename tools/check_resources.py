@@ -63,6 +63,11 @@ CTL_WIDE = {'cpw_list_kernel': 0, 'cpw_plan_kernel': 0, 'cpw_rank1_kernel': 0,
             'cpw_walk_kernelILi2E': 0, 'cpw_walk_kernelILi4E': 0, 'cpw_walk_kernelILi8E': 0,
             'cpw_rows_kernelILi2E': 0, 'cpw_rows_kernelILi4E': 0, 'cpw_rows_kernelILi8E': 220,
             'cpw_finish_kernelILi2E': 0, 'cpw_finish_kernelILi4E': 0, 'cpw_finish_kernelILi8E': 116}
+# the shared-dictionary rounds under the margin rule (kb_set_shared_plus): each instance beside the Projectron one
+# it is a variant of.  The scan holds no scratch and keeps the occupancy its __launch_bounds__(64, KB_SCAN_OCC) asks for; the
+# apply may spill no more than the Projectron instance does
+SHARED_PLUS = {'shared_scan_plus_kernel': 'shared_scan_kernel', 'shared_apply_plus_kernel': 'shared_apply_kernel'}
+KB_SCAN_OCC = 3
 PRODUCTION = ["embb_step_kernelILi16ELb0ELb0ELb1E", "embb_step_kernelILi16ELb0ELb1ELb1E"]   # <16, false, plain | BLOCK, FDIV>
 PLAIN = PRODUCTION[0]          # the instance bench.py's headline runs
 STEP_KERNEL = 'embb_step_kernelIL'
@@ -204,6 +209,22 @@ def check(path=LOG):
                                                                                       r.get('Occupancy'), r.get('LDS Size')))
         if r.get('ScratchSize', 0) > min(scratch, LIMIT):
             bad.append('%s spills %d B/lane (> %d)' % (key, r['ScratchSize'], scratch))
+    for key, base in SHARED_PLUS.items():
+        hit, hit0 = [k for k in res if re.search(r'\d' + key, k)], [k for k in res if re.search(r'\d' + base, k)]
+        if not hit or not hit0:
+            bad.append('%s: not found in %s' % (key if not hit else base, path))
+            continue
+        for name, r in ((base, res[hit0[0]]), (key, res[hit[0]])):
+            print('%s: VGPRs %s, SGPRs %s, scratch %s B/lane, occupancy %s, LDS %s B' % (name, r.get('VGPRs'), r.get('TotalSGPRs'),
+                                                                                        r.get('ScratchSize'), r.get('Occupancy'), r.get('LDS Size')))
+        r, r0 = res[hit[0]], res[hit0[0]]
+        if 'scan' in key:
+            if r.get('ScratchSize', 0) > 0 or r0.get('ScratchSize', 0) > 0:
+                bad.append('%s / %s: the scan spills (%s / %s B/lane)' % (key, base, r.get('ScratchSize'), r0.get('ScratchSize')))
+            if min(r.get('Occupancy', 0), r0.get('Occupancy', 0)) < KB_SCAN_OCC:
+                bad.append('%s / %s: occupancy %s / %s < %d waves/SIMD' % (key, base, r.get('Occupancy'), r0.get('Occupancy'), KB_SCAN_OCC))
+        elif r.get('ScratchSize', 0) > r0.get('ScratchSize', 0):
+            bad.append('%s spills %d B/lane (> %d, the Projectron instance)' % (key, r['ScratchSize'], r0['ScratchSize']))
     return bad
 
 

@@ -14,7 +14,10 @@ both runs alike, so the ms per step include it.  Per shrink: landmarks removed, 
 before and after, and either the device ms of its three kernels (kb_prune_time_ms, with the launches counted; kernel timing is
 switched on for that call alone) or -- every other shrink, timing off -- the wall ms of the call.
 
-  python tools/shared_prune_record.py [--replicas 4096] [--steps 1400] [--target 768] [--every 200]
+--shared-plus: the fleet learns by the margin rule of Projectron++ in both runs (kb_set_shared_plus); the record
+then says so, and --out should name another file than the committed one.
+
+  python tools/shared_prune_record.py [--replicas 4096] [--steps 1400] [--target 768] [--every 200] [--shared-plus]
 """
 import argparse
 import ctypes as C
@@ -45,7 +48,7 @@ def child(a):
     sf = np.concatenate([rng.integers(EMBB_SEC[0], EMBB_SEC[1], size=(n, cfg.n_embb)),
                          rng.integers(MMTC_SEC[0], MMTC_SEC[1], size=(n, cfg.n_mmtc))], axis=1).astype(np.int32)
     env.reset(seeds=replica_seeds(0, 0, n))
-    agent = SharedVecKBRL(n, dims, cfg.n_prbs, budget=BUDGET, max_rounds=MAX_ROUNDS, capacity=CAPACITY)
+    agent = SharedVecKBRL(n, dims, cfg.n_prbs, budget=BUDGET, max_rounds=MAX_ROUNDS, capacity=CAPACITY, shared_plus=a.shared_plus)
     agent.reset(ia, sf, seeds=replica_seeds(7, 0, n))
     env._check(env.L.rs_step(env.h, np.ascontiguousarray(ia).ctypes.data_as(C.POINTER(C.c_int32)), None, None, None, None))
     windows, shrinks = [], []
@@ -100,7 +103,7 @@ def child(a):
 
 def run(mode, a):
     cmd = ['timeout', '-k', '10', str(a.timeout), sys.executable, os.path.abspath(__file__), '--child', mode, '--replicas', str(a.replicas),
-           '--steps', str(a.steps), '--target', str(a.target), '--every', str(a.every)]
+           '--steps', str(a.steps), '--target', str(a.target), '--every', str(a.every)] + (['--shared-plus'] if a.shared_plus else [])
     p = subprocess.run(cmd, capture_output=True, text=True)
     if p.returncode != 0:
         raise SystemExit('%s failed with status %d\n%s' % (' '.join(cmd), p.returncode, p.stderr[-2000:]))
@@ -114,6 +117,7 @@ def main():
     ap.add_argument('--steps', type=int, default=1400)
     ap.add_argument('--target', type=int, default=768)
     ap.add_argument('--every', type=int, default=200)
+    ap.add_argument('--shared-plus', action='store_true', help='the rounds learn by the margin rule (kb_set_shared_plus)')
     ap.add_argument('--timeout', type=int, default=400)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'shared_prune_record.json'))
     a = ap.parse_args()
@@ -123,6 +127,8 @@ def main():
     if a.steps % WINDOW or a.every % WINDOW:
         raise SystemExit('--steps and --every must be multiples of %d' % WINDOW)
     rec = dict(scenario=SCENARIO, budget=BUDGET, max_rounds=MAX_ROUNDS, capacity=CAPACITY, statistic='one run per mode, one MI355X')
+    if a.shared_plus:
+        rec['shared_plus'] = True
     for mode in ('plain', 'shrink'):   # (one after the other: never two processes on the GPU at once)
         rec[mode] = run(mode, a)
         print(json.dumps({k: v for k, v in rec[mode].items() if k != 'windows'}), flush=True)
