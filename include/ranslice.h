@@ -942,6 +942,39 @@ int kb_fit_steps_batch_info(kb_handle* k, uint64_t work[8]);   /* of the last kb
 int kb_set_shared_plus(kb_handle* k, int32_t on);
 int kb_get_shared_plus(kb_handle* k, int32_t* on);
 
+/* ---- Chip-wide passes for shared dictionaries that still grow under the margin rule (csrc/kb_shared_plus_batch.hip, DESIGN.md
+ * §8r).  kb_set_shared_plus_batch(k, min_landmarks, segments): min_landmarks = 0 (the default) off -- every launch, kernel and
+ * byte as kb_set_shared_plus leaves them.  Otherwise, while kb_set_shared_plus is on and KBRL_SERIAL_APPLY is not set (test
+ * build), a merged list of at least one proposal whose dictionary holds min_landmarks <= m < capacity landmarks when the apply
+ * begins is ENGAGED and applied in segments (between two insertions the landmarks and Kinv are fixed):
+ *   1. for the proposals that remain, against the dictionary as it stands, KF, d* = Kinv KF, F0 = KF . coeff and the lower block
+ *      triangle of A = KF d*^T, each value summed as kb_shared_apply sums it for a dictionary at its capacity, by kernels as wide as
+ *      the chip (the mat-vec on the matrix cores where m is a multiple of 64);
+ *   2. one wave walks them by that dictionary's rule (above: f_p = F0_p + g_p with g = 0 at the segment's start, branches 0, 1, 3
+ *      and 4) with one addition: a mistake with max(1 - A[p][p], 0) > eta while m < capacity stops the walk before it is applied;
+ *      a mistake that does not stop projects with w_p = y_p, and the saturation flag is raised only at the capacity;
+ *   3. the coefficients take c + w_p d*_p of the applied proposals in list order;
+ *   4. the sample the walk stopped at goes through the one-by-one update with the walk's f_p: its own residual decides between
+ *      projection and insertion, its capacity and pool rules apply; the next segment starts behind it.
+ * A list whose dictionary reaches its capacity in the middle stays with the segments to its end.  Lists that are not engaged go as
+ * without this switch (m < min_landmarks one by one, the float32 regime of m <= 1 included; m >= capacity the full-batch walk).
+ * `segments` (0 .. 16) segment rounds are enqueued per apply, then a finishing launch that takes what they left in the same
+ * segments with the same arithmetic: the results do not depend on `segments`, which may differ between the ranks of a group;
+ * min_landmarks must be the same on every rank, and nothing checks it.  Nothing waits on the host.
+ * As for a dictionary at its capacity, f_p is F0_p plus a chain of fused multiply-adds, not a fresh k . coeff: the results are
+ * defined as bits by tests/shared_plus_batch_mirror.py; against the switch off every branch is equal, coefficients and Kinv agree
+ * within DESIGN.md §2's tolerances.  Counters as above (kb_get_stats[1], [2], work[6] of kb_get_repair_work).
+ * Host state like kb_set_shared_plus: in no kb_save_state blob, left alone by kb_share, kb_unshare and kb_shared_prune; it is
+ * remembered while kb_set_shared_plus is off and acts only while that is on.
+ * RS_EINVAL for a null handle, min_landmarks other than 0 or 2 .. capacity, segments outside 0 .. 16; RS_ESTATE for a handle that
+ * is not shared-dictionary and while a round is open between kb_shared_scan and kb_shared_commit.
+ * kb_shared_plus_batch_info, since kb_reset: work[0] engaged lists, [1] segments walked, [2] proposals covered by the segments'
+ * wide passes (the sum of the proposals that remained, over the segments), [3] segments ended by a stop, [4] segments run by the
+ * finishing launch; the rest 0. */
+int kb_set_shared_plus_batch(kb_handle* k, int32_t min_landmarks, int32_t segments);
+int kb_get_shared_plus_batch(kb_handle* k, int32_t* min_landmarks, int32_t* segments);
+int kb_shared_plus_batch_info(kb_handle* k, uint64_t work[8]);   /* since kb_reset */
+
 #ifdef __cplusplus
 }
 #endif

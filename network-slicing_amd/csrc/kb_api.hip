@@ -76,6 +76,8 @@ struct kb_handle {
     int32_t fit_wide_plus = 0;                      // kb_set_fit_wide_plus: 1 = the rounds also teach in Projectron++ mode; host state as well
     int32_t control_plus = 0;                       // kb_set_control_plus: 1 = the closed control loop learns in Projectron++ mode; host state as well (kb_control_plus.hip)
     int32_t shared_plus = 0;                        // kb_set_shared_plus: 1 = the shared-dictionary rounds learn by the margin rule; host state as well (kb_shared_plus.hip)
+    int32_t spb_min = 0, spb_segments = 0;          // kb_set_shared_plus_batch: from how many landmarks a growing shared dictionary's list is applied in segments (0: never) and the segment rounds enqueued per apply; host state as well (kb_shared_plus_batch.hip)
+    char* d_spb = nullptr;                          // its counters and per-slice state (allocated by the setter)
     unsigned long long* d_ctl_work = nullptr;       // [4] control_plus_kernel's counters (allocated when the switch is first set)
     int32_t cpb_width = 0, cpb_max = 0;             // kb_set_control_plus_batch: candidates per pass over Kinv (0: one by one) and the largest dictionary grouped; host state as well (kb_control_plus_batch.hip)
     char* d_cpb = nullptr;                          // its scratch: work[8], the ticket, the workgroups' arenas (allocated by the setter, freed at width 0)
@@ -118,6 +120,10 @@ static void kb_control_plus_release(kb_handle* k);  // kb_control_plus.hip
 static void kb_control_plus_batch_release(kb_handle* k);  // kb_control_plus_batch.hip
 static void kb_fit_steps_batch_release(kb_handle* k);     // kb_fit_steps_batch.hip
 static void kb_control_plus_wide_release(kb_handle* k);   // kb_control_plus_wide.hip
+static void kb_shared_plus_batch_release(kb_handle* k);   // kb_shared_plus_batch.hip
+static void kb_shared_plus_batch_restart(kb_handle* k);
+static bool kb_shared_plus_batch_on(const kb_handle* k);
+static void launch_shared_plus_batch(kb_handle* k, const double* props, const int32_t* counts, int budget);
 static kb_handle* kb_ref_store(kb_handle* k);
 static int kb_ref_dict(kb_handle* k, size_t task);
 static int kb_ref_select(kb_handle* k, const float* d_state);  // the scoring of launch_select: one fused kernel
@@ -510,6 +516,7 @@ extern "C" void kb_destroy(kb_handle* k) {
     kb_control_plus_batch_release(k);
     kb_fit_steps_batch_release(k);
     kb_control_plus_wide_release(k);
+    kb_shared_plus_batch_release(k);
     if (k->h_seen) (void)hipHostFree(k->h_seen);
     if (k->h_total) (void)hipHostFree(k->h_total);
     if (k->stream) (void)hipStreamDestroy(k->stream);
@@ -527,6 +534,7 @@ static int kb_restart_counters(kb_handle* k) {
     HIPCHK(k, hipMemsetAsync(k->d_gstats, 0, sizeof(uint64_t) * 32, k->stream));
     HIPCHK(k, hipMemsetAsync(k->K.hv_work, 0, sizeof(unsigned long long) * 8, k->stream));
     kb_prune_restart(k);
+    kb_shared_plus_batch_restart(k);
     return RS_OK;
 }
 // What a transfer of agents into the handle restarts (kb_fork.hip, kb_import_agents): the counters, the repair queue, the
@@ -598,6 +606,8 @@ static int kb_check(kb_handle* k) {
 // apply a proposal list per slice: the wide kernels prepare what a full dictionary's list needs (they return at once for
 // dictionaries that can still grow), then one workgroup per slice walks its list in order
 static void launch_shared_apply(kb_handle* k, const double* props, const int32_t* counts, int budget) {
+    // (kb_set_shared_plus_batch with the margin rule on: growing dictionaries take their lists in segments)
+    if (kb_shared_plus_batch_on(k)) return launch_shared_plus_batch(k, props, counts, budget);
     const unsigned S = (unsigned)k->cfg.n_slices;
     hipLaunchKernelGGL(kb::shared_cols_kernel, dim3(S, KB_COLS_BLOCKS), dim3(256), 0, k->stream, k->D, k->K, props, counts, budget);
     // d* of the whole list: on the matrix cores when the capacity (the size of a full dictionary) is a multiple of 64, by

@@ -1485,6 +1485,7 @@ extern "C" int rs_load_state(rs_handle* h, const void* blob, uint64_t bytes) {
 #include "kb_control_plus_wide.hip"
 #include "kb_fit_steps_batch.hip"
 #include "kb_shared_plus.hip"
+#include "kb_shared_plus_batch.hip"
 #ifdef RS_DEV
 #include "rs_probe.hip"  // rs_dev_probe: the arithmetic primitives one by one (tests/test_gpu_primitives.py)
 #include "kb_probe.hip"  // kb_dev_get_scores / kb_dev_get_rows: what the agent's scoring chain left, stage by stage (tests/scoring_mirror.py)

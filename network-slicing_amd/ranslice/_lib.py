@@ -35,6 +35,7 @@ KB_EXPORTS = (
     'kb_set_control_plus_wide', 'kb_get_control_plus_wide', 'kb_control_plus_wide_info',
     'kb_set_fit_steps_batch', 'kb_get_fit_steps_batch', 'kb_fit_steps_batch_info',
     'kb_set_shared_plus', 'kb_get_shared_plus',
+    'kb_set_shared_plus_batch', 'kb_get_shared_plus_batch', 'kb_shared_plus_batch_info',
 )
 
 EXPORTS = (
@@ -234,6 +235,9 @@ def load(dev=None):
     L.kb_get_control_plus.argtypes = [vp, ip]
     L.kb_set_shared_plus.argtypes = [vp, C.c_int32]
     L.kb_get_shared_plus.argtypes = [vp, ip]
+    L.kb_set_shared_plus_batch.argtypes = [vp, C.c_int32, C.c_int32]
+    L.kb_get_shared_plus_batch.argtypes = [vp, ip, ip]
+    L.kb_shared_plus_batch_info.argtypes = [vp, up]
     L.kb_set_control_plus_batch.argtypes = [vp, C.c_int32, C.c_int32]
     L.kb_get_control_plus_batch.argtypes = [vp, ip, ip, up]
     L.kb_control_plus_batch_info.argtypes = [vp, up]

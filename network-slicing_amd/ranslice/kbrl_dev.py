@@ -861,9 +861,14 @@ class SharedVecKBRL(VecKBRL):
     list is applied in order by the margin rule -- y f >= 1 nothing, y f <= 0 Projectron's projection or insertion, in between the
     scaled projection coeff += alpha y d* when its slack is positive -- and a taken proposer moves past its candidate whichever
     branch the sample took.  Every rank of a group must set the same value before the same step.  stats()[1] then counts
-    the samples that changed a dictionary (branches 1-3), kb_get_repair_work's work[6] those whose branch was 1-4."""
+    the samples that changed a dictionary (branches 1-3), kb_get_repair_work's work[6] those whose branch was 1-4.
 
-    def __init__(self, n_envs, dims, n_prbs, budget=64, max_rounds=4, exchange=None, shared_plus=False, **kw):
+    `shared_plus_batch=M` (or set_shared_plus_batch()): under the margin rule, a dictionary of M <= m < capacity landmarks takes
+    its merged list in segments between insertions, each with the chip-wide passes a full dictionary gets (kb_set_shared_plus_batch,
+    DESIGN.md section 8r); None is off.  `shared_plus_segments` segment rounds are enqueued per apply; the results do not depend on it."""
+
+    def __init__(self, n_envs, dims, n_prbs, budget=64, max_rounds=4, exchange=None, shared_plus=False, shared_plus_batch=None,
+                 shared_plus_segments=4, **kw):
         if kw.get('algorithm', 'projectron') != 'projectron':
             raise ValueError("SharedVecKBRL learns through its proposal rounds: algorithm=%r is not supported (the rounds learn by "
                              "the margin rule of 'projectron_plus' with shared_plus=True; or fit a per-replica VecKBRL, then "
@@ -874,6 +879,8 @@ class SharedVecKBRL(VecKBRL):
         self.rounds_last = 0
         if shared_plus:
             self.set_shared_plus(True)
+        if shared_plus_batch:
+            self.set_shared_plus_batch(shared_plus_batch, shared_plus_segments)
 
     def set_shared_plus(self, on=True):
         """whether the proposal rounds learn by the margin rule of Projectron++ (kb_set_shared_plus); off is the default.  Between
@@ -886,6 +893,27 @@ class SharedVecKBRL(VecKBRL):
         a = C.c_int32()
         self._check(self.L.kb_get_shared_plus(self.h, C.byref(a)))
         return bool(a.value)
+
+    def set_shared_plus_batch(self, min_landmarks, segments=4):
+        """from how many landmarks on a shared dictionary that can still grow takes a merged list in segments under the margin
+        rule (kb_set_shared_plus_batch): 0 or None (the default) never, else 2 .. capacity; `segments` (0 .. 16) segment rounds are
+        enqueued per apply and a finishing launch takes the rest.  Remembered, but it acts only while set_shared_plus is on.
+        Between steps only; every rank of a group sets the same min_landmarks."""
+        self._check(self.L.kb_set_shared_plus_batch(self.h, int(min_landmarks or 0), int(segments)))
+
+    @property
+    def shared_plus_batch(self):
+        """(min_landmarks, segments) of set_shared_plus_batch (kb_get_shared_plus_batch); min_landmarks 0 while off"""
+        a, b = C.c_int32(), C.c_int32()
+        self._check(self.L.kb_get_shared_plus_batch(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def shared_plus_batch_work(self):
+        """kb_shared_plus_batch_info since reset: engaged lists, segments walked, proposals covered by the segments' wide passes,
+        segments ended by a stop, segments run by the finishing launch; the rest 0"""
+        w = (C.c_uint64 * 8)()
+        self._check(self.L.kb_shared_plus_batch_info(self.h, w))
+        return [int(v) for v in w]
 
     def fit(self, learners, X, y, chunk=0):
         """refused: the replicas' learners map to ONE dictionary per slice, so their sample lists are not independent sequences

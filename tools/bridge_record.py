@@ -62,13 +62,14 @@ def first_step(env, actions):
     env._check(env.L.rs_step(env.h, a.ctypes.data_as(C.POINTER(C.c_int32)), None, None, None, None))
 
 
-def shared_fleet(n, steps=None, limit=800, shared_plus=False):
+def shared_fleet(n, steps=None, limit=800, shared_plus=False, shared_plus_batch=0):
     """-> (env, shared agent, steps run): `steps` closed-loop steps, or (None) until the largest dictionary is at capacity;
     shared_plus: the fleet learns by the margin rule (kb_set_shared_plus)"""
     from ranslice.kbrl_dev import SharedVecKBRL
     from ranslice.sharding import replica_seeds
     env, cfg, dims, ia, sf = world(n)
-    agent = SharedVecKBRL(n, dims, cfg.n_prbs, budget=BUDGET, max_rounds=1, capacity=CAPACITY, shared_plus=shared_plus)
+    agent = SharedVecKBRL(n, dims, cfg.n_prbs, budget=BUDGET, max_rounds=1, capacity=CAPACITY, shared_plus=shared_plus,
+                          shared_plus_batch=shared_plus_batch or None)
     agent.reset(ia, sf, seeds=replica_seeds(7, 0, n))
     first_step(env, ia)
     done = 0
@@ -96,7 +97,7 @@ def agents_like(shared, n, sizes, capacity=None):
 def child_timing(a):
     import numpy as np
     from ranslice.kbrl_dev import SharedVecKBRL, shared_pool_bytes
-    env, shared, steps = shared_fleet(a.replicas, shared_plus=a.shared_plus)
+    env, shared, steps = shared_fleet(a.replicas, shared_plus=a.shared_plus, shared_plus_batch=a.shared_plus_batch)
     sizes = shared.dictionary_sizes().astype(int)
     out = dict(replicas=a.replicas, steps_trained=steps, dictionary_sizes=sizes.tolist(),
                regime='saturated' if sizes.max() >= CAPACITY else 'filling', unshare=[])
@@ -165,7 +166,7 @@ def child_use(a):
     import numpy as np
     from ranslice.sharding import replica_seeds
     # leg 1
-    env, shared, _ = shared_fleet(a.replicas, steps=a.pretrain, shared_plus=a.shared_plus)
+    env, shared, _ = shared_fleet(a.replicas, steps=a.pretrain, shared_plus=a.shared_plus, shared_plus_batch=a.shared_plus_batch)
     shared_sizes = shared.dictionary_sizes().astype(int)
     env.close()
     index = np.arange(a.agents, dtype=np.int32) % a.replicas
@@ -209,7 +210,8 @@ def child_use(a):
 
 def run(leg, a):
     cmd = ['timeout', '-k', '10', str(a.timeout), sys.executable, os.path.abspath(__file__), '--child', leg, '--replicas', str(a.replicas),
-           '--agents', str(a.agents), '--pretrain', str(a.pretrain), '--tail', str(a.tail)] + (['--shared-plus'] if a.shared_plus else [])
+           '--agents', str(a.agents), '--pretrain', str(a.pretrain), '--tail', str(a.tail)] + (['--shared-plus'] if a.shared_plus else []) + (
+        ['--shared-plus-batch', str(a.shared_plus_batch)] if a.shared_plus_batch else [])
     p = subprocess.run(cmd, capture_output=True, text=True)
     if p.returncode != 0:
         raise SystemExit('%s failed with status %d\n%s' % (' '.join(cmd), p.returncode, p.stderr[-2000:]))
@@ -225,6 +227,8 @@ def main():
     ap.add_argument('--tail', type=int, default=200)
     ap.add_argument('--shared-plus', action='store_true',
                     help='the shared fleet that is grown learns by the margin rule (kb_set_shared_plus); name another --out than the committed record')
+    ap.add_argument('--shared-plus-batch', type=int, default=0, metavar='M',
+                    help='with --shared-plus: growing dictionaries of M landmarks or more take their lists in segments (kb_set_shared_plus_batch)')
     ap.add_argument('--timeout', type=int, default=540)
     ap.add_argument('--only', choices=['timing', 'use'])
     ap.add_argument('--base', default=None, help='with --only: the record whose other leg is kept (default: --out)')
@@ -236,6 +240,8 @@ def main():
     rec = dict(scenario=SCENARIO, budget=BUDGET, shared_capacity=CAPACITY, statistic='one run per leg')
     if a.shared_plus:
         rec['shared_plus'] = True
+    if a.shared_plus_batch:
+        rec['shared_plus_batch'] = a.shared_plus_batch
     if a.only and os.path.exists(a.base or a.out):
         with open(a.base or a.out) as f:
             rec.update(json.load(f))

@@ -67,6 +67,9 @@ CTL_WIDE = {'cpw_list_kernel': 0, 'cpw_plan_kernel': 0, 'cpw_rank1_kernel': 0,
 # it is a variant of.  The scan holds no scratch and keeps the occupancy its __launch_bounds__(64, KB_SCAN_OCC) asks for; the
 # apply may spill no more than the Projectron instance does
 SHARED_PLUS = {'shared_scan_plus_kernel': 'shared_scan_kernel', 'shared_apply_plus_kernel': 'shared_apply_kernel'}
+# the segments of a growing shared dictionary under the margin rule (kb_shared_plus_batch.hip): the wide kernels and
+# begin kernel hold no scratch; the walk and the finishing kernel (both run apply_update_plus) no more than shared_apply_plus_kernel
+SHARED_PLUS_BATCH = ('spb_begin_kernel', 'spb_cols_kernel', 'spb_matvec_kernel', 'spb_gram_kernel', 'spb_walk_kernel', 'spb_finish_kernel')
 KB_SCAN_OCC = 3
 PRODUCTION = ["embb_step_kernelILi16ELb0ELb0ELb1E", "embb_step_kernelILi16ELb0ELb1ELb1E"]   # <16, false, plain | BLOCK, FDIV>
 PLAIN = PRODUCTION[0]          # the instance bench.py's headline runs
@@ -225,6 +228,18 @@ def check(path=LOG):
                 bad.append('%s / %s: occupancy %s / %s < %d waves/SIMD' % (key, base, r.get('Occupancy'), r0.get('Occupancy'), KB_SCAN_OCC))
         elif r.get('ScratchSize', 0) > r0.get('ScratchSize', 0):
             bad.append('%s spills %d B/lane (> %d, the Projectron instance)' % (key, r['ScratchSize'], r0['ScratchSize']))
+    base = [k for k in res if re.search(r'\d' + 'shared_apply_plus_kernel', k)]
+    for key in SHARED_PLUS_BATCH:
+        hit = [k for k in res if re.search(r'\d' + key, k)]
+        if not hit or not base:
+            bad.append('%s: not found in %s' % (key, path))
+            continue
+        r = res[hit[0]]
+        print('%s: VGPRs %s, SGPRs %s, scratch %s B/lane, occupancy %s, LDS %s B' % (key, r.get('VGPRs'), r.get('TotalSGPRs'),
+                                                                                    r.get('ScratchSize'), r.get('Occupancy'), r.get('LDS Size')))
+        limit = res[base[0]].get('ScratchSize', 0) if key in ('spb_walk_kernel', 'spb_finish_kernel') else 0
+        if r.get('ScratchSize', 0) > limit:
+            bad.append('%s spills %d B/lane (> %d)' % (key, r['ScratchSize'], limit))
     return bad
 
 

@@ -48,7 +48,8 @@ def child(a):
     sf = np.concatenate([rng.integers(EMBB_SEC[0], EMBB_SEC[1], size=(n, cfg.n_embb)),
                          rng.integers(MMTC_SEC[0], MMTC_SEC[1], size=(n, cfg.n_mmtc))], axis=1).astype(np.int32)
     env.reset(seeds=replica_seeds(0, 0, n))
-    agent = SharedVecKBRL(n, dims, cfg.n_prbs, budget=BUDGET, max_rounds=MAX_ROUNDS, capacity=CAPACITY, shared_plus=a.shared_plus)
+    agent = SharedVecKBRL(n, dims, cfg.n_prbs, budget=BUDGET, max_rounds=MAX_ROUNDS, capacity=CAPACITY, shared_plus=a.shared_plus,
+                          shared_plus_batch=a.shared_plus_batch or None)
     agent.reset(ia, sf, seeds=replica_seeds(7, 0, n))
     env._check(env.L.rs_step(env.h, np.ascontiguousarray(ia).ctypes.data_as(C.POINTER(C.c_int32)), None, None, None, None))
     windows, shrinks = [], []
@@ -103,7 +104,8 @@ def child(a):
 
 def run(mode, a):
     cmd = ['timeout', '-k', '10', str(a.timeout), sys.executable, os.path.abspath(__file__), '--child', mode, '--replicas', str(a.replicas),
-           '--steps', str(a.steps), '--target', str(a.target), '--every', str(a.every)] + (['--shared-plus'] if a.shared_plus else [])
+           '--steps', str(a.steps), '--target', str(a.target), '--every', str(a.every)] + (['--shared-plus'] if a.shared_plus else []) + (
+        ['--shared-plus-batch', str(a.shared_plus_batch)] if a.shared_plus_batch else [])
     p = subprocess.run(cmd, capture_output=True, text=True)
     if p.returncode != 0:
         raise SystemExit('%s failed with status %d\n%s' % (' '.join(cmd), p.returncode, p.stderr[-2000:]))
@@ -118,6 +120,8 @@ def main():
     ap.add_argument('--target', type=int, default=768)
     ap.add_argument('--every', type=int, default=200)
     ap.add_argument('--shared-plus', action='store_true', help='the rounds learn by the margin rule (kb_set_shared_plus)')
+    ap.add_argument('--shared-plus-batch', type=int, default=0, metavar='M',
+                    help='with --shared-plus: growing dictionaries of M landmarks or more take their lists in segments (kb_set_shared_plus_batch)')
     ap.add_argument('--timeout', type=int, default=400)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'shared_prune_record.json'))
     a = ap.parse_args()
@@ -129,6 +133,8 @@ def main():
     rec = dict(scenario=SCENARIO, budget=BUDGET, max_rounds=MAX_ROUNDS, capacity=CAPACITY, statistic='one run per mode, one MI355X')
     if a.shared_plus:
         rec['shared_plus'] = True
+    if a.shared_plus_batch:
+        rec['shared_plus_batch'] = a.shared_plus_batch
     for mode in ('plain', 'shrink'):   # (one after the other: never two processes on the GPU at once)
         rec[mode] = run(mode, a)
         print(json.dumps({k: v for k, v in rec[mode].items() if k != 'windows'}), flush=True)
