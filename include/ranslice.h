@@ -162,6 +162,24 @@ int rs_kernel_time_ms(rs_handle* h, double* avg_ms, int64_t* launches);
 int rs_kernel_time_stats_ms(rs_handle* h, double out[3], int64_t* launches);
 int rs_set_kernel_timing(rs_handle* h, int enable);
 
+/* Lanes of the step loop.  A lane is a contiguous range of replicas with a stream of its own.  rs_random_actions opens a
+ * handle whose mode engages lanes; until another entry point closes it, rs_random_actions / rs_step_resident (and the loop of
+ * rs_run_random without a graph) enqueue every lane's launches on the lane's stream and do NOT join the lanes between steps,
+ * so one lane's last waves run under another lane's launch.  Every other function that takes the handle first makes h's stream
+ * wait for all lanes; results, counters and the saved state are those of a single-lane handle, bit for bit.
+ * n = 0 (default): automatic -- per-slice L1, no mMTC slices, no allocation trace, 16 lanes per task, an ordered launch,
+ * between one round of waves (4 tasks x SIMDs of the device) and the split step's 49,152 tasks: two lanes (DESIGN.md
+ * section 4; every other handle: one).  n = 1: off.  n >= 2: that many lanes (at most 8, at most one per
+ * replica) wherever the first three conditions hold; RS_EINVAL on multiplexed handles and handles with mMTC slices. */
+int rs_set_lanes(rs_handle* h, int n);
+/* Kernel timing with lanes: the sample of a step (rs_kernel_time_ms, rs_kernel_time_stats_ms) is the SUM of its lanes' bracketed
+ * launch durations -- what a kernel trace adds up; overlapped launches each run longer, so the sum can only understate a
+ * roofline fraction derived from it.  rs_get_lane_info, over the window rs_kernel_time_stats_ms drained last (or the pairs not
+ * drained yet): out[0] = lanes in use, out[1] = sum of the lanes' launch durations per step (ms), out[2] = length of the union of
+ * all bracketed intervals of the window / steps (ms), out[3] = 1 - union / sum, the share of step-kernel time that ran under
+ * another lane's launch.  Timestamps are hipEventElapsedTime against one reference event (rs_set_kernel_timing records it). */
+int rs_get_lane_info(rs_handle* h, double out[4]);
+
 /* Lanes per (replica, eMBB slice) task in the primary step launch: 8, 16 or 32 (default: 32 up to 6144 tasks,
  * 16 above).  Tasks that need
  * more UE lanes are replayed by the 32-lane instance; results are identical for every setting. */

@@ -830,6 +830,7 @@ extern "C" int kb_select_action(kb_handle* k, const float* state, int32_t* actio
 
 extern "C" int kb_step_resident(kb_handle* k, rs_handle* env) {
     if (!k || !env) return RS_EINVAL;
+    if (lanes_close(env) != RS_OK) return RS_EHIP;
     if (!k->is_reset || env->cfg.n_envs != k->cfg.n_envs || env->n_slices != k->cfg.n_slices || env->n_vars != k->nv ||
         env->device != k->device) {
         k->err = "kb_step_resident: agent and environment do not match (or kb_reset missing)";
@@ -897,6 +898,7 @@ static int enqueue_closed_step(kb_handle* k, rs_handle* env) {
 
 extern "C" int kb_run_resident(kb_handle* k, rs_handle* env, int n_steps, int use_graph) {
     if (!k || !env || n_steps < 0) return RS_EINVAL;
+    if (lanes_close(env) != RS_OK) return RS_EHIP;
     int done = 0, rc;
     // (asked here too: a graph captured before the mode changed would replay the update phase without passing kb_step_resident)
     if (k->learning && (rc = kb_refuse_plus(k, "kb_run_resident")) != RS_OK) return rc;
@@ -1544,6 +1546,7 @@ extern "C" int kb_shared_step(kb_handle* k, const float* state, const int32_t* a
 // crosses PCIe.
 extern "C" int kb_shared_step_resident(kb_handle* k, rs_handle* env, int32_t budget, int32_t max_rounds, int32_t* rounds_out) {
     if (!k || !env || budget <= 0 || max_rounds <= 0) return RS_EINVAL;
+    if (lanes_close(env) != RS_OK) return RS_EHIP;
     if (!k->D.shared || !k->is_reset || env->cfg.n_envs != k->cfg.n_envs || env->n_slices != k->cfg.n_slices ||
         env->n_vars != k->nv || env->device != k->device || budget > k->budget_cap) {
         k->err = "kb_shared_step_resident: agent and environment do not match (or not a reset shared-dictionary agent, or budget > 256)";

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -160,6 +161,25 @@ struct rs_handle {
     // device-resident policy interface (rs_policy_io.hip), created by its first call; not a region of the saved state either
     struct PolicyIo* pio = nullptr;
     EventSpans spans;  // kernel timing (rs_set_kernel_timing): a pair around the primary step launches of every step
+    // Lanes of the step loop (rs_set_lanes; lanes_open / lanes_step / lanes_close below).  A lane is a contiguous range of replicas
+    // with a stream of its own; while the handle is OPEN the lanes' launch sequences are not joined between steps.  Lane 0 is
+    // `stream` with d_run, d_ohist and d_pace; the others own one small allocation each, no region of the saved state.
+    struct Lane {
+        hipStream_t stream = nullptr;
+        bool own_stream = false;             // created for the lane (not `stream` or a side stream of the handle)
+        int rep0 = 0, n_rep = 0;             // its replicas (set when the handle opens)
+        int64_t* run = nullptr;              // [4] slot clock and script index, as d_run
+        int* hist = nullptr;                 // [2][RS_ORDER_BINS] as d_ohist
+        unsigned long long* pace = nullptr;  // [4] as d_pace
+        void* mem = nullptr;                 // the allocation behind the three (lanes >= 1)
+        hipEvent_t ev_open = nullptr, ev_done = nullptr;
+    };
+    std::vector<Lane> lanes;
+    int lanes_req = 0;          // rs_set_lanes: 0 automatic, 1 off, n >= 2 forced where the mode is legal
+    int lanes_open = 0;         // 0: closed (everything queued is ordered on `stream`); L >= 2: open with L lanes
+    uint64_t lane_steps = 0;    // steps enqueued since the handle opened
+    hipEvent_t ev_ref = nullptr;  // kernel timing: the event the pairs' timestamps are taken against (rs_get_lane_info)
+    double lane_info[4] = {1.0, 0.0, 0.0, 0.0};  // rs_get_lane_info of the last window drained
     std::string err;
 };
 
@@ -270,12 +290,14 @@ __global__ void reset_kernel(const RsDev* D, RsState S, const uint64_t* seeds_in
     }
 }
 
-// reward of RanSlice.step (ran_slice.py:45-52)
+// reward of RanSlice.step (ran_slice.py:45-52), for the replicas [rep0, rep0 + n_rep): the whole batch, or a lane's (whose `run`
+// is then the lane's own)
 __global__ void finalize_kernel(const RsDev* D, const int32_t* actions, const int32_t* viol, double* reward,
-                                int64_t* run) {
+                                int64_t* run, int rep0, int n_rep) {
     int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= D->n_envs) return;
-    if (r == 0) {  // last kernel of the step: advance the device-side clock and the action-script index
+    if (r >= n_rep) return;
+    r += rep0;
+    if (r == rep0) {  // last kernel of the step: advance the device-side clock and the action-script index
         run[0] += D->slots;
         run[1] += 1;
     }
@@ -296,15 +318,16 @@ __global__ void finalize_kernel(const RsDev* D, const int32_t* actions, const in
 // bench action script: one wave per replica, one categorical draw
 // per PRB over S slices + "unused"; identical to rso_random_actions.
 // With `run` the seed and the step index come from the device-side run state (graph-captured loops).
+// The launch deals the replicas [rep0, rep0 + n_rep) their actions (the draws are keyed by the replica's index in the batch).
 __global__ __launch_bounds__(256) void random_actions_kernel(const RsDev* D, int32_t* actions, uint64_t seed,
-                                                           uint64_t step, const int64_t* run) {
+                                                           uint64_t step, const int64_t* run, int rep0, int n_rep) {
     if (run) {
         step = (uint64_t)run[1];
         seed = (uint64_t)run[2];
     }
     const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= D->n_envs) return;
+    const int r = rep0 + blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rep0 + n_rep) return;
     const int S = D->n_act;
     int my_bin[8];
     int cnt = 0;
@@ -625,6 +648,7 @@ extern "C" int rs_create(const rs_config* cfg, int device, rs_handle** out) {
     if (const char* e = dev_env("RANSLICE_MIXED")) h->mixed = atoi(e);
     if (const char* e = dev_env("RANSLICE_MIXED_UE")) h->mixed_ue = atoi(e);
     if (const char* e = dev_env("RANSLICE_MIXED_LIGHT")) h->mixed_light = atoi(e);
+    if (const char* e = dev_env("RANSLICE_LANES")) h->lanes_req = atoi(e) > 0 ? atoi(e) : 0;  // developer knob: as rs_set_lanes
     if (h->mixed > 0 || h->mixed_light < 256) {
         // the split step's two extra streams exist only on handles that split: several handles side by side (evaluate_grid: six cells)
         // must stay within the hardware queues of the runtime -- with two idle streams more per handle the grid took 220 s against 135
@@ -650,13 +674,17 @@ extern "C" int rs_create(const rs_config* cfg, int device, rs_handle** out) {
 }
 
 static void fork_release(rs_handle* h);
+static int lanes_close(rs_handle* h);
+static void lanes_release(rs_handle* h);
 static void policy_io_release(rs_handle* h);
 static int policy_io_on_reset(rs_handle* h);
 
 extern "C" void rs_destroy(rs_handle* h) {
     if (!h) return;
+    (void)lanes_close(h);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     drop_graph(h);
+    lanes_release(h);
     fork_release(h);
     policy_io_release(h);
     if (guards_on()) check_guards(h->guarded, "rs");
@@ -822,6 +850,7 @@ static int upload_fading(rs_handle* h) {
 
 extern "C" int rs_load_fading(rs_handle* h, int trace_id, const double* data, int rows, int cols) {
     if (!h) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     if (trace_id < 0 || trace_id >= RS_N_TRACES || !data || rows <= 0 || cols <= 0 || h->cfg.n_prbs > 2 * rows) {
         h->err = "rs_load_fading: bad arguments";
         return RS_EINVAL;
@@ -873,6 +902,7 @@ static bool fading_ready(const rs_handle* h) {
 
 extern "C" int rs_reset(rs_handle* h, const uint64_t* seeds, float* obs) {
     if (!h || !seeds) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     HIPCHK(h, hipSetDevice(h->device));
     if (!fading_ready(h)) {
         h->err = "rs_reset: fading traces not loaded";
@@ -921,7 +951,39 @@ static StepArgs step_args(const rs_handle* h) {
     return a;
 }
 
-static int launch_step(rs_handle* h) {
+// one launch of embb_step_kernel's g-lane instance on `lstream`: every task (a.order_cnt < 0) or a.order_cnt tasks of the ranking
+static void launch_embb(const rs_handle* h, StepArgs& a, int g, hipStream_t lstream) {
+    // at most one wave per SIMD of the chip: one task per wave (StepArgs::spread)
+    if (a.order_cnt < 0) a.spread = (h->spread_mode == 1 || (h->spread_mode < 0 && h->n_tasks <= h->spread_max)) ? 1 : 0;
+    const int per_block = a.spread ? 4 : 256 / g;
+    const int n_mine = a.order_cnt >= 0 ? a.order_cnt : h->n_tasks;
+    dim3 grid((n_mine + per_block - 1) / per_block), block(256);
+    const bool tr = h->trace_on;
+    // BLOCK instances hand out the RB pairs of wide contested slices in block rounds; the plain 16-lane one
+    // carries the trip loop alone (rs_set_schedule_hint)
+#define RS_LAUNCH_STEP(G_, TR_, BL_)                                                                              \
+    do {                                                                                                          \
+        if (h->hdev.pf_div_fast)                                                                                  \
+            hipLaunchKernelGGL((embb_step_kernel<G_, TR_, BL_, true>), grid, block, 0, lstream, a);             \
+        else                                                                                                      \
+            hipLaunchKernelGGL((embb_step_kernel<G_, TR_, BL_, false>), grid, block, 0, lstream, a);            \
+    } while (0)
+    if (g == 8) {
+        if (tr) RS_LAUNCH_STEP(8, true, true);
+        else if (h->block_hint) RS_LAUNCH_STEP(8, false, true);
+        else RS_LAUNCH_STEP(8, false, false);
+    } else if (g == 16) {
+        if (tr) RS_LAUNCH_STEP(16, true, true);
+        else if (h->block_hint) RS_LAUNCH_STEP(16, false, true);
+        else RS_LAUNCH_STEP(16, false, false);
+    } else {
+        if (tr) RS_LAUNCH_STEP(32, true, true);
+        else RS_LAUNCH_STEP(32, false, true);
+    }
+#undef RS_LAUNCH_STEP
+}
+
+static int step_ready(rs_handle* h) {
     if (!h->is_reset) {
         h->err = "rs_step: call rs_reset first";
         return RS_ESTATE;
@@ -930,6 +992,13 @@ static int launch_step(rs_handle* h) {
         h->err = "rs_step: slot clock would overflow; reset the environment";
         return RS_ESTATE;
     }
+    return RS_OK;
+}
+
+// one step of a CLOSED handle: the whole batch on h->stream (and the side streams it forks to and joins inside the step)
+static int launch_step(rs_handle* h) {
+    const int ready = step_ready(h);
+    if (ready != RS_OK) return ready;
     if (h->mux) {
         if (h->n_tasks > 0) {
             StepArgs a = step_args(h);
@@ -954,7 +1023,7 @@ static int launch_step(rs_handle* h) {
             hipLaunchKernelGGL(rs::mtc_mux_step_kernel, dim3((unsigned)h->cfg.n_envs), dim3(64), lds, h->stream, ma);
         }
         hipLaunchKernelGGL(finalize_kernel, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, h->stream, h->ddev,
-                           h->d_actions, h->d_viol, h->d_reward, h->d_run);
+                           h->d_actions, h->d_viol, h->d_reward, h->d_run, 0, h->cfg.n_envs);
         HIPCHK(h, hipGetLastError());
         h->clock += h->cfg.slots_per_step;
         h->steps += 1;
@@ -976,36 +1045,7 @@ static int launch_step(rs_handle* h) {
         a.pace = h->d_pace;
         a.order_cnt = -1;
         hipStream_t lstream = h->stream;
-        auto launch = [&](int g) {
-            // at most one wave per SIMD of the chip: one task per wave (StepArgs::spread)
-            if (a.order_cnt < 0) a.spread = (h->spread_mode == 1 || (h->spread_mode < 0 && h->n_tasks <= h->spread_max)) ? 1 : 0;
-            const int per_block = a.spread ? 4 : 256 / g;
-            const int n_mine = a.order_cnt >= 0 ? a.order_cnt : h->n_tasks;
-            dim3 grid((n_mine + per_block - 1) / per_block), block(256);
-            const bool tr = h->trace_on;
-            // BLOCK instances hand out the RB pairs of wide contested slices in block rounds; the plain 16-lane one
-            // carries the trip loop alone (rs_set_schedule_hint)
-#define RS_LAUNCH_STEP(G_, TR_, BL_)                                                                              \
-    do {                                                                                                          \
-        if (h->hdev.pf_div_fast)                                                                                  \
-            hipLaunchKernelGGL((embb_step_kernel<G_, TR_, BL_, true>), grid, block, 0, lstream, a);             \
-        else                                                                                                      \
-            hipLaunchKernelGGL((embb_step_kernel<G_, TR_, BL_, false>), grid, block, 0, lstream, a);            \
-    } while (0)
-            if (g == 8) {
-                if (tr) RS_LAUNCH_STEP(8, true, true);
-                else if (h->block_hint) RS_LAUNCH_STEP(8, false, true);
-                else RS_LAUNCH_STEP(8, false, false);
-            } else if (g == 16) {
-                if (tr) RS_LAUNCH_STEP(16, true, true);
-                else if (h->block_hint) RS_LAUNCH_STEP(16, false, true);
-                else RS_LAUNCH_STEP(16, false, false);
-            } else {
-                if (tr) RS_LAUNCH_STEP(32, true, true);
-                else RS_LAUNCH_STEP(32, false, true);
-            }
-#undef RS_LAUNCH_STEP
-        };
+        auto launch = [&](int g) { launch_embb(h, a, g, lstream); };
         // primary launch with h->group lanes per task; tasks that do not fit raise their redo flag and are
         // replayed from their untouched state by the 32-lane instance (waves without flagged tasks exit)
         int seg_head = 0, seg_light = 0;
@@ -1024,11 +1064,11 @@ static int launch_step(rs_handle* h) {
             const int seg_mid = h->n_tasks - seg_head - seg_light;
             hipLaunchKernelGGL(order_key_kernel, dim3(nb), dim3(256), 0, h->stream, h->ddev, h->d_st, h->d_actions,
                                h->order_mode, h->d_ohist + par * RS_ORDER_BINS, h->d_oslot, make_int4(h->key_w[0], h->key_w[1], h->key_w[2], h->key_w[3]),
-                               split ? h->mixed_ue : 0);
+                               split ? h->mixed_ue : 0, 0, h->n_tasks, 0);
             hipLaunchKernelGGL(order_scatter_kernel, dim3(nb), dim3(256), 0, h->stream, h->ddev,
                                h->d_ohist + par * RS_ORDER_BINS, h->d_ohist + (1 - par) * RS_ORDER_BINS, h->d_oslot,
                                h->d_order, h->order_mode > 3 ? h->order_pair : 0, 64 / h->group,  // modes 4.. = keys 1.. with heavy+light pairing
-                               h->snake == 1 ? h->spread_max : h->snake, h->snake_mask, h->rot_mask, seg_head, seg_head + seg_mid);
+                               h->snake == 1 ? h->spread_max : h->snake, h->snake_mask, h->rot_mask, seg_head, seg_head + seg_mid, 0, h->n_tasks);
             a.order = h->d_order;
         }
         // the event pair brackets the step launches of the step (without a split: what rocprofv3 lists as embb_step_kernel<G,...>)
@@ -1083,7 +1123,7 @@ static int launch_step(rs_handle* h) {
     if (forked) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
     else if (h->cfg.n_mmtc > 0) mtc_step(h, &h->mst, h->stream);
     hipLaunchKernelGGL(finalize_kernel, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, h->stream, h->ddev,
-                       h->d_actions, h->d_viol, h->d_reward, h->d_run);
+                       h->d_actions, h->d_viol, h->d_reward, h->d_run, 0, h->cfg.n_envs);
     HIPCHK(h, hipGetLastError());
     h->clock += h->cfg.slots_per_step;
     h->steps += 1;
@@ -1096,6 +1136,199 @@ static int launch_step(rs_handle* h) {
 static int auto_hint(const rs_handle* h) {
     const int gran = h->cfg.pf_granularity > 0 ? h->cfg.pf_granularity : 1;
     return h->cfg.n_prbs / (h->n_slices + 1) >= RS_HINT_PAIRS * gran ? 1 : 0;
+}
+
+// ------------------------------------------------------------------ lanes of the step loop
+// Replicas are independent, so step n + 1 of one half of the batch needs nothing from step n of the other half.  An OPEN handle
+// steps its lanes -- contiguous replica ranges -- as launch sequences of their own, each on its own stream and NOT joined between
+// steps: one lane's tail of slow waves runs under the other's bulk.  Only the action script opens a handle (lanes_actions), and
+// only rs_step_resident and the loop of rs_run_random step an open one (lanes_step); every other entry point calls lanes_close
+// first, after which everything queued is ordered on h->stream and the handle holds what a single-lane handle would.
+// Lanes of the handles that engage them by themselves (lanes_wanted).  4096 replicas of scenario 0: 0.835 ms per step on one lane,
+// 0.800 on two; a half-batch launch still takes 0.76 ms (0.80 whole: the slowest wave's chain, not the wave count, sets it), the
+// two overlap all but entirely, and a lane's own sequence of launches is then the bound -- which more lanes cannot shorten
+// (four: no faster where they overlap, 1.53 ms where they shared hardware queues; profiles/step_lanes_ab.txt).
+static const int kLanesAuto = 2;
+static const int kLanesMax = 8;
+
+static int lanes_wanted(const rs_handle* h) {
+    const bool legal = !h->mux && h->cfg.n_mmtc == 0 && !h->trace_on && h->n_tasks > 0 && h->order_mode > 0 && h->mixed == 0 &&
+                       h->mixed_light >= 256;
+    if (!legal || h->lanes_req == 1) return 1;
+    int want = h->lanes_req;
+    // by itself: the 16-lane step of a batch that is at least one round of waves (four tasks to a wave, one wave per SIMD) and
+    // stays below the split step's threshold
+    if (want == 0) want = (h->group == 16 && h->n_tasks < 49152 && h->n_tasks >= 4 * h->spread_max) ? kLanesAuto : 1;
+    if (want > h->cfg.n_envs) want = h->cfg.n_envs;  // (no lane without a replica)
+    return want < kLanesMax ? want : kLanesMax;
+}
+
+// streams, events and private words of lanes [0, L)
+static int lanes_ensure(rs_handle* h, int L) {
+    while ((int)h->lanes.size() < L) {
+        const int l = (int)h->lanes.size();
+        rs_handle::Lane ln;
+        if (l == 0) {
+            ln.stream = h->stream;
+            ln.run = h->d_run;
+            ln.hist = h->d_ohist;
+            ln.pace = h->d_pace;
+        } else {
+            // streams that share a hardware queue run one after the other, and the runtime deals its few queues out to the streams as
+            // they are created: the handle's side streams were created right after h->stream and are idle in this mode (no mMTC
+            // slices, no split step), so they come first; further lanes get streams of their own
+            hipStream_t idle[3] = {h->side, h->side2, h->side3};
+            for (int k = 0, seen = 0; k < 3 && !ln.stream; ++k)
+                if (idle[k] && ++seen == l) ln.stream = idle[k];
+            if (!ln.stream) {
+                HIPCHK(h, hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
+                ln.own_stream = true;
+            }
+            const size_t bytes = sizeof(int64_t) * 4 + sizeof(unsigned long long) * 4 + sizeof(int) * 2 * RS_ORDER_BINS;
+            const hipError_t e = hipMalloc(&ln.mem, bytes);
+            if (e != hipSuccess) {
+                if (ln.own_stream) (void)hipStreamDestroy(ln.stream);
+                h->err = std::string("hipMalloc (lane): ") + hipGetErrorString(e);
+                return RS_EHIP;
+            }
+            ln.run = (int64_t*)ln.mem;
+            ln.pace = (unsigned long long*)(ln.run + 4);
+            ln.hist = (int*)(ln.pace + 4);
+        }
+        h->lanes.push_back(ln);
+    }
+    return RS_OK;
+}
+
+static void lanes_release(rs_handle* h) {
+    for (auto& ln : h->lanes) {
+        if (ln.ev_open) (void)hipEventDestroy(ln.ev_open);
+        if (ln.ev_done) (void)hipEventDestroy(ln.ev_done);
+        if (ln.own_stream) (void)hipStreamDestroy(ln.stream);
+        if (ln.mem) (void)hipFree(ln.mem);
+    }
+    h->lanes.clear();
+    if (h->ev_ref) (void)hipEventDestroy(h->ev_ref);
+    h->ev_ref = nullptr;
+}
+
+// open the handle if its mode engages lanes: the lane streams wait for what is queued on h->stream and take their copies of the
+// run words and the pace, and zeroed order counters
+static int lanes_open(rs_handle* h) {
+    if (h->lanes_open) return RS_OK;
+    const int L = lanes_wanted(h);
+    if (L < 2) return RS_OK;
+    int rc = lanes_ensure(h, L);
+    if (rc != RS_OK) return rc;
+    const int N = h->cfg.n_envs;
+    for (int l = 0, r = 0; l < L; ++l) {
+        rs_handle::Lane& ln = h->lanes[l];
+        ln.rep0 = r;
+        ln.n_rep = N / L + (l < N % L ? 1 : 0);
+        r += ln.n_rep;
+        if (l == 0) continue;
+        // (on h->stream, ahead of the edge: lane 0's first step advances d_run, so a copy taken on the lane's own stream could
+        // come too late; the lane's words are free, h->stream waited for the lane when the handle closed)
+        HIPCHK(h, hipMemcpyAsync(ln.run, h->d_run, sizeof(int64_t) * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(ln.pace, h->d_pace, sizeof(unsigned long long) * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemsetAsync(ln.hist, 0, sizeof(int) * 2 * RS_ORDER_BINS, h->stream));
+    }
+    for (int l = 1; l < L; ++l)
+        if ((rc = stream_after(h, &h->lanes[l].ev_open, h->stream, h->lanes[l].stream)) != RS_OK) return rc;
+    h->lanes_open = L;
+    h->lane_steps = 0;
+    return RS_OK;
+}
+
+// Close the handle: h->stream waits for every lane's last launch.  The lanes have advanced the same number of steps, so d_run
+// (lane 0's) is right.  The launch-order scratch -- regions of the saved state -- then holds per-lane rankings; it is ranked
+// again over the whole batch from the bins the lanes' rankings left in d_oslot, so that a closed handle holds what a single-lane
+// handle holds after the same steps.  Nothing to do on a closed handle.
+static int lanes_close(rs_handle* h) {
+    if (!h || !h->lanes_open) return RS_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int L = h->lanes_open;
+    h->lanes_open = 0;
+    for (int l = 1; l < L; ++l) {
+        const int rc = stream_after(h, &h->lanes[l].ev_done, h->lanes[l].stream, h->stream);
+        if (rc != RS_OK) return rc;
+    }
+    if (h->lane_steps > 0) {
+        const int par = h->order_par ^ 1;  // the parity the last step counted into
+        const unsigned nb = (unsigned)((h->n_tasks + 255) / 256);
+        HIPCHK(h, hipMemsetAsync(h->d_ohist + par * RS_ORDER_BINS, 0, sizeof(int) * RS_ORDER_BINS, h->stream));
+        hipLaunchKernelGGL(order_key_kernel, dim3(nb), dim3(256), 0, h->stream, h->ddev, h->d_st, h->d_actions, h->order_mode,
+                           h->d_ohist + par * RS_ORDER_BINS, h->d_oslot, make_int4(h->key_w[0], h->key_w[1], h->key_w[2], h->key_w[3]),
+                           0, 0, h->n_tasks, 1);
+        hipLaunchKernelGGL(order_scatter_kernel, dim3(nb), dim3(256), 0, h->stream, h->ddev, h->d_ohist + par * RS_ORDER_BINS,
+                           h->d_ohist + (1 - par) * RS_ORDER_BINS, h->d_oslot, h->d_order, h->order_mode > 3 ? h->order_pair : 0,
+                           64 / h->group, h->snake == 1 ? h->spread_max : h->snake, h->snake_mask, h->rot_mask, 0, h->n_tasks, 0,
+                           h->n_tasks);
+        HIPCHK(h, hipGetLastError());
+    }
+    return RS_OK;
+}
+
+// the action script's draw of a step: per lane on an open handle (which this call opens where the mode engages lanes), else the
+// whole batch on h->stream.  scripted: seed and step index from the run words (the lane's own), as rs_run_random sets them
+static int lanes_actions(rs_handle* h, uint64_t seed, uint64_t step_index, bool scripted) {
+    const int rc = lanes_open(h);
+    if (rc != RS_OK) return rc;
+    const int L = h->lanes_open ? h->lanes_open : 1;
+    for (int l = 0; l < L; ++l) {
+        const int rep0 = h->lanes_open ? h->lanes[l].rep0 : 0, n_rep = h->lanes_open ? h->lanes[l].n_rep : h->cfg.n_envs;
+        const int64_t* run = !scripted ? nullptr : (h->lanes_open ? h->lanes[l].run : h->d_run);
+        hipLaunchKernelGGL(random_actions_kernel, dim3((n_rep + 3) / 4), dim3(256), 0, h->lanes_open ? h->lanes[l].stream : h->stream,
+                           h->ddev, h->d_actions, seed, step_index, run, rep0, n_rep);
+    }
+    HIPCHK(h, hipGetLastError());
+    return RS_OK;
+}
+
+// one step: launch_step on a closed handle; on an open one every lane's order pair, primary launch, 32-lane replay and finalize
+// over its own tasks, on its own stream
+static int lanes_step(rs_handle* h) {
+    if (!h->lanes_open) return launch_step(h);
+    const int ready = step_ready(h);
+    if (ready != RS_OK) return ready;
+    const int L = h->lanes_open, par = h->order_par;
+    h->order_par ^= 1;
+    for (int l = 0; l < L; ++l) {
+        const rs_handle::Lane& ln = h->lanes[l];
+        const int task0 = ln.rep0 * h->cfg.n_embb, cnt = ln.n_rep * h->cfg.n_embb;
+        const unsigned nb = (unsigned)((cnt + 255) / 256);
+        hipLaunchKernelGGL(order_key_kernel, dim3(nb), dim3(256), 0, ln.stream, h->ddev, h->d_st, h->d_actions, h->order_mode,
+                           ln.hist + par * RS_ORDER_BINS, h->d_oslot, make_int4(h->key_w[0], h->key_w[1], h->key_w[2], h->key_w[3]), 0,
+                           task0, cnt, 0);
+        hipLaunchKernelGGL(order_scatter_kernel, dim3(nb), dim3(256), 0, ln.stream, h->ddev, ln.hist + par * RS_ORDER_BINS,
+                           ln.hist + (1 - par) * RS_ORDER_BINS, h->d_oslot, h->d_order, h->order_mode > 3 ? h->order_pair : 0,
+                           64 / h->group, h->snake == 1 ? h->spread_max : h->snake, h->snake_mask, h->rot_mask, 0, cnt, task0, cnt);
+        StepArgs a = step_args(h);
+        a.run = ln.run;
+        a.sections = h->d_sections;
+        a.redo = h->d_redo;
+        a.pace = ln.pace;
+        a.order = h->d_order;
+        a.order_off = task0;
+        a.order_cnt = cnt;
+        a.spread = (h->spread_mode == 1 || (h->spread_mode < 0 && h->n_tasks <= h->spread_max)) ? 1 : 0;
+        // the pair of a lane is tagged lane | L << 8: a step's sample is the sum over its lanes (rs_kernel_time_stats_ms)
+        hipEvent_t e1;
+        HIPCHK(h, h->spans.begin(ln.stream, l | (L << 8), &e1));
+        launch_embb(h, a, h->group, ln.stream);
+        if (e1) HIPCHK(h, hipEventRecord(e1, ln.stream));
+        if (h->group < 32) {  // (the replay walks the lane's stretch of the ranking: any order of its tasks will do)
+            a.replay = 1;
+            launch_embb(h, a, 32, ln.stream);
+        }
+        hipLaunchKernelGGL(finalize_kernel, dim3((ln.n_rep + 255) / 256), dim3(256), 0, ln.stream, h->ddev, h->d_actions, h->d_viol,
+                           h->d_reward, ln.run, ln.rep0, ln.n_rep);
+    }
+    HIPCHK(h, hipGetLastError());
+    h->clock += h->cfg.slots_per_step;
+    h->steps += 1;
+    h->lane_steps += 1;
+    return RS_OK;
 }
 
 static int check_errors(rs_handle* h) {
@@ -1115,6 +1348,7 @@ static int check_errors(rs_handle* h) {
 extern "C" int rs_fetch(rs_handle* h, int32_t* actions, float* obs, double* reward, int32_t* labels,
                         int32_t* violations) {
     if (!h) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     HIPCHK(h, hipSetDevice(h->device));
     const size_t N = (size_t)h->cfg.n_envs, S = (size_t)h->n_slices;
     if (actions) HIPCHK(h, hipMemcpyAsync(actions, h->d_actions, sizeof(int32_t) * N * S, hipMemcpyDeviceToHost, h->stream));
@@ -1128,6 +1362,7 @@ extern "C" int rs_fetch(rs_handle* h, int32_t* actions, float* obs, double* rewa
 extern "C" int rs_step(rs_handle* h, const int32_t* actions, float* obs, double* reward, int32_t* labels,
                        int32_t* violations) {
     if (!h || !actions) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     HIPCHK(h, hipSetDevice(h->device));
     const size_t N = (size_t)h->cfg.n_envs, S = (size_t)h->n_slices;
     size_t wide = 0;  // eMBB slices wide enough for block rounds of the PF allocation
@@ -1163,7 +1398,7 @@ extern "C" int rs_step(rs_handle* h, const int32_t* actions, float* obs, double*
 extern "C" int rs_step_resident(rs_handle* h) {
     if (!h) return RS_EINVAL;
     HIPCHK(h, hipSetDevice(h->device));
-    return launch_step(h);
+    return lanes_step(h);
 }
 
 extern "C" int rs_random_actions(rs_handle* h, uint64_t seed, uint64_t step_index) {
@@ -1174,10 +1409,7 @@ extern "C" int rs_random_actions(rs_handle* h, uint64_t seed, uint64_t step_inde
         return RS_EINVAL;
     }
     if (h->cfg.n_prbs > 512) return RS_EINVAL;
-    hipLaunchKernelGGL(random_actions_kernel, dim3((h->cfg.n_envs + 3) / 4), dim3(256), 0, h->stream, h->ddev,
-                       h->d_actions, seed, step_index, (const int64_t*)nullptr);
-    HIPCHK(h, hipGetLastError());
-    return RS_OK;
+    return lanes_actions(h, seed, step_index, false);
 }
 
 static void drop_graph(rs_handle* h) {
@@ -1188,10 +1420,15 @@ static void drop_graph(rs_handle* h) {
     h->graph = nullptr;
 }
 
-// one step of the on-device action script: actions from (run[2], run[1]), then RanSlice.step
-static int enqueue_scripted_step(rs_handle* h) {
+// one step of the on-device action script: actions from (run[2], run[1]), then RanSlice.step.  On h->stream alone (what the
+// graph captures), or `laned`: on the lanes where the handle's mode engages them
+static int enqueue_scripted_step(rs_handle* h, bool laned) {
+    if (laned) {
+        const int rc = lanes_actions(h, 0, 0, true);
+        return rc != RS_OK ? rc : lanes_step(h);
+    }
     hipLaunchKernelGGL(random_actions_kernel, dim3((h->cfg.n_envs + 3) / 4), dim3(256), 0, h->stream, h->ddev,
-                       h->d_actions, (uint64_t)0, (uint64_t)0, (const int64_t*)h->d_run);
+                       h->d_actions, (uint64_t)0, (uint64_t)0, (const int64_t*)h->d_run, 0, h->cfg.n_envs);
     return launch_step(h);
 }
 
@@ -1214,11 +1451,12 @@ extern "C" int rs_run_random(rs_handle* h, uint64_t seed, uint64_t step_index0, 
         h->err = "rs_run_random: slot clock would overflow; reset the environment";
         return RS_ESTATE;
     }
-    hipLaunchKernelGGL(set_run_kernel, dim3(1), dim3(1), 0, h->stream, h->d_run, seed, step_index0);
     int done = 0, rc;
+    if ((rc = lanes_close(h)) != RS_OK) return rc;  // (the script's seed and index go into d_run; the loop below opens again)
+    hipLaunchKernelGGL(set_run_kernel, dim3(1), dim3(1), 0, h->stream, h->d_run, seed, step_index0);
     if (use_graph && !h->spans.on && n_steps >= 2) {
         if (h->gexec && h->graph_par != h->order_par) {  // realign with the parity the graph was captured at
-            if ((rc = enqueue_scripted_step(h)) != RS_OK) return rc;
+            if ((rc = enqueue_scripted_step(h, false)) != RS_OK) return rc;
             done += 1;
         }
         if (!h->gexec) {
@@ -1226,8 +1464,8 @@ extern "C" int rs_run_random(rs_handle* h, uint64_t seed, uint64_t step_index0, 
             const uint64_t steps0 = h->steps;
             h->graph_par = h->order_par;
             HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-            const int rc1 = enqueue_scripted_step(h);
-            const int rc2 = rc1 == RS_OK ? enqueue_scripted_step(h) : rc1;
+            const int rc1 = enqueue_scripted_step(h, false);
+            const int rc2 = rc1 == RS_OK ? enqueue_scripted_step(h, false) : rc1;
             const hipError_t ec = hipStreamEndCapture(h->stream, &h->graph);
             h->clock = clock0;
             h->steps = steps0;
@@ -1246,13 +1484,15 @@ extern "C" int rs_run_random(rs_handle* h, uint64_t seed, uint64_t step_index0, 
             done += 2;
         }
     }
-    for (; done < n_steps; ++done)
-        if ((rc = enqueue_scripted_step(h)) != RS_OK) return rc;
+    // without a graph: the lane-aware pair (a remainder behind graph replays stays on h->stream, where they ran)
+    for (const bool laned = done == 0; done < n_steps; ++done)
+        if ((rc = enqueue_scripted_step(h, laned)) != RS_OK) return rc;
     return RS_OK;
 }
 
 extern "C" int rs_get_info(rs_handle* h, double* info) {
     if (!h || !info) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpyAsync(info, h->d_info, sizeof(double) * (size_t)h->cfg.n_envs * h->n_ran * 10,
                              hipMemcpyDeviceToHost, h->stream));
@@ -1262,6 +1502,7 @@ extern "C" int rs_get_info(rs_handle* h, double* info) {
 
 extern "C" int rs_set_alloc_trace(rs_handle* h, int enable) {
     if (!h) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     HIPCHK(h, hipSetDevice(h->device));
     if (enable && !h->d_trace) {
         size_t n = (size_t)h->n_tasks * h->cfg.slots_per_step * RS_GROUP;
@@ -1275,6 +1516,7 @@ extern "C" int rs_set_alloc_trace(rs_handle* h, int enable) {
 
 extern "C" int rs_get_alloc_trace(rs_handle* h, rs_alloc_rec* out) {
     if (!h || !out || !h->d_trace) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     HIPCHK(h, hipSetDevice(h->device));
     size_t n = (size_t)h->n_tasks * h->cfg.slots_per_step * RS_GROUP;
     if (h->mux) n = (size_t)h->cfg.n_envs * h->cfg.slots_per_step * RS_MUX_UE;  // [n_envs][slots][64]
@@ -1285,6 +1527,7 @@ extern "C" int rs_get_alloc_trace(rs_handle* h, rs_alloc_rec* out) {
 
 extern "C" int rs_get_counters(rs_handle* h, uint64_t counters[4]) {
     if (!h || !counters) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemsetAsync(h->d_counter_sum, 0, sizeof(uint64_t) * 4, h->stream));
     if (h->n_tasks > 0)
@@ -1298,6 +1541,7 @@ extern "C" int rs_get_counters(rs_handle* h, uint64_t counters[4]) {
 
 extern "C" int rs_get_rx_stats(rs_handle* h, uint64_t out[3]) {
     if (!h || !out) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     uint64_t c[4];
     const int rc = rs_get_counters(h, c);
     if (rc != RS_OK) return rc;
@@ -1315,6 +1559,7 @@ extern "C" int rs_get_rx_stats(rs_handle* h, uint64_t out[3]) {
 // switches BLOCK on for the environment it drives).  A scheduling hint only: results are identical.
 extern "C" int rs_set_schedule_hint(rs_handle* h, int mode) {
     if (!h) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     h->hint_auto = mode < 0;
     h->block_hint = mode < 0 ? auto_hint(h) : (mode ? 1 : 0);
     drop_graph(h);
@@ -1323,6 +1568,7 @@ extern "C" int rs_set_schedule_hint(rs_handle* h, int mode) {
 
 extern "C" int rs_set_group_size(rs_handle* h, int lanes) {
     if (!h || (lanes != 8 && lanes != 16 && lanes != 32)) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     h->group = lanes;
     drop_graph(h);
     return RS_OK;
@@ -1331,6 +1577,7 @@ extern "C" int rs_set_group_size(rs_handle* h, int lanes) {
 // cycle sums per code section of embb_step_kernel; all zero unless built with -DRS_SECTION_PROFILE
 extern "C" int rs_get_section_profile(rs_handle* h, uint64_t out[16]) {
     if (!h || !out) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpyAsync(out, h->d_sections, sizeof(uint64_t) * 16, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1339,6 +1586,7 @@ extern "C" int rs_get_section_profile(rs_handle* h, uint64_t out[16]) {
 
 extern "C" int rs_get_task_profile(rs_handle* h, uint64_t* out) {
     if (!h || !out) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     HIPCHK(h, hipSetDevice(h->device));
     // [n_tasks][4] per-task records followed by the 16 section sums of the slowest wave seen so far
     HIPCHK(h, hipMemcpyAsync(out, h->d_sections + 16, sizeof(uint64_t) * (4 * (size_t)h->n_tasks + 16),
@@ -1349,22 +1597,65 @@ extern "C" int rs_get_task_profile(rs_handle* h, uint64_t* out) {
 
 extern "C" int rs_set_kernel_timing(rs_handle* h, int enable) {
     if (!h) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     h->spans.on = enable != 0;
     h->spans.reset();
+    if (enable) {  // the pairs' timestamps are taken against this event (rs_get_lane_info)
+        HIPCHK(h, hipSetDevice(h->device));
+        if (!h->ev_ref) HIPCHK(h, hipEventCreate(&h->ev_ref));
+        HIPCHK(h, hipEventRecord(h->ev_ref, h->stream));
+    }
+    return RS_OK;
+}
+
+// rs_get_lane_info of the pairs taken since the last drain (the streams must have been waited for; the pool stays as it is)
+static int lane_window(rs_handle* h, double out[4]) {
+    std::vector<std::pair<double, double>> iv;
+    double sum = 0.0;
+    int64_t steps = 0;
+    for (size_t i = 0; i < h->spans.used && h->ev_ref; ++i) {
+        const EventSpans::Span& sp = h->spans.spans[i];
+        float t0 = 0.f, t1 = 0.f;
+        HIPCHK(h, hipEventElapsedTime(&t0, h->ev_ref, sp.e0));
+        HIPCHK(h, hipEventElapsedTime(&t1, h->ev_ref, sp.e1));
+        iv.emplace_back((double)t0, (double)t1);
+        sum += (double)t1 - (double)t0;
+        const int L = sp.kind >> 8, l = sp.kind & 255;
+        steps += (L == 0 || l == L - 1) ? 1 : 0;
+    }
+    std::sort(iv.begin(), iv.end());
+    double uni = 0.0, hi = 0.0;
+    for (size_t i = 0; i < iv.size(); ++i) {  // length of the union of the intervals
+        const double lo = (i == 0 || iv[i].first > hi) ? iv[i].first : hi;
+        if (iv[i].second > lo) uni += iv[i].second - lo;
+        hi = (i == 0 || iv[i].second > hi) ? iv[i].second : hi;
+    }
+    if (uni > sum) uni = sum;  // (the same terms added in another order)
+    out[0] = (double)lanes_wanted(h);
+    out[1] = steps ? sum / (double)steps : 0.0;
+    out[2] = steps ? uni / (double)steps : 0.0;
+    out[3] = sum > 0.0 ? 1.0 - uni / sum : 0.0;
+    if (out[3] < 0.0) out[3] = 0.0;  // (single-precision timestamps of back-to-back pairs)
     return RS_OK;
 }
 
 extern "C" int rs_kernel_time_stats_ms(rs_handle* h, double out[3], int64_t* launches) {
     if (!h || !out) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    double tot = 0.0, mn = 0.0, mx = 0.0;
+    if (h->spans.used > 0 && lane_window(h, h->lane_info) != RS_OK) return RS_EHIP;
+    double tot = 0.0, mn = 0.0, mx = 0.0, step_ms = 0.0;
     int64_t n = 0;
-    HIPCHK(h, h->spans.drain([&](int, double ms) {
-        tot += ms;
-        mn = (n == 0 || ms < mn) ? ms : mn;
-        mx = ms > mx ? ms : mx;
+    // one sample per step: the pair of a closed step, or the sum over the lanes' pairs of a laned one (tagged lane | L << 8)
+    HIPCHK(h, h->spans.drain([&](int kind, double ms) {
+        step_ms += ms;
+        if ((kind >> 8) != 0 && (kind & 255) != (kind >> 8) - 1) return;
+        tot += step_ms;
+        mn = (n == 0 || step_ms < mn) ? step_ms : mn;
+        mx = step_ms > mx ? step_ms : mx;
         n += 1;
+        step_ms = 0.0;
     }));
     out[0] = n ? tot / (double)n : 0.0;
     out[1] = mn;
@@ -1373,8 +1664,33 @@ extern "C" int rs_kernel_time_stats_ms(rs_handle* h, double out[3], int64_t* lau
     return RS_OK;
 }
 
+extern "C" int rs_get_lane_info(rs_handle* h, double out[4]) {
+    if (!h || !out) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->spans.used > 0) {  // a window not drained yet: measured here; else the one rs_kernel_time_stats_ms drained last
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (lane_window(h, h->lane_info) != RS_OK) return RS_EHIP;
+    }
+    memcpy(out, h->lane_info, sizeof(double) * 4);
+    out[0] = (double)lanes_wanted(h);
+    return RS_OK;
+}
+
+extern "C" int rs_set_lanes(rs_handle* h, int n) {
+    if (!h || n < 0) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
+    if (n >= 2 && (h->mux || h->cfg.n_mmtc > 0)) {
+        h->err = "rs_set_lanes: no lanes for multiplexed handles or handles with mMTC slices";
+        return RS_EINVAL;
+    }
+    h->lanes_req = n;
+    return RS_OK;
+}
+
 extern "C" int rs_kernel_time_ms(rs_handle* h, double* avg_ms, int64_t* launches) {
     if (!h || !avg_ms) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     double st[3];
     const int rc = rs_kernel_time_stats_ms(h, st, launches);
     if (rc == RS_OK) *avg_ms = st[0];
@@ -1383,6 +1699,7 @@ extern "C" int rs_kernel_time_ms(rs_handle* h, double* avg_ms, int64_t* launches
 
 extern "C" int rs_synchronize(rs_handle* h) {
     if (!h) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RS_OK;
@@ -1413,12 +1730,14 @@ static uint64_t rs_cfg_hash(const rs_handle* h) {
 }
 extern "C" int rs_state_bytes(rs_handle* h, uint64_t* bytes) {
     if (!h || !bytes) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     uint64_t t = sizeof(rs_state_header);
     for (auto& r : h->regions) t += r.second;
     *bytes = t;
     return RS_OK;
 }
 extern "C" int rs_save_state(rs_handle* h, void* blob, uint64_t bytes) {
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     uint64_t need = 0;
     if (!h || !blob || rs_state_bytes(h, &need) != RS_OK) return RS_EINVAL;
     if (bytes < need) {
@@ -1438,6 +1757,7 @@ extern "C" int rs_save_state(rs_handle* h, void* blob, uint64_t bytes) {
     return RS_OK;
 }
 extern "C" int rs_load_state(rs_handle* h, const void* blob, uint64_t bytes) {
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     uint64_t need = 0;
     if (!h || !blob || rs_state_bytes(h, &need) != RS_OK) return RS_EINVAL;
     rs_state_header hd;

@@ -221,6 +221,8 @@ static int fork_adopt(rs_handle* dst, const rs_handle* src) {
 
 extern "C" int rs_fork(rs_handle* dst, rs_handle* src, const int32_t* src_index) {
     if (!dst || !src || !src_index) return RS_EINVAL;
+    if (lanes_close(dst) != RS_OK) return RS_EHIP;
+    if (lanes_close(src) != RS_OK) return RS_EHIP;
     if (dst == src) {
         dst->err = "rs_fork: source and destination must be different handles";
         return RS_EINVAL;
@@ -283,6 +285,7 @@ static void fork_release(rs_handle* h) {
 
 extern "C" int rs_set_lookahead(rs_handle* h, int max_branches) {
     if (!h) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     if (max_branches < 0 || (max_branches > 0 && max_branches < h->cfg.n_prbs + 1)) {
         h->err = "rs_set_lookahead: max_branches must be 0 or at least n_prbs + 1";
         return RS_EINVAL;
@@ -299,6 +302,7 @@ extern "C" int rs_set_lookahead(rs_handle* h, int max_branches) {
 
 extern "C" int rs_set_clairvoyant_fallback(rs_handle* h, int mode) {
     if (!h || mode < 0 || mode > 1) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     h->la_widest = mode;
     return RS_OK;
 }
@@ -353,6 +357,7 @@ static int ensure_branches(rs_handle* h) {
 extern "C" int rs_step_clairvoyant(rs_handle* h, int32_t* actions_out, float* obs, double* reward, int32_t* labels,
                                    int32_t* violations) {
     if (!h) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->is_reset) {
         h->err = "rs_step_clairvoyant: call rs_reset first";

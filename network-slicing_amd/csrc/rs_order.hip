@@ -40,16 +40,21 @@ __device__ __forceinline__ int order_key(int mode, int n_ue, int n_prb, int cost
 
 // hist: this step's bin counters (zero on entry); slot[task] = bin | rank-in-bin << 11.  Ranks are taken inside the
 // block first (LDS atomics), then one global atomic per (block, occupied bin) reserves the block's range.
+// The launch ranks the tasks [task0, task0 + task_cnt) among themselves (a lane of the step loop, rs_api.hip; the whole batch is
+// 0, n_tasks).  rebin: the bins are the ones a ranking over other ranges left in `slot`, not recomputed (the state has moved on).
 __global__ __launch_bounds__(256) void order_key_kernel(const RsDev* __restrict__ D, const RsState* __restrict__ Sp,
                                                         const int32_t* __restrict__ actions, int mode, int* hist,
-                                                        uint64_t* slot, int4 kw, int split_ue) {
+                                                        uint64_t* slot, int4 kw, int split_ue, int task0, int task_cnt, int rebin) {
     __shared__ int cnt[RS_ORDER_BINS];  // tasks of this block per bin, then the block's base rank in the bin
     for (int k = threadIdx.x; k < RS_ORDER_BINS; k += 256) cnt[k] = 0;
     __syncthreads();
-    const int n_tasks = D->n_envs * D->n_embb;
-    const int task = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    const int n_tasks = task0 + task_cnt;
+    const int task = task0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
     int bin = 0, local = 0;
-    if (task < n_tasks) {
+    if (task < n_tasks && rebin) {
+        bin = (int)(slot[task] & (RS_ORDER_BINS - 1));
+        local = atomicAdd(&cnt[bin], 1);
+    } else if (task < n_tasks) {
         const int rep = task / D->n_embb, sl = task - rep * D->n_embb;
         const int n_prb = actions[rep * D->n_slices + sl];
         int key;
@@ -87,11 +92,12 @@ __global__ __launch_bounds__(256) void order_key_kernel(const RsDev* __restrict_
     if (task < n_tasks) slot[task] = (uint64_t)bin | ((uint64_t)(cnt[bin] + local) << 11);
 }
 
-// order[start(bin) + rank] = task; also clears the other parity's counters for the next step
+// order[start(bin) + rank] = task; also clears the other parity's counters for the next step.  The ranking is the one of the
+// tasks [task0, task0 + task_cnt) and fills their stretch of `order`: seg_lo, seg_hi and the wave composition count from task0.
 __global__ __launch_bounds__(256) void order_scatter_kernel(const RsDev* __restrict__ D, const int* __restrict__ hist,
                                                             int* hist_next, const uint64_t* __restrict__ slot,
                                                             int32_t* order, int pair, int tpw, int snake, int snake_mask, int rot_mask,
-                                                            int seg_lo, int seg_hi) {
+                                                            int seg_lo, int seg_hi, int task0, int task_cnt) {
     __shared__ int start[RS_ORDER_BINS];
     __shared__ int part[256];
     constexpr int PER = RS_ORDER_BINS / 256;
@@ -119,9 +125,9 @@ __global__ __launch_bounds__(256) void order_scatter_kernel(const RsDev* __restr
     __syncthreads();
     if (blockIdx.x == 0)
         for (int k = threadIdx.x; k < RS_ORDER_BINS; k += 256) hist_next[k] = 0;
-    const int n_all = D->n_envs * D->n_embb;
-    const int task = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (task >= n_all) return;
+    const int task = task0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (task >= task0 + task_cnt) return;
+    order += task0;
     const uint64_t v = slot[task];
     int p = start[(int)(v & (RS_ORDER_BINS - 1))] + (int)(v >> 11);  // rank, heaviest first
     // The split step (rs_api.hip) deals the ranking out to several launches: ranks [seg_lo, seg_hi) are the packed 16-lane

@@ -225,6 +225,7 @@ static int policy_io_on_reset(rs_handle* h) {
 
 extern "C" int rs_get_device_view(rs_handle* h, rs_device_view* out) {
     if (!h || !out) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     int rc = pio_ensure(h);
     if (rc != RS_OK) return rc;
     const PolicyIo* p = h->pio;
@@ -251,6 +252,7 @@ extern "C" int rs_get_device_view(rs_handle* h, rs_device_view* out) {
 
 extern "C" int rs_step_device(rs_handle* h, int kind, const void* actions_device, void* caller_stream) {
     if (!h || !actions_device) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     if (kind != RS_ACT_PRBS && kind != RS_ACT_SHARES && kind != RS_ACT_INDEX) {
         h->err = "rs_step_device: unknown action kind";
         return RS_EINVAL;
@@ -319,6 +321,7 @@ extern "C" int rs_step_device(rs_handle* h, int kind, const void* actions_device
 
 extern "C" int rs_stream_join(rs_handle* h, void* caller_stream) {
     if (!h) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     hipStream_t cs = (hipStream_t)caller_stream;
     if (cs == h->stream) return RS_OK;
     int rc = pio_ensure(h);
@@ -329,6 +332,7 @@ extern "C" int rs_stream_join(rs_handle* h, void* caller_stream) {
 
 extern "C" int rs_set_action_table(rs_handle* h, const int32_t* table, int32_t n_actions) {
     if (!h || !table || n_actions <= 0) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     int rc = pio_ensure(h);
     if (rc != RS_OK) return rc;
     PolicyIo* p = h->pio;
@@ -359,6 +363,7 @@ static int pio_new_history(rs_handle* h, int32_t steps, int16_t** v, double** rw
 
 extern "C" int rs_report_begin(rs_handle* h, int32_t steps) {
     if (!h || steps < 0) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     int rc = pio_ensure(h);
     if (rc != RS_OK) return rc;
     PolicyIo* p = h->pio;
@@ -373,6 +378,7 @@ extern "C" int rs_report_begin(rs_handle* h, int32_t steps) {
 
 extern "C" int rs_report_extend(rs_handle* h, int32_t eval_steps) {
     if (!h || eval_steps < 0) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     PolicyIo* p = h->pio;
     if (!p || !p->h_viol) {
         h->err = "rs_report_extend: no report history (rs_report_begin)";
@@ -402,6 +408,7 @@ extern "C" int rs_report_extend(rs_handle* h, int32_t eval_steps) {
 
 extern "C" int rs_report_fetch(rs_handle* h, int16_t* violation, double* reward, int16_t* resources, int32_t* n_recorded) {
     if (!h) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     PolicyIo* p = h->pio;
     if (!p || !p->h_viol) {
         h->err = "rs_report_fetch: no report history (rs_report_begin)";
@@ -421,6 +428,7 @@ extern "C" int rs_report_fetch(rs_handle* h, int16_t* violation, double* reward,
 
 extern "C" int rs_device_copy(rs_handle* h, void* dst, const void* src, uint64_t bytes, int to_device) {
     if (!h || (bytes && (!dst || !src))) return RS_EINVAL;
+    if (lanes_close(h) != RS_OK) return RS_EHIP;
     HIPCHK(h, hipSetDevice(h->device));
     if (bytes == 0) return RS_OK;
     HIPCHK(h, hipMemcpyAsync(dst, src, (size_t)bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, h->stream));

@@ -45,6 +45,7 @@ EXPORTS = (
     'rs_fork', 'rs_set_lookahead', 'rs_step_clairvoyant', 'rs_set_clairvoyant_fallback',
     'rs_get_device_view', 'rs_step_device', 'rs_stream_join', 'rs_set_action_table', 'rs_report_begin', 'rs_report_extend',
     'rs_report_fetch', 'rs_device_copy',
+    'rs_set_lanes', 'rs_get_lane_info',
 ) + KB_EXPORTS
 
 # action kinds of rs_step_device
@@ -132,6 +133,8 @@ def load(dev=None):
     L.rs_get_task_profile.argtypes = [vp, up]
     L.rs_set_group_size.argtypes = [vp, C.c_int]
     L.rs_set_schedule_hint.argtypes = [vp, C.c_int]
+    L.rs_set_lanes.argtypes = [vp, C.c_int]
+    L.rs_get_lane_info.argtypes = [vp, dp]
     L.rs_kernel_time_ms.argtypes = [vp, dp, C.POINTER(C.c_int64)]
     L.rs_kernel_time_stats_ms.argtypes = [vp, dp, C.POINTER(C.c_int64)]
     L.rs_set_kernel_timing.argtypes = [vp, C.c_int]

@@ -247,6 +247,18 @@ class VecRanSlice:
         """lanes per task of the primary step launch (8, 16, 32); results do not depend on it"""
         self._check(self.L.rs_set_group_size(self.h, int(lanes)))
 
+    def set_lanes(self, n):
+        """lanes of the step loop (rs_set_lanes): 0 automatic, 1 off, n >= 2 that many replica ranges stepped on streams of
+        their own by random_actions / step_resident / run_random, not joined between steps; same results"""
+        self._check(self.L.rs_set_lanes(self.h, int(n)))
+
+    def lane_info(self):
+        """(lanes in use, sum of the lanes' step-kernel times per step in ms, union of their intervals per step in ms,
+        1 - union / sum) over the last window of kernel timing (rs_get_lane_info)"""
+        out = (C.c_double * 4)()
+        self._check(self.L.rs_get_lane_info(self.h, out))
+        return int(out[0]), out[1], out[2], out[3]
+
     def set_schedule_hint(self, mode):
         """1: allocations are agent-made (few wide slices), 0: plain instance, -1: automatic; same results"""
         self._check(self.L.rs_set_schedule_hint(self.h, int(mode)))
