@@ -9,6 +9,14 @@ struct kb_rebuild_state;  // kb_rebuild.hip
 struct kb_bridge_state;   // kb_bridge.hip
 struct kb_fit_state;      // kb_fit.hip
 
+// the scratch of a grouped Projectron++ walk (kb_control_plus_batch.hip): work[8], the ticket, the workgroups' arenas; allocated
+// by the switch's setter (kb_arena_set), freed at width 0
+struct kb_arena_scratch {
+    int32_t width = 0, max = 0;  // candidates per pass over Kinv (0: one by one), the largest dictionary grouped
+    char* d = nullptr;
+    uint64_t bytes = 0;
+};
+
 struct kb_handle {
     kb_config cfg;
     int device = 0;
@@ -79,16 +87,12 @@ struct kb_handle {
     int32_t spb_min = 0, spb_segments = 0;          // kb_set_shared_plus_batch: from how many landmarks a growing shared dictionary's list is applied in segments (0: never) and the segment rounds enqueued per apply; host state as well (kb_shared_plus_batch.hip)
     char* d_spb = nullptr;                          // its counters and per-slice state (allocated by the setter)
     unsigned long long* d_ctl_work = nullptr;       // [4] control_plus_kernel's counters (allocated when the switch is first set)
-    int32_t cpb_width = 0, cpb_max = 0;             // kb_set_control_plus_batch: candidates per pass over Kinv (0: one by one) and the largest dictionary grouped; host state as well (kb_control_plus_batch.hip)
-    char* d_cpb = nullptr;                          // its scratch: work[8], the ticket, the workgroups' arenas (allocated by the setter, freed at width 0)
-    uint64_t cpb_bytes = 0;
+    kb_arena_scratch cpb;                           // kb_set_control_plus_batch: host state as well (kb_control_plus_batch.hip)
     int32_t cpw_min = 0, cpw_max = 0, cpw_rounds = 0;  // kb_set_control_plus_wide: which learners' passes are spread over the chip (0: none), the largest of them, the rounds enqueued; host state as well (kb_control_plus_wide.hip)
     char* d_cpw = nullptr;                          // its scratch: work[8], the slots' records, the two work lines, the slot numbers, the arenas (allocated by the setter, freed at min_landmarks 0)
     uint64_t cpw_bytes = 0;
     int cpw_grid[3] = {2048, 2048, 2048};           // one co-resident round of workgroups of its pass kernel at width 2, 4, 8 (the setter)
-    int32_t fsb_width = 0, fsb_max = 0;             // kb_set_fit_steps_batch: the same for the rows of kb_fit_steps in Projectron++ mode; host state as well (kb_fit_steps_batch.hip)
-    char* d_fsb = nullptr;                          // its own scratch, laid out as d_cpb (allocated by the setter, freed at width 0)
-    uint64_t fsb_bytes = 0;
+    kb_arena_scratch fsb;                           // kb_set_fit_steps_batch: the same for the rows of kb_fit_steps in Projectron++ mode, a scratch of its own; host state as well (kb_fit_steps_batch.hip)
     // kb_fork / kb_deploy into this handle (kb_fork.hip)
     hipEvent_t ev_fork_in = nullptr, ev_fork_out = nullptr;
     int32_t* d_fork_idx = nullptr;   // [n_envs] source agent of every agent
@@ -117,8 +121,7 @@ static void kb_rebuild_release(kb_handle* k);  // kb_rebuild.hip
 static void kb_bridge_release(kb_handle* k);   // kb_bridge.hip
 static void kb_fit_release(kb_handle* k);      // kb_fit.hip
 static void kb_control_plus_release(kb_handle* k);  // kb_control_plus.hip
-static void kb_control_plus_batch_release(kb_handle* k);  // kb_control_plus_batch.hip
-static void kb_fit_steps_batch_release(kb_handle* k);     // kb_fit_steps_batch.hip
+static void kb_arena_release(kb_arena_scratch* a);        // kb_control_plus_batch.hip
 static void kb_control_plus_wide_release(kb_handle* k);   // kb_control_plus_wide.hip
 static void kb_shared_plus_batch_release(kb_handle* k);   // kb_shared_plus_batch.hip
 static void kb_shared_plus_batch_restart(kb_handle* k);
@@ -477,6 +480,28 @@ static int kb_retire_graph(kb_handle* k) {
     return RS_OK;
 }
 
+// the handles on which nothing learns, for the setters of a learning path's switches (`who`): `through` names the path
+static int kb_refuse_non_learning(kb_handle* k, const char* who, const char* through) {
+    if (k->frozen || k->ref || k->D.shared) {
+        k->err = std::string(who) + ": " +
+                 (k->ref ? "a by-reference handle (kb_deploy_ref)" : k->frozen ? "an inference-only handle (kb_deploy, kb_import_agents)"
+                                                                               : "a shared-dictionary handle") +
+                 " does not learn through " + through;
+        return RS_ESTATE;
+    }
+    return RS_OK;
+}
+
+// the first n counter words (4 or 8) of a switch's or a call's scratch `d`, for the *_info readers: zeros while there is none
+static int kb_read_words(kb_handle* k, const void* d, int n, uint64_t* work) {
+    for (int q = 0; q < n; ++q) work[q] = 0;
+    if (!d) return RS_OK;
+    HIPCHK(k, hipSetDevice(k->device));
+    HIPCHK(k, hipMemcpyAsync(work, d, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost, k->stream));
+    HIPCHK(k, hipStreamSynchronize(k->stream));
+    return RS_OK;
+}
+
 extern "C" void kb_destroy(kb_handle* k) {
     if (!k) return;
     if (k->stream) (void)hipStreamSynchronize(k->stream);
@@ -513,8 +538,8 @@ extern "C" void kb_destroy(kb_handle* k) {
     kb_bridge_release(k);
     kb_fit_release(k);
     kb_control_plus_release(k);
-    kb_control_plus_batch_release(k);
-    kb_fit_steps_batch_release(k);
+    kb_arena_release(&k->cpb);
+    kb_arena_release(&k->fsb);
     kb_control_plus_wide_release(k);
     kb_shared_plus_batch_release(k);
     if (k->h_seen) (void)hipHostFree(k->h_seen);
@@ -667,7 +692,7 @@ static int launch_update_control(kb_handle* k, const float* d_state, const int32
         // (kb_get_repair_work keeps its zeros)
         // (kb_set_control_plus_batch: the same row, `width` candidates per pass over Kinv)
         // (kb_set_control_plus_wide: the rows of the batch kernel, the large learners by chip-wide rounds)
-        const int rc = k->cpb_width > 0 ? (kb_control_plus_wide_on(k) ? launch_control_plus_wide(k, a) : launch_control_plus_batch(k, a))
+        const int rc = k->cpb.width > 0 ? (kb_control_plus_wide_on(k) ? launch_control_plus_wide(k, a) : launch_control_plus_batch(k, a))
                                         : launch_control_plus(k, a);
         if (rc != RS_OK) return rc;
         if (e1) HIPCHK(k, hipEventRecord(e1, k->stream));
@@ -1850,12 +1875,9 @@ extern "C" int kb_set_algorithm(kb_handle* k, int32_t alg) {
         k->err = "kb_set_algorithm: " + std::to_string(alg) + " names no algorithm (KB_ALG_PROJECTRON, KB_ALG_PROJECTRON_PLUS)";
         return RS_EINVAL;
     }
-    if (alg == KB_ALG_PROJECTRON_PLUS && (k->frozen || k->ref || k->D.shared)) {
-        k->err = std::string("kb_set_algorithm: ") +
-                 (k->ref ? "a by-reference handle (kb_deploy_ref)" : k->frozen ? "an inference-only handle (kb_deploy, kb_import_agents)"
-                                                                               : "a shared-dictionary handle") +
-                 " does not learn through kb_update / kb_fit: Projectron++ has nothing to act on";
-        return RS_ESTATE;
+    if (alg == KB_ALG_PROJECTRON_PLUS) {
+        const int rc = kb_refuse_non_learning(k, "kb_set_algorithm", "kb_update / kb_fit: Projectron++ has nothing to act on");
+        if (rc != RS_OK) return rc;
     }
     if (k->alg != alg) {  // (a captured loop carries the update phase of the algorithm it was captured in)
         const int rc = kb_retire_graph(k);

@@ -105,13 +105,8 @@ extern "C" int kb_set_control_plus(kb_handle* k, int32_t on) {
         k->err = "kb_set_control_plus: on = " + std::to_string(on) + " (0: the control loop refuses Projectron++ mode, the default; 1: it learns by the margin rule)";
         return RS_EINVAL;
     }
-    if (k->frozen || k->ref || k->D.shared) {
-        k->err = std::string("kb_set_control_plus: ") +
-                 (k->ref ? "a by-reference handle (kb_deploy_ref)" : k->frozen ? "an inference-only handle (kb_deploy, kb_import_agents)"
-                                                                               : "a shared-dictionary handle") +
-                 " does not learn through kb_update_control";
-        return RS_ESTATE;
-    }
+    const int refused = kb_refuse_non_learning(k, "kb_set_control_plus", "kb_update_control");
+    if (refused != RS_OK) return refused;
     if (on && !k->d_ctl_work) {  // (here, not at the first launch: that may be inside a stream capture)
         HIPCHK(k, hipSetDevice(k->device));
         HIPCHK(k, hipMalloc((void**)&k->d_ctl_work, sizeof(unsigned long long) * 4));

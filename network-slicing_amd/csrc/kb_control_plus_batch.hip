@@ -383,10 +383,10 @@ __global__ __launch_bounds__(256, 2) void control_plus_batch_kernel(CtlBatchArgs
 
 }  // namespace kb
 
-static void kb_control_plus_batch_release(kb_handle* k) {
-    if (k->d_cpb) (void)hipFree(k->d_cpb);
-    k->d_cpb = nullptr;
-    k->cpb_bytes = 0;
+static void kb_arena_release(kb_arena_scratch* a) {
+    if (a->d) (void)hipFree(a->d);
+    a->d = nullptr;
+    a->bytes = 0;
 }
 
 static uint64_t kb_control_plus_batch_bytes(const kb_handle* k, int32_t width, int32_t max_landmarks) {
@@ -394,88 +394,110 @@ static uint64_t kb_control_plus_batch_bytes(const kb_handle* k, int32_t width, i
     return KB_CPB_HEAD + arenas * 2 * (uint64_t)width * (uint64_t)max_landmarks * sizeof(double);
 }
 
+// ---- what the setters of the grouped walks share (kb_set_control_plus_batch, kb_set_fit_steps_batch, kb_set_control_plus_wide)
+
+// a width: 0, 2, 4 or 8 (`shares`: what the candidates of a group share, in the caller's words)
+static int kb_check_width(kb_handle* k, const char* who, int32_t width, const char* shares) {
+    if (width != 0 && width != 2 && width != 4 && width != 8) {
+        k->err = std::string(who) + ": width = " + std::to_string(width) + " (0: the candidates one by one, the default; 2, 4 or 8: that many " +
+                 shares + ")";
+        return RS_EINVAL;
+    }
+    return RS_OK;
+}
+
+// the largest dictionary an arena holds: a multiple of 64, at least 64 and at most the handle's capacity
+static int kb_check_max_landmarks(kb_handle* k, const char* who, int32_t max_landmarks) {
+    if (max_landmarks < 64 || max_landmarks % 64 != 0 || max_landmarks > k->D.cap) {
+        k->err = std::string(who) + ": max_landmarks = " + std::to_string(max_landmarks) +
+                 " (a multiple of 64, at least 64 and at most the handle's capacity, " + std::to_string(k->D.cap) + ")";
+        return RS_EINVAL;
+    }
+    return RS_OK;
+}
+
+// the scratch `s` of the handle at (width, max_landmarks): whatever runs on the stream still uses the arenas, so the stream is
+// waited for; the scratch is freed, and allocated again unless the width is 0, when either number changes; the counters and the
+// ticket start over.  All device scratch is allocated here -- the first launch may be inside a stream capture.
+static int kb_arena_set(kb_handle* k, kb_arena_scratch* s, int32_t width, int32_t max_landmarks) {
+    HIPCHK(k, hipStreamSynchronize(k->stream));
+    if (s->width != width || s->max != max_landmarks) {
+        kb_arena_release(s);
+        s->width = 0;
+        s->max = 0;
+        if (width) {
+            const uint64_t bytes = kb_control_plus_batch_bytes(k, width, max_landmarks);
+            HIPCHK(k, hipMalloc((void**)&s->d, (size_t)bytes));
+            s->bytes = bytes;
+        }
+    }
+    if (s->d) HIPCHK(k, hipMemsetAsync(s->d, 0, KB_CPB_HEAD, k->stream));
+    s->width = width;
+    s->max = max_landmarks;
+    return RS_OK;
+}
+
+// the scratch's part of a batch kernel's arguments (CtlBatchArgs, StepsBatchArgs) for a launch over T learners; -> the launch's grid
+template <class Args>
+static unsigned kb_arena_args(Args* a, const kb_arena_scratch& s, int32_t T) {
+    a->bwork = (unsigned long long*)s.d;
+    a->ticket = (int32_t*)(s.d + 64);
+    a->arena = (double*)(s.d + KB_CPB_HEAD);
+    a->max_m = s.max;
+    a->T = T;
+    return (unsigned)(T < KB_CPB_ARENAS ? T : KB_CPB_ARENAS);
+}
+
+// f(std::integral_constant<int, W>) for the instance W = 2, 4 or 8 of a set width
+template <class F>
+static void kb_by_width(int32_t width, F f) {
+    if (width == 2)
+        f(std::integral_constant<int, 2>());
+    else if (width == 4)
+        f(std::integral_constant<int, 4>());
+    else
+        f(std::integral_constant<int, 8>());
+}
+
 // the update phase of a closed-loop step in Projectron++ mode, grouped: one launch (launch_update_control times it as span 0)
 static int launch_control_plus_batch(kb_handle* k, const kb::CtlArgs& c) {
     kb::CtlBatchArgs a;
     a.C = c;
     a.work = k->d_ctl_work;
-    a.bwork = (unsigned long long*)k->d_cpb;
-    a.ticket = (int32_t*)(k->d_cpb + 64);
-    a.arena = (double*)(k->d_cpb + KB_CPB_HEAD);
-    a.max_m = k->cpb_max;
-    a.T = k->T;
-    const unsigned grid = (unsigned)(k->T < KB_CPB_ARENAS ? k->T : KB_CPB_ARENAS);
-    if (k->cpb_width == 2)
-        hipLaunchKernelGGL(kb::control_plus_batch_kernel<2>, dim3(grid), dim3(256), 0, k->stream, a);
-    else if (k->cpb_width == 4)
-        hipLaunchKernelGGL(kb::control_plus_batch_kernel<4>, dim3(grid), dim3(256), 0, k->stream, a);
-    else
-        hipLaunchKernelGGL(kb::control_plus_batch_kernel<8>, dim3(grid), dim3(256), 0, k->stream, a);
+    const unsigned grid = kb_arena_args(&a, k->cpb, k->T);
+    kb_by_width(k->cpb.width, [&](auto w) {
+        hipLaunchKernelGGL(kb::control_plus_batch_kernel<decltype(w)::value>, dim3(grid), dim3(256), 0, k->stream, a);
+    });
     return RS_OK;
 }
 
 /* How the closed control loop's Projectron++ update phase walks a step's candidates (ranslice.h): host state of
-   the handle beside control_plus.  All device scratch is allocated here -- the first launch may be inside a stream capture. */
+   the handle beside control_plus. */
 extern "C" int kb_set_control_plus_batch(kb_handle* k, int32_t width, int32_t max_landmarks) {
     if (!k) return RS_EINVAL;
-    if (width != 0 && width != 2 && width != 4 && width != 8) {
-        k->err = "kb_set_control_plus_batch: width = " + std::to_string(width) +
-                 " (0: the candidates one by one, the default; 2, 4 or 8: that many candidates share one pass over Kinv)";
-        return RS_EINVAL;
-    }
-    if (width != 0 && (max_landmarks < 64 || max_landmarks % 64 != 0 || max_landmarks > k->D.cap)) {
-        k->err = "kb_set_control_plus_batch: max_landmarks = " + std::to_string(max_landmarks) +
-                 " (a multiple of 64, at least 64 and at most the handle's capacity, " + std::to_string(k->D.cap) + ")";
-        return RS_EINVAL;
-    }
-    if (k->frozen || k->ref || k->D.shared) {
-        k->err = std::string("kb_set_control_plus_batch: ") +
-                 (k->ref ? "a by-reference handle (kb_deploy_ref)" : k->frozen ? "an inference-only handle (kb_deploy, kb_import_agents)"
-                                                                               : "a shared-dictionary handle") +
-                 " does not learn through kb_update_control";
-        return RS_ESTATE;
-    }
+    int rc = kb_check_width(k, "kb_set_control_plus_batch", width, "candidates share one pass over Kinv");
+    if (rc == RS_OK && width != 0) rc = kb_check_max_landmarks(k, "kb_set_control_plus_batch", max_landmarks);
+    if (rc == RS_OK) rc = kb_refuse_non_learning(k, "kb_set_control_plus_batch", "kb_update_control");
+    if (rc != RS_OK) return rc;
     if (width == 0) max_landmarks = 0;
     HIPCHK(k, hipSetDevice(k->device));
     // (a captured loop carries the update phase and the arenas it was captured with; whatever runs on the stream still uses them)
-    if (k->cpb_width != width || k->cpb_max != max_landmarks) {
-        const int rc = kb_retire_graph(k);
+    if (k->cpb.width != width || k->cpb.max != max_landmarks) {
+        rc = kb_retire_graph(k);
         if (rc != RS_OK) return rc;
     }
-    HIPCHK(k, hipStreamSynchronize(k->stream));
-    if (k->cpb_width != width || k->cpb_max != max_landmarks) {
-        kb_control_plus_batch_release(k);
-        k->cpb_width = 0;
-        k->cpb_max = 0;
-        if (width) {
-            const uint64_t bytes = kb_control_plus_batch_bytes(k, width, max_landmarks);
-            HIPCHK(k, hipMalloc((void**)&k->d_cpb, (size_t)bytes));
-            k->cpb_bytes = bytes;
-        }
-    }
-    // the counters since the switch was last set, and the ticket
-    if (k->d_cpb) HIPCHK(k, hipMemsetAsync(k->d_cpb, 0, KB_CPB_HEAD, k->stream));
-    k->cpb_width = width;
-    k->cpb_max = max_landmarks;
-    return RS_OK;
+    return kb_arena_set(k, &k->cpb, width, max_landmarks);
 }
 
 extern "C" int kb_get_control_plus_batch(kb_handle* k, int32_t* width, int32_t* max_landmarks, uint64_t* scratch_bytes) {
     if (!k || !width || !max_landmarks || !scratch_bytes) return RS_EINVAL;
-    *width = k->cpb_width;
-    *max_landmarks = k->cpb_max;
-    *scratch_bytes = k->cpb_bytes;
+    *width = k->cpb.width;
+    *max_landmarks = k->cpb.max;
+    *scratch_bytes = k->cpb.bytes;
     return RS_OK;
 }
 
 extern "C" int kb_control_plus_batch_info(kb_handle* k, uint64_t work[8]) {
     if (!k || !work) return RS_EINVAL;
-    for (int q = 0; q < 8; ++q) work[q] = 0;
-    if (!k->d_cpb) return RS_OK;
-    HIPCHK(k, hipSetDevice(k->device));
-    unsigned long long w[8];
-    HIPCHK(k, hipMemcpyAsync(w, k->d_cpb, sizeof w, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(k, hipStreamSynchronize(k->stream));
-    for (int q = 0; q < 8; ++q) work[q] = w[q];
-    return RS_OK;
+    return kb_read_words(k, k->cpb.d, 8, work);
 }

@@ -608,7 +608,7 @@ static uint64_t kb_control_plus_wide_bytes(const kb_handle* k, int32_t max_landm
 }
 
 // whether the update phase of a Projectron++ control step goes through the rounds (launch_update_control asks)
-static bool kb_control_plus_wide_on(const kb_handle* k) { return k->cpw_min > 0 && k->cpb_width > 0 && k->d_cpw && k->d_cpb; }
+static bool kb_control_plus_wide_on(const kb_handle* k) { return k->cpw_min > 0 && k->cpb.width > 0 && k->d_cpw && k->cpb.d; }
 
 template <int W>
 static void kb_cpw_launch(kb_handle* k, const kb::CpwArgs& a) {
@@ -632,11 +632,7 @@ static int launch_control_plus_wide(kb_handle* k, const kb::CtlArgs& c) {
     kb::CpwArgs a;
     a.B.C = c;
     a.B.work = k->d_ctl_work;
-    a.B.bwork = (unsigned long long*)k->d_cpb;
-    a.B.ticket = (int32_t*)(k->d_cpb + 64);
-    a.B.arena = (double*)(k->d_cpb + KB_CPB_HEAD);
-    a.B.max_m = k->cpb_max;
-    a.B.T = k->T;
+    (void)kb_arena_args(&a.B, k->cpb, k->T);
     const uint64_t slots = kb_cpw_slots(k), T = (uint64_t)k->T;
     char* q = k->d_cpw;
     a.info = (unsigned long long*)q;
@@ -654,12 +650,7 @@ static int launch_control_plus_wide(kb_handle* k, const kb::CtlArgs& c) {
     a.wmin = k->cpw_min;
     a.wmax = k->cpw_max;
     a.slots = (int32_t)slots;
-    if (k->cpb_width == 2)
-        kb_cpw_launch<2>(k, a);
-    else if (k->cpb_width == 4)
-        kb_cpw_launch<4>(k, a);
-    else
-        kb_cpw_launch<8>(k, a);
+    kb_by_width(k->cpb.width, [&](auto w) { kb_cpw_launch<decltype(w)::value>(k, a); });
     return RS_OK;
 }
 
@@ -669,11 +660,8 @@ static int launch_control_plus_wide(kb_handle* k, const kb::CtlArgs& c) {
 extern "C" int kb_set_control_plus_wide(kb_handle* k, int32_t min_landmarks, int32_t max_landmarks, int32_t rounds) {
     if (!k) return RS_EINVAL;
     if (min_landmarks != 0) {
-        if (max_landmarks < 64 || max_landmarks % 64 != 0 || max_landmarks > k->D.cap) {
-            k->err = "kb_set_control_plus_wide: max_landmarks = " + std::to_string(max_landmarks) +
-                     " (a multiple of 64, at least 64 and at most the handle's capacity, " + std::to_string(k->D.cap) + ")";
-            return RS_EINVAL;
-        }
+        const int rc = kb_check_max_landmarks(k, "kb_set_control_plus_wide", max_landmarks);
+        if (rc != RS_OK) return rc;
         if (min_landmarks < 2 || min_landmarks > max_landmarks) {
             k->err = "kb_set_control_plus_wide: min_landmarks = " + std::to_string(min_landmarks) +
                      " (0 turns the rounds off, the default; else 2 .. max_landmarks = " + std::to_string(max_landmarks) +
@@ -685,13 +673,8 @@ extern "C" int kb_set_control_plus_wide(kb_handle* k, int32_t min_landmarks, int
             return RS_EINVAL;
         }
     }
-    if (k->frozen || k->ref || k->D.shared) {
-        k->err = std::string("kb_set_control_plus_wide: ") +
-                 (k->ref ? "a by-reference handle (kb_deploy_ref)" : k->frozen ? "an inference-only handle (kb_deploy, kb_import_agents)"
-                                                                               : "a shared-dictionary handle") +
-                 " does not learn through kb_update_control";
-        return RS_ESTATE;
-    }
+    const int refused = kb_refuse_non_learning(k, "kb_set_control_plus_wide", "kb_update_control");
+    if (refused != RS_OK) return refused;
     if (min_landmarks == 0) max_landmarks = rounds = 0;
     HIPCHK(k, hipSetDevice(k->device));
     const bool changed = k->cpw_min != min_landmarks || k->cpw_max != max_landmarks || k->cpw_rounds != rounds;
@@ -738,12 +721,5 @@ extern "C" int kb_get_control_plus_wide(kb_handle* k, int32_t* min_landmarks, in
 
 extern "C" int kb_control_plus_wide_info(kb_handle* k, uint64_t work[8]) {
     if (!k || !work) return RS_EINVAL;
-    for (int q = 0; q < 8; ++q) work[q] = 0;
-    if (!k->d_cpw) return RS_OK;
-    HIPCHK(k, hipSetDevice(k->device));
-    unsigned long long w[8];
-    HIPCHK(k, hipMemcpyAsync(w, k->d_cpw, sizeof w, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(k, hipStreamSynchronize(k->stream));
-    for (int q = 0; q < 8; ++q) work[q] = w[q];
-    return RS_OK;
+    return kb_read_words(k, k->d_cpw, 8, work);
 }

@@ -405,16 +405,7 @@ static int kb_fit_can_learn(kb_handle* k, const char* who) {
 }
 
 // and for the settings of the chip-wide rounds (kb_set_fit_wide, kb_set_fit_wide_plus)
-static int kb_fit_wide_can_set(kb_handle* k, const char* who) {
-    if (k->frozen || k->ref || k->D.shared) {
-        k->err = std::string(who) + ": " +
-                 (k->ref ? "a by-reference handle (kb_deploy_ref)" : k->frozen ? "an inference-only handle (kb_deploy, kb_import_agents)"
-                                                                               : "a shared-dictionary handle") +
-                 " does not learn through kb_fit";
-        return RS_ESTATE;
-    }
-    return RS_OK;
-}
+static int kb_fit_wide_can_set(kb_handle* k, const char* who) { return kb_refuse_non_learning(k, who, "kb_fit"); }
 
 // the list of a fitting call: every entry of `array` names one of `limit` learners / agents (`noun`), none twice (`seq`: its samples / rows)
 static int kb_fit_list(kb_handle* k, const char* who, const char* array, const char* noun, const char* seq, const int32_t* list,
@@ -658,9 +649,9 @@ extern "C" int kb_fit_time_ms(kb_handle* k, double ms[2], uint64_t work[4]) {
     HIPCHK(k, p->score_spans.drain([&](int, double t) { p->score_ms += t; }));
     ms[0] = p->fit_ms;
     ms[1] = p->score_ms;
-    unsigned long long w[8];
-    HIPCHK(k, hipMemcpyAsync(w, p->d_work, sizeof w, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(k, hipStreamSynchronize(k->stream));
+    uint64_t w[8];
+    const int rc = kb_read_words(k, p->d_work, 8, w);
+    if (rc != RS_OK) return rc;
     work[0] = w[0];
     work[1] = w[1];
     work[2] = w[2];

@@ -217,7 +217,7 @@ extern "C" int kb_fit_steps(kb_handle* k, const int32_t* agent, int32_t n, const
         a.from = (long long)from;
         hipEvent_t e;
         HIPCHK(k, p->fit_spans.begin(k->stream, 0, &e));
-        if (k->alg == KB_ALG_PROJECTRON_PLUS && k->fsb_width > 0)  // (kb_set_fit_steps_batch: `width` candidates of a row per pass over Kinv)
+        if (k->alg == KB_ALG_PROJECTRON_PLUS && k->fsb.width > 0)  // (kb_set_fit_steps_batch: `width` candidates of a row per pass over Kinv)
             (void)launch_fit_steps_batch(k, a, n * S);
         else if (k->alg == KB_ALG_PROJECTRON_PLUS)
             hipLaunchKernelGGL(kb::fit_steps_plus_kernel, dim3(grid), dim3(256), 0, k->stream, a);

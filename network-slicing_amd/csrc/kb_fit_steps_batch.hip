@@ -141,15 +141,9 @@ __global__ __launch_bounds__(256, 2) void fit_steps_batch_kernel(StepsBatchArgs 
 
 }  // namespace kb
 
-static void kb_fit_steps_batch_release(kb_handle* k) {
-    if (k->d_fsb) (void)hipFree(k->d_fsb);
-    k->d_fsb = nullptr;
-    k->fsb_bytes = 0;
-}
-
 // a kb_fit_steps call opens: kb_fit_steps_batch_info describes this call
 static int kb_fit_steps_batch_open(kb_handle* k) {
-    if (k->d_fsb) HIPCHK(k, hipMemsetAsync(k->d_fsb, 0, sizeof(unsigned long long) * 8, k->stream));
+    if (k->fsb.d) HIPCHK(k, hipMemsetAsync(k->fsb.d, 0, sizeof(unsigned long long) * 8, k->stream));
     return RS_OK;
 }
 
@@ -157,80 +151,36 @@ static int kb_fit_steps_batch_open(kb_handle* k) {
 static int launch_fit_steps_batch(kb_handle* k, const kb::StepsArgs& s, int32_t learners) {
     kb::StepsBatchArgs a;
     a.S = s;
-    a.bwork = (unsigned long long*)k->d_fsb;
-    a.ticket = (int32_t*)(k->d_fsb + 64);
-    a.arena = (double*)(k->d_fsb + KB_CPB_HEAD);
-    a.max_m = k->fsb_max;
-    a.T = learners;
     // (no agent is listed twice, so learners <= n_envs x S and every workgroup's arena lies inside the scratch)
-    const unsigned grid = (unsigned)(learners < KB_CPB_ARENAS ? learners : KB_CPB_ARENAS);
-    if (k->fsb_width == 2)
-        hipLaunchKernelGGL(kb::fit_steps_batch_kernel<2>, dim3(grid), dim3(256), 0, k->stream, a);
-    else if (k->fsb_width == 4)
-        hipLaunchKernelGGL(kb::fit_steps_batch_kernel<4>, dim3(grid), dim3(256), 0, k->stream, a);
-    else
-        hipLaunchKernelGGL(kb::fit_steps_batch_kernel<8>, dim3(grid), dim3(256), 0, k->stream, a);
+    const unsigned grid = kb_arena_args(&a, k->fsb, learners);
+    kb_by_width(k->fsb.width, [&](auto w) {
+        hipLaunchKernelGGL(kb::fit_steps_batch_kernel<decltype(w)::value>, dim3(grid), dim3(256), 0, k->stream, a);
+    });
     return RS_OK;
 }
 
 /* How kb_fit_steps walks a row's candidates in Projectron++ mode (ranslice.h): host state of the handle beside alg.
-   All device scratch is allocated here. */
+   kb_set_control_plus_batch without a captured loop to retire: kb_fit_steps is in none. */
 extern "C" int kb_set_fit_steps_batch(kb_handle* k, int32_t width, int32_t max_landmarks) {
     if (!k) return RS_EINVAL;
-    if (width != 0 && width != 2 && width != 4 && width != 8) {
-        k->err = "kb_set_fit_steps_batch: width = " + std::to_string(width) +
-                 " (0: the candidates one by one, the default; 2, 4 or 8: that many candidates of a row share one pass over Kinv)";
-        return RS_EINVAL;
-    }
-    if (width != 0 && (max_landmarks < 64 || max_landmarks % 64 != 0 || max_landmarks > k->D.cap)) {
-        k->err = "kb_set_fit_steps_batch: max_landmarks = " + std::to_string(max_landmarks) +
-                 " (a multiple of 64, at least 64 and at most the handle's capacity, " + std::to_string(k->D.cap) + ")";
-        return RS_EINVAL;
-    }
-    if (k->frozen || k->ref || k->D.shared) {
-        k->err = std::string("kb_set_fit_steps_batch: ") +
-                 (k->ref ? "a by-reference handle (kb_deploy_ref)" : k->frozen ? "an inference-only handle (kb_deploy, kb_import_agents)"
-                                                                               : "a shared-dictionary handle") +
-                 " does not learn through kb_fit_steps";
-        return RS_ESTATE;
-    }
+    int rc = kb_check_width(k, "kb_set_fit_steps_batch", width, "candidates of a row share one pass over Kinv");
+    if (rc == RS_OK && width != 0) rc = kb_check_max_landmarks(k, "kb_set_fit_steps_batch", max_landmarks);
+    if (rc == RS_OK) rc = kb_refuse_non_learning(k, "kb_set_fit_steps_batch", "kb_fit_steps");
+    if (rc != RS_OK) return rc;
     if (width == 0) max_landmarks = 0;
     HIPCHK(k, hipSetDevice(k->device));
-    HIPCHK(k, hipStreamSynchronize(k->stream));  // (whatever runs on the stream still uses the arenas)
-    if (k->fsb_width != width || k->fsb_max != max_landmarks) {
-        kb_fit_steps_batch_release(k);
-        k->fsb_width = 0;
-        k->fsb_max = 0;
-        if (width) {
-            const uint64_t arenas = (uint64_t)(k->T < KB_CPB_ARENAS ? k->T : KB_CPB_ARENAS);
-            const uint64_t bytes = KB_CPB_HEAD + arenas * 2 * (uint64_t)width * (uint64_t)max_landmarks * sizeof(double);
-            HIPCHK(k, hipMalloc((void**)&k->d_fsb, (size_t)bytes));
-            k->fsb_bytes = bytes;
-        }
-    }
-    // the counters and the ticket
-    if (k->d_fsb) HIPCHK(k, hipMemsetAsync(k->d_fsb, 0, KB_CPB_HEAD, k->stream));
-    k->fsb_width = width;
-    k->fsb_max = max_landmarks;
-    return RS_OK;
+    return kb_arena_set(k, &k->fsb, width, max_landmarks);
 }
 
 extern "C" int kb_get_fit_steps_batch(kb_handle* k, int32_t* width, int32_t* max_landmarks, uint64_t* scratch_bytes) {
     if (!k || !width || !max_landmarks || !scratch_bytes) return RS_EINVAL;
-    *width = k->fsb_width;
-    *max_landmarks = k->fsb_max;
-    *scratch_bytes = k->fsb_bytes;
+    *width = k->fsb.width;
+    *max_landmarks = k->fsb.max;
+    *scratch_bytes = k->fsb.bytes;
     return RS_OK;
 }
 
 extern "C" int kb_fit_steps_batch_info(kb_handle* k, uint64_t work[8]) {
     if (!k || !work) return RS_EINVAL;
-    for (int q = 0; q < 8; ++q) work[q] = 0;
-    if (!k->d_fsb) return RS_OK;
-    HIPCHK(k, hipSetDevice(k->device));
-    unsigned long long w[8];
-    HIPCHK(k, hipMemcpyAsync(w, k->d_fsb, sizeof w, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(k, hipStreamSynchronize(k->stream));
-    for (int q = 0; q < 8; ++q) work[q] = w[q];
-    return RS_OK;
+    return kb_read_words(k, k->fsb.d, 8, work);
 }

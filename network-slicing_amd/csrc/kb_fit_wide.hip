@@ -399,13 +399,5 @@ extern "C" int kb_get_fit_wide_plus(kb_handle* k, int32_t* on) {
 
 extern "C" int kb_fit_wide_info(kb_handle* k, uint64_t work[4]) {
     if (!k || !work) return RS_EINVAL;
-    for (int q = 0; q < 4; ++q) work[q] = 0;
-    kb_fit_state* p = k->fit;
-    if (!p) return RS_OK;
-    unsigned long long w[4];
-    HIPCHK(k, hipSetDevice(k->device));
-    HIPCHK(k, hipMemcpyAsync(w, p->d_work + 8, sizeof w, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(k, hipStreamSynchronize(k->stream));
-    for (int q = 0; q < 4; ++q) work[q] = w[q];
-    return RS_OK;
+    return kb_read_words(k, k->fit ? k->fit->d_work + 8 : nullptr, 4, work);
 }

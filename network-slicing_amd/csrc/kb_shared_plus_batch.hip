@@ -557,12 +557,5 @@ extern "C" int kb_get_shared_plus_batch(kb_handle* k, int32_t* min_landmarks, in
 
 extern "C" int kb_shared_plus_batch_info(kb_handle* k, uint64_t work[8]) {
     if (!k || !work) return RS_EINVAL;
-    for (int q = 0; q < 8; ++q) work[q] = 0;
-    if (!k->d_spb) return RS_OK;
-    HIPCHK(k, hipSetDevice(k->device));
-    unsigned long long w[8];
-    HIPCHK(k, hipMemcpyAsync(w, k->d_spb, sizeof w, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(k, hipStreamSynchronize(k->stream));
-    for (int q = 0; q < 8; ++q) work[q] = w[q];
-    return RS_OK;
+    return kb_read_words(k, k->d_spb, 8, work);
 }
