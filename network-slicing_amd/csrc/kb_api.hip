@@ -386,7 +386,7 @@ static int kb_create_impl(const kb_config* cfg, int device, kb_handle** out, uns
             return RS_EINVAL;
         }
         D.pool_doubles = want;
-        KA(K.pool, (size_t)want, false);  // every entry is written before it is read
+        KA(K.pool, (size_t)want, false);  // not zeroed: what anybody COMPUTES with is written first; page rows beyond a learner's own coordinates are only ever copied (prune, save_state)
     }
     KA(K.f_last, T, true);
     KA(K.m_last, T, true);

@@ -24,6 +24,10 @@
 //                      the `budget` THAT call was given: KF and DS [budget][capr] (kernel columns and d* = Kinv k_f of the list,
 //                      capr = the capacity rounded up to 64), A [budget][budget] the proposals' Gram block stored by column
 //                      (A[q * budget + p] = k_p . d*_q, tiles tj <= ti only) and F0 [budget]
+//   kb_dev_get_prune_grid  the workgroups (of 256 threads: four waves each) kb_prune / kb_shared_prune launch their downdate
+//                      kernel with on this handle: host state of kb_prune_state, chosen by the first prune call the handle
+//                      takes (RS_ESTATE before it).  With the plan's prefix sums it gives the stretch of every wave
+//                      (tests/test_gpu_prune_chain.py)
 // By-reference handles (kb_ref.hip) answer the first two: their scores are per task as everywhere (they keep no W: zeros), their rows are
 // those of the store's dictionary the map names for (e, s) -- which no selection may ever have changed.
 //
@@ -199,6 +203,16 @@ extern "C" int kb_dev_get_shared_apply(kb_handle* k, int s, int32_t budget, doub
     if (DS) HIPCHK(k, hipMemcpy(DS, kf + b * capr, sizeof(double) * b * capr, hipMemcpyDeviceToHost));
     if (A) HIPCHK(k, hipMemcpy(A, k->K.workg + (size_t)s * b * b, sizeof(double) * b * b, hipMemcpyDeviceToHost));
     if (F0) HIPCHK(k, hipMemcpy(F0, k->K.workf + (size_t)s * b, sizeof(double) * b, hipMemcpyDeviceToHost));
+    return RS_OK;
+}
+
+extern "C" int kb_dev_get_prune_grid(kb_handle* k, int32_t* grid) {
+    if (!k || !grid) return RS_EINVAL;
+    if (!k->prune) {
+        k->err = "kb_dev_get_prune_grid: the handle has taken no prune call yet (the first one chooses the grid)";
+        return RS_ESTATE;
+    }
+    *grid = (int32_t)k->prune->grid;
     return RS_OK;
 }
 

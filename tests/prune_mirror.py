@@ -11,7 +11,14 @@ Pruning.  While m > target:  r = argmin_j c_j^2 / P[j][j] (lowest j on a tie);  
 c_i += c_r (-p_i / q) and P[i][j] -= (p_i p_j) / q over the survivors;  the last landmark moves into slot r;  m -= 1.
 P[S][S] - P[S][r] P[r][S] / q is the Schur complement that inverts the survivors' Gram matrix, c_r (-p / q) are the
 coefficients of the best approximation of c_r k(l_r, .) in their span, and c_r^2 / q is its squared RKHS error.
+
+No sum is formed in a removal, so remove_one() -- separate NumPy ufuncs on IEEE float64, nothing fused -- performs the device's
+operations in the device's order: a mirror loaded with a device's own state (Mirror.from_state) defines the device's bits
+(tests/test_gpu_prune_chain.py).  remove_one_scalar() is the same removal in Python floats and loops, written from the seven
+steps of kb_prune.hip's header; tests/test_prune_mirror.py holds the two to each other bit for bit.
 """
+import struct
+
 import numpy as np
 
 
@@ -58,9 +65,27 @@ class Mirror:
         self.c = np.zeros(0)
         self.P = np.zeros((0, 0))
         self.ids = []
+        self.idx = None      # grid index per slot (from_state): carried through the move of remove_one
         self.born = 0
         self.k = np.zeros(0)
         self.f = 0.0
+
+    @classmethod
+    def from_state(cls, L, c, P, idx=None):
+        """a mirror loaded with a dictionary as read from a device: landmark rows L [m, d], coefficients c [m], Kinv P [m, m] and,
+        optionally, the grid indices idx [m].  Pruning only: remove_one() forms no kernel value, so gamma and eta play no part,
+        and fed the device's own state it performs the device's operations in the device's order (ids[j] = the slot the
+        landmark held when it was loaded)"""
+        L, c, P = (np.array(a, dtype=np.float64) for a in (L, c, P))
+        m = len(c)
+        if L.shape[0] != m or P.shape != (m, m) or (idx is not None and len(idx) != m):
+            raise ValueError('from_state: L [m, d], c [m], P [m, m], idx [m]')
+        mr = cls(L.shape[1])
+        mr.L, mr.c, mr.P = L, c, P
+        mr.ids = list(range(m))
+        mr.born = m
+        mr.idx = None if idx is None else np.array(idx, dtype=np.int64)
+        return mr
 
     @property
     def m(self):
@@ -144,6 +169,10 @@ class Mirror:
             c[r] = c[last]
             self.L[r] = self.L[last]
             self.ids[r] = self.ids[last]
+            if self.idx is not None:
+                self.idx[r] = self.idx[last]
+        if self.idx is not None:
+            self.idx = self.idx[:last].copy()
         self.P = self.P[:last, :last].copy()
         self.c = c[:last].copy()
         self.L = self.L[:last].copy()
@@ -155,6 +184,51 @@ class Mirror:
         while self.m > target:
             log.append(self.remove_one())
         return log
+
+
+def key_bits(x):
+    """the bit pattern of a float64 as an unsigned 64-bit integer (the device's __double_as_longlong, read unsigned)"""
+    return struct.unpack('<Q', struct.pack('<d', x))[0]
+
+
+def remove_one_scalar(L, c, P, idx=None):
+    """One removal in plain Python floats and loops, written from the seven steps of kb_prune.hip's header and from nothing
+    else: lists (of lists) in, -> (r, L, c, P, idx) as new lists, the inputs untouched.  Every product, quotient, sum and
+    difference is one IEEE float64 operation of the interpreter, in the order the header writes them; the argmin runs over
+    the pair (bit pattern of the key as uint64, slot), as prune_choose_kernel's does."""
+    m = len(c)
+    # 1. r = argmin_j (c_j c_j) / P[j][j], the lowest j on a tie
+    best = None
+    for j in range(m):
+        pair = (key_bits((c[j] * c[j]) / P[j][j]), j)
+        if best is None or pair < best:
+            best = pair
+    r = best[1]
+    # 2. p = P[:, r], q = P[r][r]
+    p = [P[i][r] for i in range(m)]
+    q = P[r][r]
+    cr = c[r]
+    # 3. c_i = c_i + c_r * ((-p_i) / q) for every survivor
+    c = [c[i] if i == r else c[i] + cr * ((-p[i]) / q) for i in range(m)]
+    # 4. P[i][j] = P[i][j] - (p_i * p_j) / q for every survivor pair
+    P = [[P[i][j] if (i == r or j == r) else P[i][j] - (p[i] * p[j]) / q for j in range(m)] for i in range(m)]
+    L = [list(row) for row in L]
+    idx = None if idx is None else list(idx)
+    # 5. landmark m - 1 moves into slot r (unless r = m - 1)
+    last = m - 1
+    if r != last:
+        for k in range(m):
+            if k != r and k != last:
+                P[r][k] = P[last][k]
+                P[k][r] = P[last][k]
+        P[r][r] = P[last][last]
+        L[r] = L[last]
+        c[r] = c[last]
+        if idx is not None:
+            idx[r] = idx[last]
+    # 6. slot m - 1 and row / column m - 1 go;  7. m -= 1
+    P = [row[:last] for row in P[:last]]
+    return r, L[:last], c[:last], P, (None if idx is None else idx[:last])
 
 
 def build_from_landmarks(L, c, gamma=1.0):

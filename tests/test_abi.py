@@ -93,7 +93,7 @@ def test_production_library_reads_no_developer_knob():
     # the primitive probe (csrc/rs_probe.hip) is test tooling too: neither the entry point nor its kernels are in the product
     # and so are the accessors of the agent's scoring chain (csrc/kb_probe.hip)
     for k in (b'rs_dev_probe', b'probe_kernel', b'kb_dev_get_scores', b'kb_dev_get_rows', b'kb_dev_get_update_rows',
-              b'kb_dev_get_shared_scores', b'kb_dev_get_shared_apply'):
+              b'kb_dev_get_shared_scores', b'kb_dev_get_shared_apply', b'kb_dev_get_prune_grid'):
         assert k not in prod, k
         assert k in dev, k
     assert not [n for n in _lib.EXPORTS if '_dev_' in n]
