@@ -438,7 +438,9 @@ int kb_get_sizes(kb_handle* k, int32_t* m);
  * exhausted (both keep learning by projection -- build-defined, the reference's SVvariable is unbounded; any may be NULL) */
 int kb_get_pool(kb_handle* k, uint64_t* used_bytes, uint64_t* total_bytes, int32_t* n_saturated, int32_t* n_pool_full);
 /* per-replica flag words [n_envs] behind kb_get_pool's counts: bit 8 a dictionary of the replica reached its capacity, bit 16
- * it found the pool exhausted */
+ * it found the pool exhausted, bit 32 the budget stage of the loop (kb_set_online_prune) met a dictionary of the replica whose
+ * Kinv diagonal is not finite and positive, or whose coefficient is not finite, and left it unpruned.  All three are sticky,
+ * travel with the agent as the word does (kb_fork, checkpoints, agent files), and none is an error to kb_synchronize */
 int kb_get_flags(kb_handle* k, int32_t* flags);
 /* bytes behind the repair rounds of the large dictionaries since kb_reset (projectron.py:42 Kinv @ K_f, :54-58 the rank-1
  * update), as their kernels count them: work[0] tiles of Kinv the mat-vec kernel read (32,768 bytes each), work[1] units of
@@ -691,6 +693,38 @@ int kb_get_prune_work(kb_handle* k, uint64_t work[2]);
  * there), kb_reset missing, a round open between kb_shared_scan and kb_shared_commit, or dictionaries with a diagonal entry of
  * Kinv that is not finite and positive -- those are left as they are, the others are pruned.  The handle stays usable. */
 int kb_shared_prune(kb_handle* k, int32_t target, uint64_t* removed_total);
+/* ---- The online budget (csrc/kb_online_prune.hip): kb_prune's rule inside the closed loop.
+ * kb_set_online_prune(k, target, rounds): target 0 = off, the default.  When on, every update phase -- enqueued by
+ * kb_update_control, kb_step_resident or kb_run_resident, plain or captured into its graph, under Projectron's rule or under
+ * Projectron++ (kb_set_control_plus, with or without its batch and wide switches) -- is followed by a budget stage, before
+ * anything else reads the dictionaries (in the resident step: between the update phase and select_action, so the action is
+ * chosen by the classifier the agent keeps and the scores select leaves for the next update phase stay valid).  Every
+ * dictionary with m > target loses min(m - target, rounds) landmarks, each by kb_prune's removal in its operation order, and is
+ * then finished once as kb_prune finishes a touched dictionary (chains, off-grid count, version, stored scores, predict cache).
+ * No sum is formed: a dictionary comes out bit for bit as kb_prune(k, target) at the same point leaves it whenever `rounds`
+ * covers its excess, whatever the launch and whichever other dictionaries are over the target.  What a stage leaves above the
+ * target the following stages take (carry).  A stage runs only behind an update phase: with kb_set_learning(k, 0) nothing
+ * grows and nothing is pruned.  kb_fit, kb_fit_steps and kb_update are not followed by one (kb_prune is the call there).
+ * Nothing in the stage waits for the host: 2 + 3 * rounds launches of a geometry fixed by the setter, which return at once
+ * while nothing is over the target.  A step that inserts more than capacity - m landmarks saturates and is flagged (bit 8)
+ * as without the switch.  A dictionary whose Kinv diagonal is not finite and positive, or whose coefficient is not finite, is
+ * left exactly as kb_prune leaves it (untouched if met in the stage's first removal, stopped after the completed ones
+ * otherwise), its replica gets bit 32 of its flag word (kb_get_flags), the others are pruned and the loop goes on.
+ * kb_get_pruned counts the stage's removals with kb_prune's.
+ * The setting is host state of the handle like the other switches: not written by kb_save_state, and kb_load_state, kb_fork,
+ * kb_unshare and kb_import_agents leave the destination's setting alone.  Setting or changing it drops a captured loop (the
+ * handle waits for its stream first); the next kb_run_resident captures the new sequence.
+ * RS_EINVAL: target neither 0 nor in 64 .. capacity - 64 (one shell of headroom for a step's insertions); rounds outside
+ * 1 .. 64.  RS_ESTATE: a shared-dictionary handle (kb_shared_prune between steps is the call there), an inference-only or
+ * by-reference handle (set it on the learning handle and deploy again), kb_reset missing.
+ * kb_get_online_prune: the setting ((0, 2) on a handle it was never set on).
+ * kb_online_prune_info, counted on the device since kb_reset / kb_load_state / kb_fork into the handle: work[0] stages
+ * enqueued, [1] landmarks removed, [2] dictionary-stages left above the target (carry), [3] the largest excess a stage met,
+ * [4] dictionaries flagged (each once), [5] units of the downdate that held rows (8,192 bytes read + 8,192 written each);
+ * [6], [7] reserved (0). */
+int kb_set_online_prune(kb_handle* k, int32_t target, int32_t rounds);
+int kb_get_online_prune(kb_handle* k, int32_t* target, int32_t* rounds);
+int kb_online_prune_info(kb_handle* k, uint64_t work[8]);
 /* ---- the learner's own surface, batched (csrc/kb_fit.hip): sample sequences in, trained learners out; query
  * sets in, scores out.  Build-defined: the reference has Projectron.predict(x) / update(x, y), one sample per call.
  *

@@ -4,6 +4,7 @@
 #include "kb_kbrl.hip"
 
 struct kb_prune_state;  // kb_prune.hip
+struct kb_online_prune_state;  // kb_online_prune.hip
 struct kb_ref_state;    // kb_ref.hip
 struct kb_rebuild_state;  // kb_rebuild.hip
 struct kb_bridge_state;   // kb_bridge.hip
@@ -100,6 +101,7 @@ struct kb_handle {
     uint64_t* d_fork_base = nullptr; // [n_dict + 1] first pool double of every dictionary (exclusive scan of its shells' sizes)
     uint64_t* h_fork_total = nullptr;  // pinned: the scan's total
     kb_prune_state* prune = nullptr; // kb_prune's lists and the pruned counters: NOT a saved region (kb_prune.hip)
+    kb_online_prune_state* oprune = nullptr;  // kb_set_online_prune: the budget stage's setting, lists and counters; host state of the handle, never copied or saved (kb_online_prune.hip)
     kb_rebuild_state* rebuild = nullptr;  // kb_fork_rebuild into this handle: its plan, result words and timing (kb_rebuild.hip)
     kb_bridge_state* bridge = nullptr;    // kb_unshare / kb_share into this handle: result words, timing and plan bytes (kb_bridge.hip)
     kb_fit_state* fit = nullptr;          // kb_fit / kb_score on this handle: the counters and the timing of the last calls (kb_fit.hip)
@@ -115,6 +117,9 @@ struct kb_handle {
 
 static void kb_prune_release(kb_handle* k);  // kb_prune.hip
 static void kb_prune_restart(kb_handle* k);  // the pruned counters start over (kb_reset, kb_load_state, kb_fork)
+static void kb_online_prune_release(kb_handle* k);  // kb_online_prune.hip
+static void kb_online_prune_restart(kb_handle* k);  // its counters start over with them
+static int launch_online_prune(kb_handle* k);       // the budget stage behind an update phase (nothing while the switch is off)
 // by-reference handles (kb_ref.hip): their dictionaries live in a store handle, (replica, slice) -> dictionary through a map
 static void kb_ref_release(kb_handle* k);
 static void kb_rebuild_release(kb_handle* k);  // kb_rebuild.hip
@@ -533,6 +538,7 @@ extern "C" void kb_destroy(kb_handle* k) {
     if (k->h_fork_idx) (void)hipHostFree(k->h_fork_idx);
     if (k->h_fork_total) (void)hipHostFree(k->h_fork_total);
     kb_prune_release(k);
+    kb_online_prune_release(k);
     kb_ref_release(k);
     kb_rebuild_release(k);
     kb_bridge_release(k);
@@ -559,6 +565,7 @@ static int kb_restart_counters(kb_handle* k) {
     HIPCHK(k, hipMemsetAsync(k->d_gstats, 0, sizeof(uint64_t) * 32, k->stream));
     HIPCHK(k, hipMemsetAsync(k->K.hv_work, 0, sizeof(unsigned long long) * 8, k->stream));
     kb_prune_restart(k);
+    kb_online_prune_restart(k);
     kb_shared_plus_batch_restart(k);
     return RS_OK;
 }
@@ -620,8 +627,9 @@ static int kb_check(kb_handle* k) {
     HIPCHK(k, hipMemcpyAsync(e.data(), k->K.err, sizeof(int32_t) * e.size(), hipMemcpyDeviceToHost, k->stream));
     HIPCHK(k, hipStreamSynchronize(k->stream));
     for (size_t i = 0; i < e.size(); ++i)
-        if (e[i] & ~(8 | 16)) {  // bit 8: a dictionary is at its capacity, bit 16: the pool is exhausted (it projects
-                                 // instead of growing): reported by kb_get_pool / kb_get_sizes, not an error
+        if (e[i] & ~(8 | 16 | 32)) {  // bit 8: a dictionary is at its capacity, bit 16: the pool is exhausted (it projects
+                                      // instead of growing): reported by kb_get_pool / kb_get_sizes, not an error; bit 32: the
+                                      // budget stage left a dictionary unpruned (kb_set_online_prune), reported by kb_get_flags
             k->err = "KBRL agent " + std::to_string(i) + ": internal error flag " + std::to_string(e[i]);
             return RS_EOVERFLOW;
         }
@@ -831,6 +839,7 @@ extern "C" int kb_update_control(kb_handle* k, const float* state, const int32_t
     HIPCHK(k, hipMemcpyAsync(k->d_labels, labels, sizeof(int32_t) * T, hipMemcpyHostToDevice, k->stream));
     int rc = launch_update_control(k, k->d_state, k->d_action, k->d_labels);
     if (rc != RS_OK) return rc;
+    if ((rc = launch_online_prune(k)) != RS_OK) return rc;  // kb_set_online_prune: the budget stage, before anything reads the dictionaries
     HIPCHK(k, hipGetLastError());
     if (hits) HIPCHK(k, hipMemcpyAsync(hits, k->d_hits, sizeof(int32_t) * T, hipMemcpyDeviceToHost, k->stream));
     return kb_check(k);
@@ -878,6 +887,7 @@ extern "C" int kb_step_resident(kb_handle* k, rs_handle* env) {
     // inference mode (kb_set_learning(k, 0), or an inference-only handle): KBRL_Control.run past learning_time, kbrl_control.py:131-133
     // -- the same launches without the update phase; d_hits keeps the last learning step's hits for the history column
     if (k->learning && (rc = launch_update_control(k, k->d_prev_state, env->d_actions, env->d_labels)) != RS_OK) return rc;
+    if (k->learning && (rc = launch_online_prune(k)) != RS_OK) return rc;  // kb_set_online_prune: only behind an update phase
     rc = launch_select(k, env->d_obs, env->d_actions);
     if (rc != RS_OK) return rc;
     if (k->h_steps > 0) {  // KBRL_Control.run's history columns of this step (kbrl_control.py:135-141)
@@ -1839,6 +1849,7 @@ extern "C" int kb_load_state(kb_handle* k, const void* blob, uint64_t bytes) {
         if (any) HIPCHK(k, hipMemcpy(k->K.err, e.data(), sizeof(int32_t) * e.size(), hipMemcpyHostToDevice));
     }
     kb_prune_restart(k);
+    kb_online_prune_restart(k);
     k->big_par = hd.big_par;
     k->is_reset = hd.is_reset != 0;
     if (k->h_seen) {

@@ -61,6 +61,10 @@ class BatchedEvaluator(Evaluator):
     prune_to = T, prune_every = P: budgeted dictionaries -- after every P-th step (between two resident stretches) every
     dictionary above T landmarks is pruned back to T (VecKBRL.prune); the result files then carry one extra
     key, `pruned`: the landmarks removed from the run's dictionaries in all.  The defaults leave everything as it was.
+    online_prune = T (online_prune_rounds = R): the budget is held INSIDE the loop instead -- behind every step's update phase every
+    dictionary above T landmarks loses up to R of them by the same rule, on the device, captured graph included
+    (VecKBRL.set_online_prune); the stretches are not cut and the host waits for nothing.  The result files carry
+    `pruned` as well.  Not together with prune_to / prune_every (ValueError): they are two ways to hold one budget.
     algorithm='projectron_plus': the agents learn by ProjectronPlus's margin rule in the closed loop (VecKBRL(...,
     algorithm='projectron_plus', control_plus=True)) -- no reference-shaped serial counterpart is run beside it.
     control_plus_batch = 2, 4 or 8 (with 'projectron_plus' only): that many candidates of a step share one pass over Kinv
@@ -70,7 +74,7 @@ class BatchedEvaluator(Evaluator):
     groups); the same results again."""
 
     def __init__(self, scenario, a_range, steps=STEPS, out_dir='./results', prune_to=None, prune_every=None, algorithm='projectron',
-                 control_plus_batch=0, control_plus_wide=0):
+                 control_plus_batch=0, control_plus_wide=0, online_prune=None, online_prune_rounds=2):
         super().__init__(scenario, a_range, steps=steps, out_dir=out_dir)
         if algorithm not in ('projectron', 'projectron_plus'):
             raise ValueError("algorithm must be 'projectron' or 'projectron_plus', not %r" % (algorithm,))
@@ -84,6 +88,10 @@ class BatchedEvaluator(Evaluator):
         if (prune_to is None) != (not prune_every):
             raise ValueError('prune_to and prune_every go together')
         self.prune_to, self.prune_every = prune_to, prune_every
+        if online_prune is not None and (prune_to is not None or prune_every):
+            raise ValueError('online_prune holds the budget inside the loop, prune_to / prune_every between its stretches: give one of the two')
+        self.online_prune, self.online_prune_rounds = online_prune, online_prune_rounds
+        self._budgeted = bool(prune_every) or online_prune is not None   # the result files carry `pruned`
         self._pruned_base = 0   # what a checkpoint this evaluation resumed from had counted (the device counters restart on load)
 
     def _setup(self, runs, device=0, capacity=16384, pool_bytes=32 << 30):
@@ -117,7 +125,8 @@ class BatchedEvaluator(Evaluator):
         env = VecRanSlice(n_envs=n, cfg=cfg, fading=fading, device=device)
         dims = [len(sc.state_variables_embb)] * n_embb + [len(sc.state_variables_mmtc)] * n_mmtc
         agent = VecKBRL(n, dims, n_prbs, alfa=sc.alfa, accuracy_range=tuple(self.a_range), capacity=capacity,
-                        device=device, pool_bytes=pool_bytes,
+                        device=device, pool_bytes=pool_bytes, online_prune=self.online_prune,
+                        online_prune_rounds=self.online_prune_rounds,
                         **(dict(algorithm=self.algorithm, control_plus=True, control_plus_batch=self.control_plus_batch,
                                 control_plus_wide=self.control_plus_wide,
                                 control_plus_wide_max=min(2048, capacity // 64 * 64))
@@ -177,7 +186,7 @@ class BatchedEvaluator(Evaluator):
         assert hist['recorded'] == self.steps
         sizes = agent.dictionary_sizes()
         pool = agent.pool()
-        pruned = (agent.pruned() + self._pruned_base).sum(axis=1) if self.prune_every else None
+        pruned = (agent.pruned() + self._pruned_base).sum(axis=1) if self._budgeted else None
         self.last_run = dict(max_dictionary=int(sizes.max()), mean_dictionary=float(sizes.mean()), pool=pool)
         if pool['saturated'] or pool['pool_full']:
             import warnings
@@ -194,7 +203,7 @@ class BatchedEvaluator(Evaluator):
         for k, i in enumerate(runs):
             results = {'reward': hist['reward'][k], 'resources': hist['resources'][k], 'hits': hist['hits'][k],
                        'adjusted': hist['adjusted'][k], 'SLA': hist['SLA'][k], 'violation': hist['violation'][k]}
-            if self.prune_every:
+            if self._budgeted:
                 results['pruned'] = np.int64(pruned[k])
             file_path = '{}results_{}.npz'.format(self.path, i)
             savez(file_path, **results)
@@ -218,7 +227,7 @@ class BatchedEvaluator(Evaluator):
         # written beside the old checkpoint and moved onto it: a crash during the write -- the case this exists for -- leaves
         # the previous checkpoint intact instead of a torn .npz
         tmp = path + '.tmp.npz'
-        extra = dict(pruned=c['agent'].pruned() + self._pruned_base) if self.prune_every else {}
+        extra = dict(pruned=c['agent'].pruned() + self._pruned_base) if self._budgeted else {}
         np.savez(tmp, next_step=np.int64(next_step), steps=np.int64(self.steps), runs=np.asarray(c['runs'], dtype=np.int64),
                  env=env_blob, agent=agent_blob, **extra)
         os.replace(tmp, path)
@@ -231,7 +240,7 @@ class BatchedEvaluator(Evaluator):
             raise ValueError('checkpoint %s belongs to another evaluation (steps / runs differ)' % path)
         c['env'].load_state(z['env'])
         c['agent'].load_state(z['agent'])
-        if self.prune_every and 'pruned' in z.files:
+        if self._budgeted and 'pruned' in z.files:
             self._pruned_base = z['pruned']
         return int(z['next_step'])
 
@@ -269,7 +278,7 @@ class BatchedEvaluator(Evaluator):
 
 def evaluate_grid(cells, runs, steps=STEPS, out_dir='./results', device=0, capacity=16384, pool_bytes=16 << 30, verbose=False,
                   graph=False, prune_to=None, prune_every=None, algorithm='projectron', control_plus_batch=0,
-                  control_plus_wide=0):
+                  control_plus_wide=0, online_prune=None, online_prune_rounds=2):
     """The reference's whole experiment (experiments_kbrl.py:57-70: every scenario x accuracy range x run) as ONE job on
     one GPU: a BatchedEvaluator per cell, each with its environment and agents on streams of their own, all advanced in
     the same host loop -- a cell of 30 runs leaves most of the chip idle (a handful of waves per kernel), so the cells'
@@ -279,11 +288,12 @@ def evaluate_grid(cells, runs, steps=STEPS, out_dir='./results', device=0, capac
     for file what evaluate_all writes cell by cell (tests/test_gpu_kbrl.py::test_grid_of_cells_equals_cell_by_cell).
     prune_to / prune_every: budgeted dictionaries in every cell (BatchedEvaluator); algorithm, control_plus_batch: its update rule
     and how many candidates share a pass over Kinv; control_plus_wide: from how many landmarks on a learner's passes are spread
-    over the chip."""
+    over the chip.  online_prune / online_prune_rounds: the budget held inside every cell's loop instead (not with prune_to)."""
     evs = []
     for scenario, a_range in cells:
         ev = BatchedEvaluator(scenario, a_range, steps=steps, out_dir=out_dir, prune_to=prune_to, prune_every=prune_every,
-                              algorithm=algorithm, control_plus_batch=control_plus_batch, control_plus_wide=control_plus_wide)
+                              algorithm=algorithm, control_plus_batch=control_plus_batch, control_plus_wide=control_plus_wide,
+                              online_prune=online_prune, online_prune_rounds=online_prune_rounds)
         ev._setup(runs, device=device, capacity=capacity, pool_bytes=pool_bytes)
         evs.append(ev)
     for i in range(0, steps, CHUNK):
@@ -311,8 +321,15 @@ if __name__ == '__main__':
     ap.add_argument('--control-plus-wide', type=int, default=0, metavar='M',
                     help='with --control-plus-batch: learners of M landmarks or more have their passes over Kinv spread over the chip '
                          '(same results; 0: every row on one workgroup)')
+    ap.add_argument('--online-prune', type=int, default=None, metavar='T',
+                    help='hold every dictionary to T landmarks inside the loop: a budget stage behind every update phase (64 <= T <= capacity - 64)')
+    ap.add_argument('--online-prune-rounds', type=int, default=2, metavar='R',
+                    help='with --online-prune: most landmarks a dictionary loses per step (1 .. 64); the rest is carried to the next steps')
     args = ap.parse_args()
     cells = list(product(args.scenarios, accuracy_list))
+    if args.serial and args.online_prune is not None:
+        ap.error('--online-prune is a switch of the batched evaluators (serial: create_kbrl_agent(..., budget=T))')
+    budget = dict(online_prune=args.online_prune, online_prune_rounds=args.online_prune_rounds)
     if args.control_plus_batch and args.algorithm != 'projectron_plus':
         ap.error('--control-plus-batch needs --algorithm projectron_plus')
     if args.control_plus_wide and not args.control_plus_batch:
@@ -327,7 +344,8 @@ if __name__ == '__main__':
     elif args.cell_by_cell:
         for scenario, a_range in cells:
             BatchedEvaluator(scenario, a_range, steps=args.steps, out_dir=args.out, algorithm=args.algorithm,
-                             control_plus_batch=args.control_plus_batch, control_plus_wide=args.control_plus_wide).evaluate_all(range(args.runs))
+                             control_plus_batch=args.control_plus_batch, control_plus_wide=args.control_plus_wide,
+                             **budget).evaluate_all(range(args.runs))
     else:
         evaluate_grid(cells, range(args.runs), steps=args.steps, out_dir=args.out, verbose=True, algorithm=args.algorithm,
-                      control_plus_batch=args.control_plus_batch, control_plus_wide=args.control_plus_wide)
+                      control_plus_batch=args.control_plus_batch, control_plus_wide=args.control_plus_wide, **budget)

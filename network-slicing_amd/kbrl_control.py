@@ -22,7 +22,7 @@ class Learner:
 
 
 class KBRL_Control:
-    def __init__(self, learners, n_prbs, alfa=0.05, accuracy_range=[0.99, 0.999], capacity=4096, device=0, seed=0):
+    def __init__(self, learners, n_prbs, alfa=0.05, accuracy_range=[0.99, 0.999], capacity=4096, device=0, seed=0, budget=None):
         self.learners = learners
         self.accuracy_range = accuracy_range
         self.n_slices = len(learners)
@@ -51,6 +51,7 @@ class KBRL_Control:
         alg0 = learners[0].algorithm
         self._dev = VecKBRL(1, dims, n_prbs, alfa=alfa, accuracy_range=tuple(accuracy_range),
                             gamma=alg0.kernel.gamma, eta=alg0.eta, capacity=capacity, device=device,
+                            online_prune=budget,   # (most landmarks a learner keeps: the budget stage behind update_control)
                             **(dict(algorithm='projectron_plus', control_plus=True) if control_plus else {}))
         self._dev.reset([[int(h.initial_action) for h in learners]], [[int(h.security_factor) for h in learners]],
                         seeds=np.array([seed], dtype=np.uint64))

@@ -95,9 +95,15 @@ class VecKBRL:
     def __init__(self, n_envs, dims, n_prbs, alfa=KBRL_ALFA, accuracy_range=(0.99, 0.999), gamma=KBRL_GAMMA,
                  eta=KBRL_ETA, capacity=4096, device=0, shared=False, first_env=0, pool_bytes=0, algorithm='projectron',
                  control_plus=False, control_plus_batch=0, control_plus_batch_max=1024, fit_steps_batch=0, fit_steps_batch_max=1024,
-                 control_plus_wide=0, control_plus_wide_max=2048, control_plus_wide_rounds=32):
+                 control_plus_wide=0, control_plus_wide_max=2048, control_plus_wide_rounds=32, online_prune=None,
+                 online_prune_rounds=2):
         if algorithm not in ALGORITHMS:
             raise ValueError('algorithm must be one of %s, not %r' % (sorted(ALGORITHMS), algorithm))
+        if online_prune is not None and shared:
+            raise ValueError('online_prune=%r: shared-dictionary handles hold no budget in the loop (SharedVecKBRL.prune between '
+                             'steps is the call there)' % (online_prune,))
+        # (kb_set_online_prune wants a reset handle: the keyword is kept and set by the first reset())
+        self._online_prune_pending = None if online_prune is None else (int(online_prune), int(online_prune_rounds))
         self.L = _lib.load()
         cfg = KbConfig()
         cfg.n_envs, cfg.n_slices, cfg.n_prbs, cfg.capacity = n_envs, len(dims), n_prbs, capacity
@@ -166,6 +172,9 @@ class VecKBRL:
             seeds = replica_seeds(0, self.cfg.first_env, self.n_envs)   # tie-break streams (kernel.py:26-27)
         seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
         self._check(self.L.kb_reset(self.h, ia.ctypes.data_as(_ip), sf.ctypes.data_as(_ip), seeds.ctypes.data_as(_up)))
+        if getattr(self, '_online_prune_pending', None):   # VecKBRL(online_prune=...): the switch is the handle's from here on
+            pending, self._online_prune_pending = self._online_prune_pending, None
+            self.set_online_prune(*pending)
 
     def update_control(self, state, action, labels):
         state = np.ascontiguousarray(state, dtype=np.float32).reshape(self.n_envs, self.nv)
@@ -563,6 +572,13 @@ class VecKBRL:
         self._check(self.L.kb_get_flags(self.h, e.ctypes.data_as(_ip)))
         return dict(saturated=[int(k) for k in np.nonzero(e & 8)[0]], pool_full=[int(k) for k in np.nonzero(e & 16)[0]])
 
+    def flags(self):
+        """the per-replica flag words int32 [n_envs] (kb_get_flags): bit 8 a dictionary reached its capacity, bit 16 the pool was
+        exhausted, bit 32 the budget stage (set_online_prune) left a dictionary of the replica unpruned.  All sticky."""
+        e = np.zeros(self.n_envs, dtype=np.int32)
+        self._check(self.L.kb_get_flags(self.h, e.ctypes.data_as(_ip)))
+        return e
+
     def repair_work(self):
         """bytes the chip-wide repair rounds streamed since reset: dict(matvec_bytes read, rank1_bytes read + written,
         matvec_launches, rank1_launches) -- counted by the kernels from their work plan (kb_get_repair_work)"""
@@ -813,6 +829,36 @@ class VecKBRL:
         return dict(choose_ms=ms[0], downdate_ms=ms[1], move_ms=ms[2], n_choose=n[0], n_downdate=n[1], n_move=n[2],
                     downdate_bytes=int(w[0]) * 16384, downdate_launches=int(w[1]))
 
+    def set_online_prune(self, target, rounds=2):
+        """the online budget (kb_set_online_prune): from now on every update phase -- update_control,
+        step_resident, run_resident with or without its graph, Projectron or Projectron++ under set_control_plus -- is followed
+        on the device by a budget stage: every dictionary above `target` landmarks loses min(excess, rounds) of them by prune()'s
+        rule, bit for bit, before select_action reads it; what is left above the target the next stages take.  target None or
+        0: off (the default).  64 <= target <= capacity - 64; 1 <= rounds <= 64.  Call it after reset() (the constructor's
+        online_prune= is set by the first reset()).  A property of this handle: checkpoints do not hold it; load_state, fork_from,
+        unshare_from and load_agents leave it alone.  A dictionary the stage cannot prune (a Kinv diagonal entry that is not
+        finite and positive) stays as it is and its replica gets bit 32 of flags().  pruned() counts the removals."""
+        self._check(self.L.kb_set_online_prune(self.h, int(target or 0), int(rounds)))
+
+    @property
+    def online_prune(self):
+        """None while the budget stage is off, else (target, rounds) (kb_get_online_prune)"""
+        pending = getattr(self, '_online_prune_pending', None)
+        if pending:
+            return pending
+        t, r = C.c_int32(), C.c_int32()
+        self._check(self.L.kb_get_online_prune(self.h, C.byref(t), C.byref(r)))
+        return (t.value, r.value) if t.value else None
+
+    def online_prune_info(self):
+        """the budget stages since reset / load_state / fork_from, counted on the device (kb_online_prune_info): stages
+        enqueued, landmarks removed, carry (dictionary-stages left above the target), the largest excess a stage met, the
+        dictionaries flagged, and the downdate's bytes (read + written)"""
+        w = (C.c_uint64 * 8)()
+        self._check(self.L.kb_online_prune_info(self.h, w))
+        return dict(stages=int(w[0]), removed=int(w[1]), carry=int(w[2]), max_excess=int(w[3]), flagged=int(w[4]),
+                    downdate_bytes=int(w[5]) * 16384)
+
 
 PROP_W = 18  # KB_PROP_WIDTH
 
@@ -873,6 +919,9 @@ class SharedVecKBRL(VecKBRL):
             raise ValueError("SharedVecKBRL learns through its proposal rounds: algorithm=%r is not supported (the rounds learn by "
                              "the margin rule of 'projectron_plus' with shared_plus=True; or fit a per-replica VecKBRL, then "
                              "to_shared)" % kw['algorithm'])
+        if kw.get('online_prune') is not None:
+            raise ValueError("SharedVecKBRL holds no budget in the loop: online_prune=%r is not supported (prune() between steps "
+                             "brings its dictionaries down to a target; or run a per-replica VecKBRL with online_prune)" % (kw['online_prune'],))
         super().__init__(n_envs, dims, n_prbs, shared=True, **kw)
         self.budget, self.max_rounds = budget, max_rounds
         self.exchange = exchange

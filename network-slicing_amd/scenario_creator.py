@@ -50,11 +50,14 @@ def create_env(rng, n, slots_per_step=50, propagation_type='macro_cell_urban_2GH
     return make('gym_ran_slice:RanSlice-v1', node_b=node, penalty=penalty)
 
 
-def create_kbrl_agent(rng, n, accuracy_range=[0.99, 0.999], device=0, capacity=4096):
+def create_kbrl_agent(rng, n, accuracy_range=[0.99, 0.999], device=0, capacity=4096, budget=None):
     """scenario_creator.py:197-238: one Projectron learner per slice, random initial action/offset.
     capacity: most landmarks a learner's dictionary may hold -- a limit, not a reservation: dictionaries take their
     storage from a pool 64 landmarks at a time (the authors' 50,400-step runs end at 45-305 landmarks on average, 1,025 at
-    most).  A dictionary that reaches it projects instead of growing and KBRL_Control.run warns."""
+    most).  A dictionary that reaches it projects instead of growing and KBRL_Control.run warns.
+    budget: number of support vectors in memory, the parameter the reference's docstring names -- every learner is held to
+    that many landmarks by the budget stage behind each update_control (VecKBRL.set_online_prune; 64 <= budget <=
+    capacity - 64).  None: unbudgeted, as before."""
     sc = scenarios[n]
     n_prbs, n_embb, n_mmtc = sc['n_prbs'], sc['n_embb'], sc['n_mmtc']
     embb_dim, mmtc_dim = len(state_variables_embb), len(state_variables_mmtc)
@@ -74,4 +77,4 @@ def create_kbrl_agent(rng, n, accuracy_range=[0.99, 0.999], device=0, capacity=4
         i += mmtc_dim
     seed = int(rng.integers(0, 2 ** 63 - 1))
     return KBRL_Control(learners, n_prbs, alfa=alfa, accuracy_range=accuracy_range, device=device, seed=seed,
-                        capacity=capacity)
+                        capacity=capacity, budget=budget)

@@ -17,6 +17,9 @@ PRUNE = ['prune_list_kernel', 'prune_choose_kernel', 'prune_plan_kernel', 'prune
 # kb_shared_prune's kernels (kb_shared_prune.hip): the same rule on full storage, reported beside them and held to no scratch as well
 PRUNE_SHARED = ['prune_shared_choose_kernel', 'prune_shared_plan_kernel', 'prune_shared_downdate_kernel', 'prune_shared_move_kernel',
                 'prune_shared_finish_kernel']
+# the online budget's kernels (kb_online_prune.hip): the stage's list and its persistent choose / move / finish
+# kernel, reported beside kb_prune's (whose plan and downdate the stage launches as they are) and held to no scratch as well
+ONLINE_PRUNE = ['budget_list_kernel', 'budget_round_kernel']
 # kb_deploy_ref's kernels (kb_ref.hip): reported, and held to no scratch at all, as they are built and documented
 REF_SCRATCH = {'select_ref_kernel': 0, 'ref_gather_kernel': 0}
 # the agent-file kernels (kb_agents.hip): reported, and held to no scratch at all -- pack and build are pure streaming kernels
@@ -158,7 +161,7 @@ def check(path=LOG):
                                                                            r.get('LDS Size')))
         if r.get('ScratchSize', 0) > 0:
             bad.append('%s spills %d B/lane (> 0)' % (key, r['ScratchSize']))
-    for key in AGENTS + BRIDGE + FORK:
+    for key in ONLINE_PRUNE + AGENTS + BRIDGE + FORK:
         hit = [k for k in res if re.search(r'\d' + key, k)]  # (the whole mangled name: share_* is not unshare_*)
         if not hit:
             bad.append('%s: not found in %s' % (key, path))
