@@ -1,7 +1,7 @@
 // kb_online_prune.hip -- the online budget: kb_prune's removal rule as a stage of the closed loop.
-// #included by rs_api.hip after kb_prune.hip: it uses that file's argument block, its accessors (prune_at / prune_get / prune_set),
-// its work line (prune_plan_kernel) and its downdate (prune_downdate_kernel: both already read the list's length from device
-// memory and run at a geometry fixed by the handle), and changes none of its kernels.
+// #included by rs_api.hip after kb_prune.hip: the rule's device functions (prune_list, prune_choose, prune_move, prune_chains), its
+// argument block, its work line (prune_plan_kernel) and its downdate (prune_downdate_kernel: both already read the list's length
+// from device memory and run at a geometry fixed by the handle) and its scratch arrays behind the handle are that file's.
 //
 // kb_set_online_prune(k, target, rounds): every update phase -- kb_update_control, kb_step_resident, kb_run_resident, plain or
 // captured -- is followed by a BUDGET STAGE before anything else reads the dictionaries: every dictionary with m > target loses
@@ -21,15 +21,14 @@
 // workgroup owns a dictionary for the whole call, so move, choose and finish of one dictionary are ordered by __syncthreads and
 // different dictionaries share nothing.  A stage with nothing over the target finds the length 0 everywhere and returns at once.
 //
-// The bits.  Choose, move and finish below restate kb_prune.hip's kernels statement for statement around a loop over the list; no
-// sum is formed, so a dictionary comes out as kb_prune(target) leaves it whenever `rounds` covers its excess, whatever the
-// launch, the grid or the other dictionaries.  (tests/test_gpu_online_prune.py holds the stage to that, and to tests/prune_mirror.py.)
+// The bits.  Choose and move are kb_prune.hip's prune_choose and prune_move, called in a loop over the list; no sum is formed,
+// so a dictionary comes out as kb_prune(target) leaves it whenever `rounds` covers its excess, whatever the launch, the grid
+// or the other dictionaries.  (tests/test_gpu_online_prune.py holds the stage to that, and to tests/prune_mirror.py.)
 //
 // A dictionary whose Kinv diagonal is not finite and positive (or whose coefficient is not finite) is left as kb_prune leaves it --
 // untouched when met in the stage's first removal, stopped after the completed ones otherwise -- and its replica gets the sticky
 // bit KB_FLAG_PRUNE_REFUSED in its flag word (kb_get_flags): the loop cannot return RS_ESTATE from the device.
 
-#define KB_FLAG_PRUNE_REFUSED 32
 #define KB_ONLINE_ROUNDS_MAX 64
 #define KB_BUDGET_CHOOSE 1
 #define KB_BUDGET_MOVE 2
@@ -44,161 +43,18 @@ struct BudgetArgs {
     int32_t* marked;           // [n_dict] 1: counted in work[4]
 };
 
-// prune_list_kernel, and the stage's counters
+// prune_list, and the stage's counters
 __global__ __launch_bounds__(1024) void budget_list_kernel(BudgetArgs b) {
     __shared__ int part[1024];
     __shared__ int most;
-    const PruneArgs& a = b.p;
-    const int t = threadIdx.x, n = a.n_dict, per = (n + 1023) / 1024;
-    const int i0 = t * per < n ? t * per : n, i1 = i0 + per < n ? i0 + per : n;
-    if (t == 0) most = 0;
-    int cnt = 0, mx = 0;
-    for (int i = i0; i < i1; ++i) {
-        const int over = a.K.m[i] - a.target;
-        if (over > 0) {
-            ++cnt;
-            mx = over > mx ? over : mx;
-        }
-    }
-    part[t] = cnt;
-    __syncthreads();
-    if (mx > 0) atomicMax(&most, mx);
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int at = t ? part[t - 1] : 0;
-    for (int i = i0; i < i1; ++i)
-        if (a.K.m[i] > a.target) {
-            a.list[at] = i;
-            a.stat[at] = 0;
-            a.removed[at] = 0;
-            ++at;
-        }
-    if (t == 0) {
-        a.info[0] = (unsigned long long)part[1023];
-        a.info[1] = (unsigned long long)most;
+    prune_list(b.p, part, most);
+    if (threadIdx.x == 0) {
         b.work[0] += 1ull;
         if ((unsigned long long)most > b.work[3]) b.work[3] = (unsigned long long)most;
     }
 }
 
-// prune_choose_kernel's body for list place li (steps 1-3); every branch is uniform over the workgroup
-__device__ __forceinline__ void budget_choose(const PruneArgs& a, int li, unsigned long long (&wkey)[4], int (&widx)[4], int (&wbad)[4]) {
-    const KbState& K = a.K;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (a.stat[li] != 0) return;
-    const int dict = a.list[li];
-    const int m = K.m[dict];
-    if (m <= a.target) {
-        if (tid == 0) a.stat[li] = 1;
-        return;
-    }
-    const uint64_t* sh = shells_of(a.D, K, dict);
-    unsigned long long best = ~0ull;
-    int bidx = 0x7fffffff, bad = 0;
-    for (int j = tid; j < m; j += 256) {
-        const double c = *vec_at(K, sh, KB_ROW_CO, j);
-        const double pjj = *prune_at(K, sh, j, j);
-        if (!(pjj > 0.0) || !__builtin_isfinite(pjj) || !__builtin_isfinite(c)) {
-            bad = 1;
-        } else {
-            const unsigned long long key = (unsigned long long)__double_as_longlong((c * c) / pjj);
-            if (key < best) {  // (j increases: the first of equal keys stays)
-                best = key;
-                bidx = j;
-            }
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long ok = __shfl_xor(best, o);
-        const int oi = __shfl_xor(bidx, o);
-        bad |= __shfl_xor(bad, o);
-        if (ok < best || (ok == best && oi < bidx)) {
-            best = ok;
-            bidx = oi;
-        }
-    }
-    if (lane == 0) {
-        wkey[wv] = best;
-        widx[wv] = bidx;
-        wbad[wv] = bad;
-    }
-    __syncthreads();
-    for (int w = 0; w < 4; ++w) {  // (every thread walks the four waves: the same winner everywhere)
-        bad |= wbad[w];
-        if (w == 0 || wkey[w] < best || (wkey[w] == best && widx[w] < bidx)) {
-            best = wkey[w];
-            bidx = widx[w];
-        }
-    }
-    if (bad) {
-        if (tid == 0) {
-            a.stat[li] = a.removed[li] > 0 ? 3 : 2;
-            atomicOr(&K.err[dict / a.D.S], KB_FLAG_PRUNE_REFUSED);  // (one agent per replica: dictionary = task)
-        }
-        return;
-    }
-    const int r = bidx;
-    const double q = *prune_at(K, sh, r, r), cr = *vec_at(K, sh, KB_ROW_CO, r);
-    if (tid == 0) {
-        a.vict[li] = r;
-        a.q[li] = q;
-    }
-    for (int i = tid; i < m; i += 256) {
-        const double p = prune_get(K, sh, i, r);
-        *vec_at(K, sh, KB_ROW_DS, i) = p;
-        if (i != r) {
-            double* ci = vec_at(K, sh, KB_ROW_CO, i);
-            *ci = *ci + cr * ((-p) / q);
-        }
-    }
-}
-
-// prune_move_kernel's body for list place li (steps 5-7)
-__device__ __forceinline__ void budget_move(const PruneArgs& a, int li) {
-    const KbState& K = a.K;
-    const int tid = threadIdx.x;
-    if (a.stat[li] != 0) return;
-    const int dict = a.list[li];
-    const uint64_t* sh = shells_of(a.D, K, dict);
-    const int m = K.m[dict], r = a.vict[li], last = m - 1;
-    const bool f32 = a.D.dims[dict % a.D.S] == 10;
-    double* Pl = vec_page(K, sh, last >> 6);
-    const int ll = last & 63;
-    if (r != last) {
-        for (int k = tid; k < m; k += 256)
-            if (k != r && k != last) prune_set(K, sh, r, k, prune_get(K, sh, last, k));
-        if (tid == 0) prune_set(K, sh, r, r, prune_get(K, sh, last, last));
-        double* Pr = vec_page(K, sh, r >> 6);
-        const int lr = r & 63;
-        if (tid >= 64 && tid < 64 + (f32 ? KB_ROW_F32 : KB_ROW_CO)) Pr[(tid - 64) * KB_CH + lr] = Pl[(tid - 64) * KB_CH + ll];
-        if (f32 && tid >= 128 && tid < 138)
-            ((float*)(Pr + KB_ROW_F32 * KB_CH))[(tid - 128) * KB_CH + lr] = ((const float*)(Pl + KB_ROW_F32 * KB_CH))[(tid - 128) * KB_CH + ll];
-        if (tid == 192) Pr[KB_ROW_CO * KB_CH + lr] = Pl[KB_ROW_CO * KB_CH + ll];
-        if (tid == 193) ((int32_t*)(Pr + KB_ROW_IDX * KB_CH))[lr] = ((const int32_t*)(Pl + KB_ROW_IDX * KB_CH))[ll];
-    }
-    __syncthreads();  // (row m - 1 and slot m - 1 have been read)
-    const int bl = last >> 6;
-    for (int e = tid; e < (bl + 1) * 64; e += 256) kinv_tile_lo(K, sh, bl, e >> 6)[ll * 64 + (e & 63)] = 0.0;
-    if (tid < 64) kinv_tile_lo(K, sh, bl, bl)[tid * 64 + ll] = 0.0;
-    if (tid >= 64 && tid < 64 + (f32 ? KB_ROW_F32 : KB_ROW_CO)) Pl[(tid - 64) * KB_CH + ll] = 0.0;
-    if (f32 && tid >= 128 && tid < 138) ((float*)(Pl + KB_ROW_F32 * KB_CH))[(tid - 128) * KB_CH + ll] = 0.0f;
-    if (tid >= 192 && tid < 192 + 5) Pl[(KB_ROW_CO + tid - 192) * KB_CH + ll] = 0.0;  // coefficient, D0, E, K_f, d*
-    if (tid == 200) {
-        int32_t* ix = (int32_t*)(Pl + KB_ROW_IDX * KB_CH);
-        ix[ll] = 0;
-        ix[64 + ll] = 0;
-    }
-    if (tid == 0) {
-        K.m[dict] = last;
-        a.removed[li] += 1;
-    }
-}
-
-// prune_finish_kernel's body for list place li, and the stage's counters: a dictionary still active and above the target is
+// prune_finish_kernel's work for list place li with the stage's counters: a dictionary still active and above the target is
 // carried; one that met a bad entry is marked, once since kb_reset
 __device__ __forceinline__ void budget_finish(const BudgetArgs& b, int li, int& off) {
     const PruneArgs& a = b.p;
@@ -211,27 +67,7 @@ __device__ __forceinline__ void budget_finish(const BudgetArgs& b, int li, int& 
         if ((st == 2 || st == 3) && atomicExch(&b.marked[dict], 1) == 0) atomicAdd(&b.work[4], 1ull);
     }
     if (n == 0) return;
-    const uint64_t* sh = shells_of(a.D, K, dict);
-    const int m = K.m[dict];
-    if (tid == 0) off = 0;
-    __syncthreads();
-    int prev = -1, cnt = 0;
-    for (int j = 0; j < m; ++j) {
-        int32_t* ix = idx_at(K, sh, j);
-        if (ix[0] == tid) {
-            ix[64] = prev;
-            prev = j;
-        }
-    }
-    K.head[(size_t)dict * KB_HEAD + tid] = prev;
-    for (int j = tid; j < m; j += 256) {
-        int32_t* ix = idx_at(K, sh, j);
-        if (ix[0] < 0) {
-            ix[64] = -1;
-            ++cnt;
-        }
-    }
-    if (cnt) atomicAdd(&off, cnt);
+    prune_chains(a, dict, off);
     __syncthreads();
     if (tid == 0) {
         K.offgrid[dict] = off;
@@ -253,10 +89,10 @@ __global__ __launch_bounds__(256) void budget_round_kernel(BudgetArgs b, int wha
     const int count = (int)b.p.info[0];
     for (int li = blockIdx.x; li < count; li += gridDim.x) {
         if (what & KB_BUDGET_MOVE) {
-            budget_move(b.p, li);
+            prune_move<KinvTri>(b.p, li);
             __syncthreads();
         }
-        if (what & KB_BUDGET_CHOOSE) budget_choose(b.p, li, wkey, widx, wbad);
+        if (what & KB_BUDGET_CHOOSE) prune_choose<KinvTri, true>(b.p, li, wkey, widx, wbad);
         if (what & KB_BUDGET_FINISH) budget_finish(b, li, off);
         __syncthreads();  // (the shared words are the next place's)
     }
@@ -264,12 +100,13 @@ __global__ __launch_bounds__(256) void budget_round_kernel(BudgetArgs b, int wha
 
 }  // namespace kb
 
-// what the switch keeps behind a handle, outside its saved regions (created when it is first set; the pruned counters are kb_prune's)
+// What the switch keeps behind a handle, outside its saved regions (created when it is first set).  The list, victim, q, status,
+// removed and base arrays and the pruned counters are k->prune's, shared with kb_prune: every kernel that touches them is enqueued
+// on k->stream, each call and each stage begins with its own list kernel, and kb_prune_release runs only from kb_destroy, so a
+// captured loop keeps valid pointers.  d_info stays apart: the stage counts its own units of the downdate (kb_online_prune_info).
 struct kb_online_prune_state {
     int32_t target = 0, rounds = 2;
-    int32_t *d_list = nullptr, *d_vict = nullptr, *d_stat = nullptr, *d_removed = nullptr, *d_marked = nullptr;
-    double* d_q = nullptr;
-    long long* d_base = nullptr;
+    int32_t* d_marked = nullptr;
     unsigned long long *d_info = nullptr, *d_work = nullptr;
     int grid = 1024;  // budget_round_kernel's persistent workgroups
 };
@@ -277,7 +114,7 @@ struct kb_online_prune_state {
 static void kb_online_prune_release(kb_handle* k) {
     kb_online_prune_state* p = k->oprune;
     if (!p) return;
-    void* ds[] = {p->d_list, p->d_vict, p->d_stat, p->d_removed, p->d_marked, p->d_q, p->d_base, p->d_info, p->d_work};
+    void* ds[] = {p->d_marked, p->d_info, p->d_work};
     for (void* d : ds)
         if (d) (void)hipFree(d);
     delete p;
@@ -294,18 +131,12 @@ static void kb_online_prune_restart(kb_handle* k) {
 }
 
 static int kb_online_prune_prepare(kb_handle* k) {
-    int rc = kb_prune_prepare(k);  // (the pruned counters, and the downdate's grid)
+    int rc = kb_prune_prepare(k, kb::prune_downdate_kernel);  // (the scratch arrays, the pruned counters, the downdate's grid)
     if (rc != RS_OK || k->oprune) return rc;
     kb_online_prune_state* p = new kb_online_prune_state();
     k->oprune = p;  // (kb_destroy frees whatever was allocated)
     const size_t nd = (size_t)k->n_dict;
-    HIPCHK(k, hipMalloc((void**)&p->d_list, sizeof(int32_t) * nd));
-    HIPCHK(k, hipMalloc((void**)&p->d_vict, sizeof(int32_t) * nd));
-    HIPCHK(k, hipMalloc((void**)&p->d_stat, sizeof(int32_t) * nd));
-    HIPCHK(k, hipMalloc((void**)&p->d_removed, sizeof(int32_t) * nd));
     HIPCHK(k, hipMalloc((void**)&p->d_marked, sizeof(int32_t) * nd));
-    HIPCHK(k, hipMalloc((void**)&p->d_q, sizeof(double) * nd));
-    HIPCHK(k, hipMalloc((void**)&p->d_base, sizeof(long long) * (nd + 1)));
     HIPCHK(k, hipMalloc((void**)&p->d_info, sizeof(unsigned long long) * 8));
     HIPCHK(k, hipMalloc((void**)&p->d_work, sizeof(unsigned long long) * 8));
     HIPCHK(k, hipMemsetAsync(p->d_marked, 0, sizeof(int32_t) * nd, k->stream));
@@ -322,19 +153,8 @@ static int launch_online_prune(kb_handle* k) {
     if (!p || p->target == 0) return RS_OK;
     kb::BudgetArgs b;
     memset(&b, 0, sizeof b);
-    kb::PruneArgs& a = b.p;
-    a.D = k->D;
-    a.K = k->K;
-    a.target = p->target;
-    a.n_dict = k->n_dict;
-    a.list = p->d_list;
-    a.vict = p->d_vict;
-    a.q = p->d_q;
-    a.stat = p->d_stat;
-    a.removed = p->d_removed;
-    a.base = p->d_base;
-    a.pruned = k->prune->d_pruned;
-    a.info = p->d_info;
+    b.p = kb_prune_args(k, p->target, p->d_info);
+    const kb::PruneArgs& a = b.p;
     b.work = p->d_work;
     b.marked = p->d_marked;
     const dim3 grid((unsigned)p->grid), down((unsigned)k->prune->grid);

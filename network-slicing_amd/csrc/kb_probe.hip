@@ -28,6 +28,9 @@
 //                      kernel with on this handle: host state of kb_prune_state, chosen by the first prune call the handle
 //                      takes (RS_ESTATE before it).  With the plan's prefix sums it gives the stretch of every wave
 //                      (tests/test_gpu_prune_chain.py)
+//   kb_dev_set_prune_grid  the one entry point that changes host state: the downdate's grid of the handle's later prune calls, from
+//                      1 to the grid the handle chose (never more than one co-resident round; RS_EINVAL outside, RS_ESTATE before
+//                      the first prune call) -- few waves make stretches of many units on a handle of few dictionaries
 // By-reference handles (kb_ref.hip) answer the first two: their scores are per task as everywhere (they keep no W: zeros), their rows are
 // those of the store's dictionary the map names for (e, s) -- which no selection may ever have changed.
 //
@@ -213,6 +216,20 @@ extern "C" int kb_dev_get_prune_grid(kb_handle* k, int32_t* grid) {
         return RS_ESTATE;
     }
     *grid = (int32_t)k->prune->grid;
+    return RS_OK;
+}
+
+extern "C" int kb_dev_set_prune_grid(kb_handle* k, int32_t grid) {
+    if (!k) return RS_EINVAL;
+    if (!k->prune) {
+        k->err = "kb_dev_set_prune_grid: the handle has taken no prune call yet (the first one chooses the grid)";
+        return RS_ESTATE;
+    }
+    if (grid < 1 || grid > k->prune->grid_most) {
+        k->err = "kb_dev_set_prune_grid: grid " + std::to_string(grid) + " is outside 1 .. " + std::to_string(k->prune->grid_most) + " (one co-resident round)";
+        return RS_EINVAL;
+    }
+    k->prune->grid = grid;
     return RS_OK;
 }
 

@@ -357,15 +357,15 @@ def _grow(sizes10, sizes3, capacity, dev_build=False):
     return ag
 
 
-def _base(size, shared):
+def _base(size, shared, dev_build=False):
     """-> (handle, pristine blob) of the two dictionaries the forced cases work on: size landmarks of ten state variables and
     193 (size 193) or 130 (size 321) of three; shared: the same two through to_shared, three replicas.  Every case begins by
-    loading an edited copy of the blob"""
-    key = ('base', size, shared)
+    loading an edited copy of the blob.  dev_build: handles of the test build, made while RANSLICE_DEV_BUILD is set"""
+    key = ('base', size, shared, dev_build)
     if key not in _cache:
-        src_key = ('base', size, False)
+        src_key = ('base', size, False, dev_build)
         if src_key not in _cache:
-            ag = _grow((size,), (193 if size == 193 else 130,), 256 if size == 193 else 384)
+            ag = _grow((size,), (193 if size == 193 else 130,), 256 if size == 193 else 384, dev_build=dev_build)
             _cache[src_key] = (ag, ag.save_state())
         if shared:
             X = _cache[src_key][0]
@@ -569,6 +569,12 @@ def _prune_grid(h):
     return int(g.value)
 
 
+def _set_prune_grid(h, grid):
+    h.L.kb_dev_set_prune_grid.argtypes = [C.c_void_p, C.c_int32]
+    h.L.kb_dev_set_prune_grid.restype = C.c_int
+    return h.L.kb_dev_set_prune_grid(h.h, grid)
+
+
 def test_stretches_across_dictionaries():
     """Four source dictionaries of 4, 5, 6 and 7 blocks, forked in a shuffled order into one handle, as many copies as make one
     round's work line at least three times as long as the waves prune_downdate_kernel is launched with (its grid: host state,
@@ -651,3 +657,51 @@ def test_stretches_across_dictionaries():
         assert dev.work() == (units, 1), (dev.work(), units)
         big.close()
         src.close()
+
+
+@pytest.mark.parametrize('grid', [1, 2])
+def test_shared_stretches(grid):
+    """The same on full storage, where a shared handle's S dictionaries never fill the waves of a co-resident round: the
+    downdate's grid is SET to 1 and 2 workgroups (kb_dev_set_prune_grid of the test build), so that the 4 and 8 waves of
+    prune_shared_downdate_kernel walk stretches of 45, and of 22 or 23, units of the round's work line.  The shared pair of 321
+    and 130 landmarks (6 and 3 blocks: 6 * 6 * 4 + 3 * 3 * 4 = 180 units); dictionary 0 is edited to stop after its first
+    removal (_stop_after_one), and shrink(129) takes dictionary 1 to the target in the same single round with work: RS_ESTATE
+    with the whole message, both dictionaries where one removal of their mirrors leaves them as bytes -- both stored triangles,
+    pages, chains, caches, counters (_hold through _Run.call) --, the work counters at that round's closed form.  Every stretch
+    is at least 3 units long, at least one begins inside a tile, at least one crosses from dictionary 0 into dictionary 1."""
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv('RANSLICE_DEV_BUILD', '1')
+        h, blob = _base(321, True, dev_build=True)
+        dev = _edited(h, blob, lambda dev, v: _stop_after_one(dev, v, 0, 10))
+        sizes = [int(m) for m in h.dictionary_sizes()]
+        assert sizes == [321, 130]
+        assert h.shrink(384) == 0                        # nothing to do: the call only chooses the grid
+        chosen = _prune_grid(h)
+        run = _Run(h)
+        assert run.dev.work() == (0, 0)
+        try:
+            for bad in (0, -1, chosen + 1):                # (no handle launches more than one co-resident round)
+                assert _set_prune_grid(h, bad) == _lib.RS_EINVAL and _prune_grid(h) == chosen
+            assert chosen >= grid and _set_prune_grid(h, grid) == _lib.RS_OK and _prune_grid(h) == grid
+            logs = run.call(129, 'shared stretches, grid %d' % grid, expect=REFUSED % ('kb_shared_prune', 1, 0, 1), stops={0: 1})
+            assert _prune_grid(h) == grid
+        finally:
+            assert _set_prune_grid(h, chosen) == _lib.RS_OK
+        assert logs[0][0]['slot'] == 10 and len(logs[0]) == 1 and len(logs[1]) == 1
+        assert (np.diag(run.mirrors[0].P) <= 0.0).sum() == 1, 'the second round must meet exactly one diagonal entry that is not positive'
+        assert list(h.dictionary_sizes()) == [320, 129] and list(h.pruned().reshape(-1)) == [1, 1]
+        # the stretches of the round with work, from the plan's prefix sums and the grid as wave_share computes them
+        base = np.concatenate([[0], np.cumsum([dev.line(m) for m in sizes])]).astype(np.int64)
+        total, waves = int(base[-1]), 4 * grid
+        assert total == 6 * 6 * 4 + 3 * 3 * 4 == 180
+        w = np.arange(waves, dtype=np.int64)
+        lo, hi = total * w // waves, total * (w + 1) // waves
+        assert (hi - lo >= 3).all()
+        slot = np.searchsorted(base, lo, side='right') - 1
+        crosses = int((hi > base[slot + 1]).sum())
+        inside = int((((lo - base[slot]) & 3) != 0).sum())
+        print('work line %d units over %d waves: stretches of %d..%d units, %d cross a dictionary boundary, %d begin inside a tile'
+              % (total, waves, (hi - lo).min(), (hi - lo).max(), crosses, inside))
+        assert crosses >= 1 and inside >= 1
+        # the work counters: one round with work, the units of both dictionaries that hold rows
+        assert dev.work() == (sum(dev.units(m) for m in sizes), 1), dev.work()
