@@ -725,6 +725,37 @@ int kb_shared_prune(kb_handle* k, int32_t target, uint64_t* removed_total);
 int kb_set_online_prune(kb_handle* k, int32_t target, int32_t rounds);
 int kb_get_online_prune(kb_handle* k, int32_t* target, int32_t* rounds);
 int kb_online_prune_info(kb_handle* k, uint64_t work[8]);
+/* ---- The online budget of a SHARED-dictionary handle (csrc/kb_shared_online_prune.hip): kb_shared_prune's rule
+ * as the last stage of every shared learning step.
+ * kb_set_shared_online_prune(k, target, rounds): target 0 = off, the default.  When on, every kb_shared_step and
+ * kb_shared_step_resident that returns RS_OK from its rounds has enqueued, on the agent's stream behind its last round and in
+ * front of whatever reads the dictionaries next (in the resident step: select_action, whose scores the next step's first scan
+ * reuses), a budget stage: every shared dictionary with m > target loses min(m - target, rounds) landmarks by kb_prune's removal
+ * on full storage and is finished once as kb_shared_prune finishes it (chains, off-grid count, version, the predict cache of
+ * EVERY replica of the slice).  No sum is formed: a dictionary comes out bit for bit as kb_shared_prune(k, target) at the same
+ * point leaves it whenever `rounds` covers its excess; what is left above the target the following stages take (carry).
+ * Nothing in the stage waits for the host: 2 + 3 * rounds launches, the same whatever the dictionaries hold, which return at
+ * once while nothing is over the target; a step that leaves with RS_EHIP enqueues none.  A dictionary whose Kinv diagonal is
+ * not finite and positive, or whose coefficient is not finite, is left as kb_shared_prune leaves it and EVERY local replica
+ * gets bit 32 of its flag word (kb_get_flags): the dictionary serves them all.  kb_get_pruned counts the removals.
+ * The setting is host state of the handle: in no kb_save_state blob, kept by kb_reset and by kb_load_state into the handle; a
+ * handle made by kb_create (what kb_share fills) starts with it off.  Nothing depends on rank or communicator and nothing is
+ * exchanged: ranks that set the same value keep bit-identical dictionaries, as with kb_set_shared_plus, and like there nothing
+ * checks the value across ranks -- the caller sets the same one on every rank before the same step.
+ * RS_EINVAL: target neither 0 nor in 64 .. capacity - 1 (a shared dictionary at its capacity projects: no headroom shell);
+ * rounds outside 1 .. 64.  RS_ESTATE: a per-replica handle (kb_set_online_prune is the call there), kb_reset missing, a round
+ * open between kb_shared_scan and kb_shared_commit.  A refusal leaves the earlier setting in place.
+ * kb_get_shared_online_prune: the setting ((0, 2) on a handle it was never set on).
+ * kb_shared_online_prune_info: kb_online_prune_info's words for these stages, restarted wherever kb_get_pruned's counters are (kb_reset, kb_load_state):
+ * work[0] stages enqueued, [1] landmarks removed, [2] dictionary-stages left above the target (carry), [3] the largest excess a
+ * stage met, [4] dictionaries flagged (each once), [5] units of the downdate that held rows; [6], [7] reserved (0).
+ * kb_shared_online_prune_stage: enqueues ONE stage with the handle's setting and returns without waiting -- for the host-driven
+ * rounds (kb_shared_scan / kb_shared_apply / kb_shared_commit), where only the caller knows that a step's rounds are over.
+ * RS_ESTATE while the switch is off, while a round is open, or on a per-replica handle. */
+int kb_set_shared_online_prune(kb_handle* k, int32_t target, int32_t rounds);
+int kb_get_shared_online_prune(kb_handle* k, int32_t* target, int32_t* rounds);
+int kb_shared_online_prune_info(kb_handle* k, uint64_t work[8]);
+int kb_shared_online_prune_stage(kb_handle* k);
 /* ---- the learner's own surface, batched (csrc/kb_fit.hip): sample sequences in, trained learners out; query
  * sets in, scores out.  Build-defined: the reference has Projectron.predict(x) / update(x, y), one sample per call.
  *

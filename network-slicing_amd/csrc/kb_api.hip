@@ -101,7 +101,7 @@ struct kb_handle {
     uint64_t* d_fork_base = nullptr; // [n_dict + 1] first pool double of every dictionary (exclusive scan of its shells' sizes)
     uint64_t* h_fork_total = nullptr;  // pinned: the scan's total
     kb_prune_state* prune = nullptr; // kb_prune's lists and the pruned counters: NOT a saved region (kb_prune.hip)
-    kb_online_prune_state* oprune = nullptr;  // kb_set_online_prune: the budget stage's setting, lists and counters; host state of the handle, never copied or saved (kb_online_prune.hip)
+    kb_online_prune_state* oprune = nullptr;  // kb_set_online_prune: the budget stage's setting, lists and counters; host state of the handle, never copied or saved (kb_online_prune.hip; on a shared handle kb_set_shared_online_prune's: kb_shared_online_prune.hip)
     kb_rebuild_state* rebuild = nullptr;  // kb_fork_rebuild into this handle: its plan, result words and timing (kb_rebuild.hip)
     kb_bridge_state* bridge = nullptr;    // kb_unshare / kb_share into this handle: result words, timing and plan bytes (kb_bridge.hip)
     kb_fit_state* fit = nullptr;          // kb_fit / kb_score on this handle: the counters and the timing of the last calls (kb_fit.hip)
@@ -120,6 +120,7 @@ static void kb_prune_restart(kb_handle* k);  // the pruned counters start over (
 static void kb_online_prune_release(kb_handle* k);  // kb_online_prune.hip
 static void kb_online_prune_restart(kb_handle* k);  // its counters start over with them
 static int launch_online_prune(kb_handle* k);       // the budget stage behind an update phase (nothing while the switch is off)
+static int launch_shared_online_prune(kb_handle* k);  // the same behind a shared learning step (kb_shared_online_prune.hip)
 // by-reference handles (kb_ref.hip): their dictionaries live in a store handle, (replica, slice) -> dictionary through a map
 static void kb_ref_release(kb_handle* k);
 static void kb_rebuild_release(kb_handle* k);  // kb_rebuild.hip
@@ -1537,7 +1538,9 @@ static int shared_step_core(kb_handle* k, const float* d_state, const int32_t* d
         rounds = rnd + 1;
     }
     if (rounds_out) *rounds_out = rounds;
-    return RS_OK;
+    // kb_set_shared_online_prune: the budget stage, behind the last round (also the one the early break above did not wait for)
+    // and in front of whatever reads the dictionaries next; a step that left with an error above enqueues none
+    return launch_shared_online_prune(k);
 }
 
 // One learning step of the shared-dictionary mode, exchange included, with every buffer on the device:
@@ -1602,7 +1605,9 @@ extern "C" int kb_shared_step_resident(kb_handle* k, rs_handle* env, int32_t bud
                              hipMemcpyDeviceToDevice, k->stream));
     if ((rc = stream_after(k, &k->ev_order, k->stream, env->stream)) != RS_OK) return rc;
     HIPCHK(k, hipGetLastError());
-    k->gemm_fresh = true;  // workF / workE now describe d_prev_state; nothing learns before the next step's first scan
+    // workF / workE now describe d_prev_state; nothing learns before the next step's first scan.  (With kb_set_shared_online_prune
+    // the budget stage was enqueued by shared_step_core, in front of launch_select: the scores are those of the pruned dictionaries.)
+    k->gemm_fresh = true;
     return RS_OK;
 }
 

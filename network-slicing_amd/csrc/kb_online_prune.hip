@@ -150,7 +150,7 @@ static int kb_online_prune_prepare(kb_handle* k) {
 // when the switch is off
 static int launch_online_prune(kb_handle* k) {
     kb_online_prune_state* p = k->oprune;
-    if (!p || p->target == 0) return RS_OK;
+    if (!p || p->target == 0 || k->D.shared) return RS_OK;  // (a shared handle's state is kb_set_shared_online_prune's)
     kb::BudgetArgs b;
     memset(&b, 0, sizeof b);
     b.p = kb_prune_args(k, p->target, p->d_info);
@@ -182,7 +182,8 @@ extern "C" int kb_set_online_prune(kb_handle* k, int32_t target, int32_t rounds)
         return RS_EINVAL;
     }
     if (k->D.shared) {
-        k->err = "kb_set_online_prune: shared-dictionary handles are not supported: prune them between steps with kb_shared_prune";
+        k->err = "kb_set_online_prune: shared-dictionary handles are not supported: prune them between steps with kb_shared_prune "
+                 "(their own switch is kb_set_shared_online_prune)";
         return RS_ESTATE;
     }
     if (k->ref) {
@@ -218,16 +219,16 @@ extern "C" int kb_set_online_prune(kb_handle* k, int32_t target, int32_t rounds)
 
 extern "C" int kb_get_online_prune(kb_handle* k, int32_t* target, int32_t* rounds) {
     if (!k || !target || !rounds) return RS_EINVAL;
-    *target = k->oprune ? k->oprune->target : 0;
-    *rounds = k->oprune ? k->oprune->rounds : 2;
+    const bool set = k->oprune && !k->D.shared;  // (a shared handle's state is kb_set_shared_online_prune's: kb_shared_online_prune.hip)
+    *target = set ? k->oprune->target : 0;
+    *rounds = set ? k->oprune->rounds : 2;
     return RS_OK;
 }
 
 // since kb_reset: work[0] stages enqueued, [1] landmarks removed, [2] dictionary-stages left above the target (carry), [3] the
 // largest excess a stage met, [4] dictionaries flagged, [5] the downdate's units that held rows (8 KB read + 8 KB written each);
 // [6], [7] reserved
-extern "C" int kb_online_prune_info(kb_handle* k, uint64_t work[8]) {
-    if (!k || !work) return RS_EINVAL;
+static int kb_online_prune_words(kb_handle* k, uint64_t work[8]) {
     const int rc = kb_read_words(k, k->oprune ? k->oprune->d_work : nullptr, 8, work);
     if (rc != RS_OK || !k->oprune) return rc;
     uint64_t info[8];
@@ -236,4 +237,13 @@ extern "C" int kb_online_prune_info(kb_handle* k, uint64_t work[8]) {
     work[5] = info[5];
     work[6] = work[7] = 0;
     return RS_OK;
+}
+
+extern "C" int kb_online_prune_info(kb_handle* k, uint64_t work[8]) {
+    if (!k || !work) return RS_EINVAL;
+    if (k->D.shared) {  // (never set here: the shared stages' counters are kb_shared_online_prune_info's)
+        for (int q = 0; q < 8; ++q) work[q] = 0;
+        return RS_OK;
+    }
+    return kb_online_prune_words(k, work);
 }

@@ -1795,6 +1795,7 @@ extern "C" int rs_load_state(rs_handle* h, const void* blob, uint64_t bytes) {
 #include "kb_prune.hip"
 #include "kb_online_prune.hip"
 #include "kb_shared_prune.hip"
+#include "kb_shared_online_prune.hip"
 #include "kb_ref.hip"
 #include "kb_agents.hip"
 #include "kb_rebuild.hip"

@@ -22,6 +22,7 @@ KB_EXPORTS = (
     'kb_prune', 'kb_get_pruned', 'kb_prune_time_ms', 'kb_get_prune_work',
     'kb_shared_prune',
     'kb_set_online_prune', 'kb_get_online_prune', 'kb_online_prune_info',
+    'kb_set_shared_online_prune', 'kb_get_shared_online_prune', 'kb_shared_online_prune_info', 'kb_shared_online_prune_stage',
     'kb_deploy_ref',
     'kb_export_bytes', 'kb_export_agents', 'kb_agents_info', 'kb_import_agents', 'kb_agents_kernel_times',
     'kb_fork_rebuild', 'kb_get_rebuild', 'kb_rebuild_time_ms',
@@ -227,6 +228,10 @@ def load(dev=None):
     L.kb_set_online_prune.argtypes = [vp, C.c_int32, C.c_int32]
     L.kb_get_online_prune.argtypes = [vp, ip, ip]
     L.kb_online_prune_info.argtypes = [vp, up]
+    L.kb_set_shared_online_prune.argtypes = [vp, C.c_int32, C.c_int32]
+    L.kb_get_shared_online_prune.argtypes = [vp, ip, ip]
+    L.kb_shared_online_prune_info.argtypes = [vp, up]
+    L.kb_shared_online_prune_stage.argtypes = [vp]
     L.kb_fit.argtypes = [vp, ip, C.c_int32, i64p, dp, C.POINTER(C.c_int8), C.c_int32, ip, dp, ip, dp, ip]
     L.kb_score.argtypes = [vp, ip, C.c_int32, i64p, dp, dp, ip]
     L.kb_fit_time_ms.argtypes = [vp, dp, up]

@@ -911,17 +911,25 @@ class SharedVecKBRL(VecKBRL):
 
     `shared_plus_batch=M` (or set_shared_plus_batch()): under the margin rule, a dictionary of M <= m < capacity landmarks takes
     its merged list in segments between insertions, each with the chip-wide passes a full dictionary gets (kb_set_shared_plus_batch,
-    DESIGN.md section 8r); None is off.  `shared_plus_segments` segment rounds are enqueued per apply; the results do not depend on it."""
+    DESIGN.md section 8r); None is off.  `shared_plus_segments` segment rounds are enqueued per apply; the results do not depend on it.
+
+    `shared_online_prune=T` (or set_shared_online_prune()): every learning step ends on the device with a budget stage that takes
+    up to `shared_online_prune_rounds` landmarks from each dictionary above T by shrink()'s rule (kb_set_shared_online_prune,
+    DESIGN.md section 8t); None is off.  The keyword is kept until the first reset(), as VecKBRL(online_prune=) is."""
 
     def __init__(self, n_envs, dims, n_prbs, budget=64, max_rounds=4, exchange=None, shared_plus=False, shared_plus_batch=None,
-                 shared_plus_segments=4, **kw):
+                 shared_plus_segments=4, shared_online_prune=None, shared_online_prune_rounds=2, **kw):
         if kw.get('algorithm', 'projectron') != 'projectron':
             raise ValueError("SharedVecKBRL learns through its proposal rounds: algorithm=%r is not supported (the rounds learn by "
                              "the margin rule of 'projectron_plus' with shared_plus=True; or fit a per-replica VecKBRL, then "
                              "to_shared)" % kw['algorithm'])
         if kw.get('online_prune') is not None:
             raise ValueError("SharedVecKBRL holds no budget in the loop: online_prune=%r is not supported (prune() between steps "
-                             "brings its dictionaries down to a target; or run a per-replica VecKBRL with online_prune)" % (kw['online_prune'],))
+                             "brings its dictionaries down to a target; or run a per-replica VecKBRL with online_prune)"
+                             "; the shared handle's own switch is shared_online_prune=" % (kw['online_prune'],))
+        # (kb_set_shared_online_prune wants a reset handle: the keyword is kept and set by the first reset())
+        self._shared_online_prune_pending = ((int(shared_online_prune), int(shared_online_prune_rounds))
+                                             if shared_online_prune else None)   # (0 or None: off, nothing pending)
         super().__init__(n_envs, dims, n_prbs, shared=True, **kw)
         self.budget, self.max_rounds = budget, max_rounds
         self.exchange = exchange
@@ -963,6 +971,43 @@ class SharedVecKBRL(VecKBRL):
         w = (C.c_uint64 * 8)()
         self._check(self.L.kb_shared_plus_batch_info(self.h, w))
         return [int(v) for v in w]
+
+    def reset(self, initial_action, security_factor, seeds=None):
+        super().reset(initial_action, security_factor, seeds)
+        if getattr(self, '_shared_online_prune_pending', None):   # SharedVecKBRL(shared_online_prune=...): the handle's from here on
+            pending, self._shared_online_prune_pending = self._shared_online_prune_pending, None
+            self.set_shared_online_prune(*pending)
+
+    def set_shared_online_prune(self, target, rounds=2):
+        """the online budget of the shared handle (kb_set_shared_online_prune): from now on every learning
+        step -- update_control, step_resident -- ends on the device with a budget stage: every dictionary above `target` landmarks
+        loses min(excess, rounds) of them by shrink()'s rule, bit for bit, before select_action reads it; what is left above the
+        target the next stages take.  target None or 0: off (the default).  64 <= target <= capacity - 1; 1 <= rounds <= 64.
+        Call it after reset() (the constructor's shared_online_prune= is set by the first reset()), between steps.  A property of
+        this handle: checkpoints do not hold it, reset() and load_state() leave it alone, to_shared() makes a handle with it off.
+        Every rank of a group sets the same value before the same step; nothing checks it across ranks.  A dictionary the stage
+        cannot prune (a Kinv diagonal entry that is not finite and positive) stays as it is and every replica gets bit 32 of
+        flags().  pruned() counts the removals.  With `exchange` given, update_control enqueues the stage behind its rounds."""
+        self._check(self.L.kb_set_shared_online_prune(self.h, int(target or 0), int(rounds)))
+
+    @property
+    def shared_online_prune(self):
+        """None while the budget stage is off, else (target, rounds) (kb_get_shared_online_prune)"""
+        pending = getattr(self, '_shared_online_prune_pending', None)
+        if pending:
+            return pending
+        t, r = C.c_int32(), C.c_int32()
+        self._check(self.L.kb_get_shared_online_prune(self.h, C.byref(t), C.byref(r)))
+        return (t.value, r.value) if t.value else None
+
+    def shared_online_prune_info(self):
+        """the budget stages since reset / load_state, counted on the device (kb_shared_online_prune_info): online_prune_info()'s
+        entries -- stages enqueued, landmarks removed, carry (dictionary-stages left above the target), the largest excess a stage
+        met, the dictionaries flagged, and the downdate's bytes (read + written)"""
+        w = (C.c_uint64 * 8)()
+        self._check(self.L.kb_shared_online_prune_info(self.h, w))
+        return dict(stages=int(w[0]), removed=int(w[1]), carry=int(w[2]), max_excess=int(w[3]), flagged=int(w[4]),
+                    downdate_bytes=int(w[5]) * 16384)
 
     def fit(self, learners, X, y, chunk=0):
         """refused: the replicas' learners map to ONE dictionary per slice, so their sample lists are not independent sequences
@@ -1111,4 +1156,6 @@ class SharedVecKBRL(VecKBRL):
             acc = np.ascontiguousarray(taken[me], dtype=np.int32)
             self._check(self.L.kb_shared_commit(self.h, acc.ctypes.data_as(_ip)))
             self.rounds_last = rnd + 1
+        if self.shared_online_prune:   # (only the caller of the host-driven rounds knows that the step's rounds are over)
+            self._check(self.L.kb_shared_online_prune_stage(self.h))
         return hits

@@ -20,6 +20,9 @@ PRUNE_SHARED = ['prune_shared_choose_kernel', 'prune_shared_plan_kernel', 'prune
 # the online budget's kernels (kb_online_prune.hip): the stage's list and its persistent choose / move / finish
 # kernel, reported beside kb_prune's (whose plan and downdate the stage launches as they are) and held to no scratch as well
 ONLINE_PRUNE = ['budget_list_kernel', 'budget_round_kernel']
+# the same stage behind a shared learning step (kb_shared_online_prune.hip): its persistent choose / move / finish
+# kernel on full storage (the list kernel above and kb_shared_prune's plan and downdate are launched as they are): no scratch
+SHARED_ONLINE_PRUNE = ['shared_budget_round_kernel']
 # kb_deploy_ref's kernels (kb_ref.hip): reported, and held to no scratch at all, as they are built and documented
 REF_SCRATCH = {'select_ref_kernel': 0, 'ref_gather_kernel': 0}
 # the agent-file kernels (kb_agents.hip): reported, and held to no scratch at all -- pack and build are pure streaming kernels
@@ -161,7 +164,7 @@ def check(path=LOG):
                                                                            r.get('LDS Size')))
         if r.get('ScratchSize', 0) > 0:
             bad.append('%s spills %d B/lane (> 0)' % (key, r['ScratchSize']))
-    for key in ONLINE_PRUNE + AGENTS + BRIDGE + FORK:
+    for key in ONLINE_PRUNE + SHARED_ONLINE_PRUNE + AGENTS + BRIDGE + FORK:
         hit = [k for k in res if re.search(r'\d' + key, k)]  # (the whole mangled name: share_* is not unshare_*)
         if not hit:
             bad.append('%s: not found in %s' % (key, path))
